@@ -12,8 +12,14 @@ host memory; the timed region covers H2D of the raw bytes, GPU parse, host join,
 z-score / alerts, and the RCCL all-reduce of the fleet-wide per-service baseline (MFMA Gram pack) with the
 lock-step clock collective -- at every N, including N = 1, so per-rank work is the same at every N.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL over xGMI)
+
+A plain run sets up, warms up, times the K steps and prints one JSON result line (``ms_per_step``:
+the timed region divided by K).  The corpus, the z-score pre-history and the alert pre-history are
+seeded, so the same arguments give the same inputs in every run, and ``--dump-outputs DIR`` writes
+the records of the last timed step as ``DIR/<stream>.npy`` (see ``dump_outputs``) for comparing
+two builds output for output.  ``--full`` is where measurements beyond the headline belong.
 """
 from __future__ import annotations
 
@@ -58,6 +64,73 @@ PRESETS = {
     "firehose": {"servers": 32, "ejb": 2000, "providers": 1125, "tx_rate": 62.5, "ring": "bfloat16",
                  "ejb_pool": 64000, "provider_pool": 36000, "max_series": 3_000_000, "db_sink": "spool"},
 }
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # all files of one --dump-outputs together (the limit is 64 MB)
+
+
+def dump_outputs(dirpath, streams, budget=DUMP_BUDGET_BYTES):
+    """Write the records of the last timed step as ``<dirpath>/<stream>.npy`` (float64).
+
+    ``streams`` maps a stream name (db, audit_db, fs, fb, al, sx) to the text the engine handed
+    to that stream from the start of the last timed step to the end of the timed region: the
+    step's own tx / fs rows, and the fb / al rows that the fleet exchange and the node-wide alert
+    decision deliver one batch late, with those of the step itself from the final drain.
+    The records of a stream are sorted as bytes (the join's worker order is not part of the
+    result) and split at ``|``, ``:`` and ``&``.  A field that reads as a finite number is stored
+    as that number, any other field (server, service, log id, ``undefined``, ``NaN``) as the first
+    48 bits of its BLAKE2b digest, which a float64 holds exactly; short rows are padded with 0.
+    ``rows.npy`` holds the number of records per stream, in the sorted order of the stream names.
+    A stream without records gets no file.  Streams that do not fit into their share of
+    ``budget`` are cut to a fixed sample of rows (seeded, order kept).  Returns {file: shape}."""
+    import hashlib
+    import math
+    import re
+
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    split = re.compile(rb"[|:&]").split
+    seen = {}
+
+    def number(tok):
+        v = seen.get(tok)
+        if v is None:
+            try:
+                v = float(tok) if b"_" not in tok else math.nan
+            except ValueError:
+                v = math.nan
+            if not math.isfinite(v):
+                v = float(int.from_bytes(hashlib.blake2b(tok, digest_size=6).digest(), "big"))
+            seen[tok] = v
+        return v
+
+    names = sorted(streams)
+    rows = {k: sorted(l for l in streams[k].split(b"\n") if l) for k in names}
+    width = {k: max((len(split(l)) for l in rows[k]), default=0) for k in names}
+    size = {k: 8 * len(rows[k]) * width[k] for k in names}
+    left, keep = budget, {}
+    for n, k in enumerate(sorted(names, key=lambda k: size[k])):  # the small streams whole, the rest share
+        share = min(size[k], left // (len(names) - n))
+        keep[k] = len(rows[k]) if share == size[k] else share // (8 * width[k])
+        left -= 8 * keep[k] * width[k]
+    written = {}
+    for k in names:
+        if not rows[k]:
+            continue
+        pick = rows[k]
+        if keep[k] < len(pick):
+            idx = np.sort(np.random.default_rng(20200107).choice(len(pick), keep[k], replace=False))
+            pick = [pick[i] for i in idx]
+        a = np.zeros((len(pick), width[k]), dtype=np.float64)
+        for r, line in enumerate(pick):
+            t = split(line)
+            a[r, :len(t)] = [number(x) for x in t]
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+        written[k + ".npy"] = list(a.shape)
+    counts = np.array([len(rows[k]) for k in names], dtype=np.float64)
+    np.save(os.path.join(dirpath, "rows.npy"), counts)
+    written["rows.npy"] = list(counts.shape)
+    return written
 
 
 def main():
@@ -132,6 +205,15 @@ def main():
     ap.add_argument("--tail-read-threads", type=int, default=8, help="--path service: tailer pread threads")
     ap.add_argument("--rank-report", default=None,
                     help="directory: every rank writes rank<R>.json (its lines, node-wide counters, per-step times)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures or checks besides its headline figure.  A plain "
+                         "run sets up, warms up, times the steps and prints the result line; everything else "
+                         "(presets, the service path, traces, rank reports) already has an option of its own, so "
+                         "today --full adds no work")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step handed to its output streams as "
+                         "DIR/<stream>.npy (float64, one row per record, see dump_outputs; 1 GPU, --path memory, "
+                         "--db-sink none)")
     args = ap.parse_args()
     for k, v in PRESETS[args.preset].items():  # a preset overrides the defaults it names
         if getattr(args, k) == ap.get_default(k):
@@ -146,6 +228,8 @@ def main():
     if n_dev < 1:
         raise SystemExit("bench.py needs a GPU")
     device = local % n_dev
+    if args.dump_outputs and (world > 1 or args.path != "memory" or args.db_sink != "none"):
+        raise SystemExit("--dump-outputs needs one rank, --path memory and --db-sink none")
     coll = args.coll
     if coll == "auto":
         coll = "rccl" if world == 1 or local_world <= n_dev else "host"
@@ -252,23 +336,51 @@ def main():
         eng.add_file(path, {0: "SOAP", 1: "SERVER", 2: "APP"}[kind], server)
 
     # ---- corpus (untimed): warmup + steps batches of `batch_seconds` of log time, pinned
+    # The generator (one native thread per JVM, ~30 ms per batch of the headline shard) runs on a
+    # thread of its own from here on, next to the rest of the set-up, the pre-history batches and
+    # the warm-up, which wait only for the batches they feed; the timed steps start after its last
+    # batch.  Each batch is copied into pinned memory as it appears (blocks of 32 batches).
+    import threading
     n_batches = args.warmup + args.steps + PRE
     batches = []
-    total = 0
-    raw = []
-    t_gen = time.time()
-    for b in range(n_batches):
-        data, chunks = gen.generate(start + (b + 1) * step_ms, args.gen_threads)
-        raw.append((data, chunks))
-        total += len(data) + 64
-    pinned = N.alloc_pinned(total)
-    off = 0
-    for data, chunks in raw:
-        N.memcpy_to(pinned, data, off)
-        batches.append((pinned + off, len(data), chunks))
-        off += len(data) + 64
-    del raw
-    t_gen = time.time() - t_gen
+    pinned_blocks = []
+    gen_state = {"s": 0.0, "error": None}
+    gen_cv = threading.Condition()
+
+    def generate_corpus():
+        t_start = time.time()
+        try:
+            torch.cuda.set_device(device)  # the pinned blocks belong to this rank's device
+            room = off = 0
+            for b in range(n_batches):
+                data, chunks = gen.generate(start + (b + 1) * step_ms, args.gen_threads)
+                if len(data) + 64 > room - off:
+                    # (batches differ a little in size: an eighth of slack, and one that still
+                    # does not fit opens the next block)
+                    room = (len(data) + len(data) // 8 + 64) * min(32, n_batches - b)
+                    pinned_blocks.append(N.alloc_pinned(room))
+                    off = 0
+                N.memcpy_to(pinned_blocks[-1], data, off)
+                with gen_cv:
+                    batches.append((pinned_blocks[-1] + off, len(data), chunks))
+                    gen_cv.notify_all()
+                off += len(data) + 64
+        except BaseException as e:  # handed to the thread that waits for the batches
+            gen_state["error"] = e
+        gen_state["s"] = time.time() - t_start
+        with gen_cv:
+            gen_cv.notify_all()
+
+    gen_thread = threading.Thread(target=generate_corpus, name="corpus", daemon=True)
+    gen_thread.start()
+
+    def wait_batches(n):
+        """Until the first n batches of the corpus are in pinned memory."""
+        n = min(n, n_batches)
+        with gen_cv:
+            gen_cv.wait_for(lambda: len(batches) >= n or gen_state["error"] is not None)
+        if gen_state["error"] is not None:
+            raise gen_state["error"]
 
     # The fleet exchange (MFMA per-service Gram pack + RCCL all-reduce) and the lock-step clock
     # collective run at every N, so each rank does the same work at N = 1 and N = 8 (weak scaling).
@@ -325,10 +437,12 @@ def main():
 
     # ---- warmup (first batches create the series; then the z-score rings get a pre-history)
     for i in range(PRE):
+        wait_batches(i + 3)  # its own, the prefetched one and the one --stage-ahead copies
         step(i)
     if not args.no_warm:
         eng.eng.warm_history(12345 + rank)
     for i in range(PRE, PRE + args.warmup):
+        wait_batches(i + 3)
         step(i)
     eng.eng.flush()
     if args.anomaly_services > 0:
@@ -347,6 +461,9 @@ def main():
                if svc.split(":")[-1] in hot_by_server.setdefault(srv, hot_names(srv))]
         for li in range(len(eng.ecfg["lags"])):
             eng.eng.import_alert_counters(li, ser, [need] * len(ser))
+    wait_batches(n_batches)  # the whole corpus is in pinned memory before the timed steps
+    gen_thread.join()
+    t_gen = gen_state["s"]
     torch.cuda.synchronize()
     # Python's cyclic GC over the setup's garbage (the series export above: ~10^5 tuples) happens
     # here, not at some step of the timed loop; collections inside the loop are timed and reported
@@ -373,8 +490,17 @@ def main():
     gc.callbacks.append(_gc_cb)
     t0 = time.perf_counter()
     step_ms = []
+    hold_ms = 0.0
     for k, i in enumerate(range(PRE, PRE + args.warmup + args.steps)[args.warmup:]):
         cur_step[0] = k
+        if args.dump_outputs and i == last:
+            # --dump-outputs: what the earlier steps produced leaves for the sink now, and from here
+            # on the streams collect in the engine's memory (inside the timed region: hold_ms)
+            ts = time.perf_counter()
+            eng.eng.flush()
+            for name in outs:
+                eng.eng.set_sink_fd(name, -1)
+            hold_ms = 1000.0 * (time.perf_counter() - ts)
         ts = time.perf_counter()
         step(i)
         step_ms.append(1000.0 * (time.perf_counter() - ts))
@@ -398,7 +524,9 @@ def main():
     dt = time.perf_counter() - t0
     m1 = eng.metrics()
     lines = m1["lines"] - m0["lines"]
-    out_bytes = {k: eng.eng.sink_bytes(k) for k in outs}
+    held = {k: eng.eng.take_bytes(k) for k in outs} if args.dump_outputs else {}
+    out_bytes = {k: eng.eng.sink_bytes(k) + len(held.get(k, b"")) for k in outs}
+    dumped = dump_outputs(args.dump_outputs, held) if args.dump_outputs else None
     lat = sorted(m1["rollover_latency_ms"][len(m0["rollover_latency_ms"]):]) or [float("nan")]
     p50 = lat[len(lat) // 2]
     ss = sorted(step_ms)
@@ -503,14 +631,17 @@ def main():
                               "rows_per_s": round(st.get("rows", 0) / dt_max, 1), "failures": st.get("failures"),
                               "lanes": st.get("lanes")}
         if args.jmx:
-            out["sx_bytes"] = eng.eng.sink_bytes("sx")
+            out["sx_bytes"] = out_bytes["sx"]
+        if dumped is not None:
+            out["dump_outputs"] = {"files": dumped, "hold_ms": round(hold_ms, 3)}
         print(json.dumps(out), flush=True)
     if args.trace:
         eng.dump_trace(args.trace if world == 1 else f"{args.trace}.rank{rank}", pid=rank)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    N.free_pinned(pinned)
+    for block in pinned_blocks:
+        N.free_pinned(block)
     os.close(sink_fd)
     if inserter is not None:
         import shutil

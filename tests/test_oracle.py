@@ -1,5 +1,6 @@
 """The CPU oracle against (a) SURVEY Appendix B golden values and (b) the reference's own JS
-(executed under node through tests/js/ref_harness.js, byte-for-byte comparison)."""
+(its answers to tests/js/ref_harness.js, recorded under tests/golden/refjs/: byte-for-byte
+comparison, see tests/refjs.py)."""
 import copy
 import json
 import math
@@ -13,7 +14,6 @@ from apmbackend_amd.utils.config import default_config
 from apmbackend_amd.utils.records import FullStatEntry, StatEntry, TxEntry, entry_from_csv
 from apmbackend_amd.utils.synth import Anomaly, Generator, SynthConfig, batches, with_watermarks
 from apmbackend_amd.utils.timeparse import TzOffset
-from conftest import requires_reference
 
 UTC = TzOffset("UTC")
 
@@ -119,7 +119,6 @@ def _synth(seed=1, duration=300, servers=2, anomalies=()):
     return cfg, with_watermarks(batches(lines, cfg.start_ms, 5.0), UTC)
 
 
-@requires_reference
 @pytest.mark.parametrize("seed", [1, 2])
 def test_parse_matches_reference_js(seed):
     import refjs
@@ -137,7 +136,6 @@ def test_parse_matches_reference_js(seed):
     assert out == js["records"]
 
 
-@requires_reference
 def test_stats_zscore_alerts_match_reference_js():
     import refjs
     start = 1578391200000
@@ -162,7 +160,6 @@ def test_stats_zscore_alerts_match_reference_js():
     assert al == P.al and len(al) > 0
 
 
-@requires_reference
 def test_util_methods_match_reference_js():
     import random
     import refjs
@@ -179,7 +176,6 @@ def test_util_methods_match_reference_js():
         assert (mine is None and v is None) or mine == v
 
 
-@requires_reference
 def test_stats_nan_elapsed_matches_reference_js():
     """A tx whose elapsed is not a number (e.g. a CT exit line carrying 'time') is pushed as
     parseInt -> NaN: it counts toward tpm, poisons the average and lands wherever the JS
@@ -228,7 +224,6 @@ def test_js_average_float_view_path_is_the_same_left_to_right_sum():
     assert js_average(View([None, float("nan")])) is None
 
 
-@requires_reference
 def test_config_reload_oracle_matches_reference_js():
     """The oracle's reload (thresholds, a LAG added / removed / re-added, alert gates) against the
     reference's own watcher callbacks run on the same st / fs streams: updateAllServiceSettings +

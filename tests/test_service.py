@@ -31,6 +31,15 @@ def srv_of(p):
     return p.split("/")[-2]
 
 
+@pytest.fixture(autouse=True)
+def _outbox_in_tmp(tmp_path, monkeypatch):
+    """IngestService builds its notifier's Mailer with the default outbox, one fixed directory for
+    every user of a machine: the mails of these tests go to the test's own directory."""
+    from apmbackend_amd.runtime import notifier
+    sendmail, _outbox = notifier.Mailer.__init__.__defaults__
+    monkeypatch.setattr(notifier.Mailer.__init__, "__defaults__", (sendmail, str(tmp_path / "outbox")))
+
+
 def make_env(tmp_path, mode="inproc", servers=2, duration=400):
     an = [Anomaly("jvm00", "getSvc0001", START + 60_000, START + 350_000, 40.0)]
     sc = SynthConfig(servers=servers, duration_s=duration, tx_per_sec_per_server=3, seed=4, ejb_services=3,
@@ -46,6 +55,8 @@ def make_env(tmp_path, mode="inproc", servers=2, duration=400):
     C["streamParseTransactions"]["tailPauseFileFullPath"] = str(tmp_path / "PAUSE")
     C["streamParseTransactions"]["tailOffsetFileFullPath"] = str(tmp_path / "offsets.json")
     C["streamInsertDb"]["bufferResumeFileFullPath"] = str(tmp_path / "ins.resume")
+    C["streamInsertDb"]["copySinkDir"] = str(tmp_path / "copy")
+    C["grafana"]["renderDir"] = str(tmp_path / "renders")
     C["gpu"].update({"timezone": "UTC", "outputMode": mode, "tailFromStart": True})
     # files on disk: <tmp>/logs_in/<server>/<basename>
     mapping = {}
