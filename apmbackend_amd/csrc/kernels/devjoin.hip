@@ -31,6 +31,7 @@
 #include "devjoin_api.h"
 #include "devjoin_dev.h"
 #include "devscan.h"
+#include "prim.h"
 #include "textout.h"
 
 namespace apm {
@@ -39,20 +40,6 @@ using namespace dj;
 namespace {
 
 constexpr int TB = 256;
-
-// Op grouping by sort (APM_OPSORT=sort, the A/B form of the slot lists, DJArgs::slot_head).  Keys
-// are table slots [0, cap), cap (JOP_DIRECT) and cap + 1 (no op): table_bits + 1 bits; onesweep
-// with 11-bit digits (two passes up to 22 bits), 8-bit digits above.  (rocprim's default runs a
-// block sort + ~8 merge passes below 1M items: ~140 us per batch, profiles/r3_*.)
-using OpSortCfg = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
-                                             rocprim::default_config, 0>;
-using OpSortCfg11 = rocprim::radix_sort_config<
-    rocprim::default_config, rocprim::default_config,
-    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 8>, rocprim::kernel_config<1024, 8>, 11,
-                                        rocprim::block_radix_rank_algorithm::match>,
-    0>;
-static int op_sort_bits(int table_bits) { return table_bits + 1; }
-static bool opsort11(int table_bits) { return op_sort_bits(table_bits) <= 22; }
 
 __device__ __forceinline__ uint32_t grid_n(uint32_t n) { return (n + TB - 1) / TB; }
 
@@ -341,7 +328,8 @@ __device__ bool aud_fields(const Event& e, const uint8_t* __restrict__ p, uint64
 //   number (el, PRE_SOAP_VALID).
 // Returns -1: the host derives the event (needs_host), 0: nothing stored, 1: stored in f.
 enum : uint8_t { PRE_BAF = 1, PRE_BAF_VALID = 2, PRE_SOAP_VALID = 4 };
-// split(/<|>/)[2] of the ASCII-trimmed line [0, len) (dj::angle_field2), on the device: the
+// split(/<|>/)[2] of the ASCII-trimmed line [0, len) -- the field between the 2nd and 3rd
+// delimiter (join_util.h angle_field2 on the host) -- on the device: the
 // delimiters of each dword found exactly by SWAR over aligned 16-byte loads -- one load per 16
 // bytes instead of a dependent byte load per character (lane per SOAP line, ~100-200 bytes).
 __device__ __forceinline__ uint32_t zero_bytes(uint32_t x) {  // 0x80 in every zero byte of x
@@ -374,7 +362,7 @@ __device__ void angle_field2_dev(const uint8_t* __restrict__ p, int len, int& fs
   if (seen == 2) { fs = start; fe = b; }
 }
 
-__device__ int pre_fields(const Event& e, const uint8_t* __restrict__ p, AudF& f, bool bytewise) {
+__device__ int pre_fields(const Event& e, const uint8_t* __restrict__ p, AudF& f) {
   if (e.mask & PM_HOST) return -1;
   f.h_item = 0; f.el = apm_nan(); f.h_sw = 0; f.ts = apm_nan(); f.ref = 0; f.len = 0; f.flags = 0; f.pad = 0;
   if (e.kind >= LK_EJB_ENTRY && e.kind <= LK_CT_EXIT) {
@@ -406,8 +394,7 @@ __device__ int pre_fields(const Event& e, const uint8_t* __restrict__ p, AudF& f
     if (m & (PM_SOAP_ACCT | PM_SOAP_VALUE)) {
       if (!(m & PM_SOAP_ACCT) && (m & PM_SOAP_KEY)) return 0;  // KEY branch wins
       int fs, fe;
-      if (bytewise) angle_field2(p, (int)e.len, fs, fe);  // (APM_PRE_BYTEWISE: A/B switch)
-      else angle_field2_dev(p, (int)e.len, fs, fe);
+      angle_field2_dev(p, (int)e.len, fs, fe);
       if (fs >= 0) {
         while (fs < fe && (p[fs] == ' ' || (p[fs] >= 9 && p[fs] <= 13))) ++fs;
         while (fe > fs && (p[fe - 1] == ' ' || (p[fe - 1] >= 9 && p[fe - 1] <= 13))) --fe;
@@ -445,7 +432,7 @@ __device__ __forceinline__ SelCount sel_unpack(uint64_t v) {
 // the join side).  Now each lane first copies its line into an LDS slot with independent 16-byte
 // loads (all in flight at once: one memory latency per line), at the same offset modulo 16 so
 // the walks' aligned vector reads stay aligned, and walks it there.  Lines longer than a slot
-// (rare) walk the batch as before.  APM_HF_STAGE=0 keeps the unstaged walk (A/B).
+// (rare) walk the batch as before.
 constexpr int HF_SLOT = 256;  // staged bytes per lane
 // Slot pitch 272 B (68 dwords): with 256 B every lane's slot began on bank 0, so the 16 lanes of a
 // ds_read_b128 group reading the same 16-byte block of their lines hit the same 4 banks -- 16.04
@@ -462,7 +449,7 @@ __device__ __forceinline__ bool hf_needs_bytes(const Event& e) {
 }
 
 __device__ __forceinline__ uint8_t hf_fields(const Event& e, const uint8_t* __restrict__ p, uint64_t fkey, AudF* aud,
-                                             uint32_t i, int bytewise) {
+                                             uint32_t i) {
   uint8_t fl = 0;
   if (e.kind == LK_APP) {
     bool host = (e.mask & PM_HOST) != 0;
@@ -474,7 +461,7 @@ __device__ __forceinline__ uint8_t hf_fields(const Event& e, const uint8_t* __re
     if (host) fl |= SEL_HOST;
   } else {
     AudF f;
-    const int r = pre_fields(e, p, f, bytewise != 0);
+    const int r = pre_fields(e, p, f);
     if (r < 0) fl |= SEL_HOST;
     else if (r > 0) aud[i] = f;  // read by k_build_ops
   }
@@ -509,14 +496,14 @@ __device__ __forceinline__ uint8_t app_bits(const Event& e) {
 __device__ __forceinline__ uint8_t hf_event(const Event& e, uint32_t i, const uint8_t* __restrict__ bytes,
                                             const uint32_t* __restrict__ chunk_file,
                                             const uint64_t* __restrict__ file_fkey, AudF* __restrict__ aud,
-                                            uint8_t* stage, int bytewise, int staged) {
+                                            uint8_t* stage) {
   const uint64_t fkey = e.kind == LK_APP ? file_fkey[chunk_file[e.chunk]] : 0;
   // (staging only decides where the walk reads: a staged line is a complete copy, so the field
   // functions -- which read bytes only in the cases hf_needs_bytes names -- are unchanged)
   const uint8_t* p = bytes + e.off;
   const uint32_t lead = e.off & 15u;
   const uint32_t nvec = (lead + e.len + 15u) >> 4;
-  if (staged && hf_needs_bytes(e) && nvec * 16u <= (uint32_t)HF_SLOT) {
+  if (hf_needs_bytes(e) && nvec * 16u <= (uint32_t)HF_SLOT) {
     // the line's aligned 16-byte blocks, four loads in flight before their LDS stores (sixteen
     // held at once put the array on scratch: 272 B of private memory per lane)
     const uint4* __restrict__ src = reinterpret_cast<const uint4*>(bytes + (e.off - lead));
@@ -533,27 +520,21 @@ __device__ __forceinline__ uint8_t hf_event(const Event& e, uint32_t i, const ui
     }
     p = stage + threadIdx.x * HF_PITCH + lead;
   }
-  return (uint8_t)(hf_fields(e, p, fkey, aud, i, bytewise) | app_bits(e));
+  return (uint8_t)(hf_fields(e, p, fkey, aud, i) | app_bits(e));
 }
 
-// Host / audit selection flags per event.  `split` (default): events whose flags need their line's
-// bytes -- audit lines, SOAP request / account lines, CommonTiming exits with a BAF account, a
-// minority of the batch -- are listed instead (audit lines from the front of `list`, the others
-// from the back) and walked densely by k_host_flags_bytes; every other event is decided here
-// from its Event alone.  One lane per event over the whole batch made every wave execute each of
-// the walks its few byte events needed, the other lanes idle (the largest join-side kernel:
-// 137 us a batch, profiles/r5_final2).  split == 0: the one-pass form (APM_HF_SPLIT=0, A/B).
-template <bool SPLIT>
+// Host / audit selection flags per event.  Events whose flags need their line's bytes -- audit
+// lines, SOAP request / account lines, CommonTiming exits with a BAF account, a minority of the
+// batch -- are listed instead (audit lines from the front of `list`, the others from the back) and
+// walked densely by k_host_flags_bytes; every other event is decided here from its Event alone.
+// One lane per event over the whole batch made every wave execute each of the walks its few byte
+// events needed, the other lanes idle (the largest join-side kernel: 137 us a batch,
+// profiles/r5_final2).  (This kernel reads no bytes: no LDS stage, the occupancy is register-bound.)
 __global__ __launch_bounds__(TB) void k_host_flags(const Event* __restrict__ ev, const uint32_t* __restrict__ n_ev_dev,
-                                                   const uint8_t* __restrict__ bytes, const uint32_t* __restrict__ chunk_file,
-                                                   const uint64_t* __restrict__ file_fkey,
+                                                   const uint8_t* __restrict__ bytes,
                                                    uint8_t* __restrict__ flag, uint64_t* __restrict__ val,
                                                    AudF* __restrict__ aud, SelCount* __restrict__ totals, uint32_t cap,
-                                                   int bytewise, int staged, uint32_t* __restrict__ list,
-                                                   uint32_t* __restrict__ list_n) {
-  constexpr int split = SPLIT ? 1 : 0;
-  // (the split form reads no bytes: no LDS stage, so the occupancy is register-bound)
-  __shared__ __attribute__((aligned(16))) uint8_t stage[SPLIT ? 16 : TB * HF_PITCH];
+                                                   uint32_t* __restrict__ list, uint32_t* __restrict__ list_n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t n = min(*n_ev_dev, cap);
   if (blockIdx.x * blockDim.x >= n) return;  // (uniform per block: the grid is sized for the capacity)
@@ -563,19 +544,16 @@ __global__ __launch_bounds__(TB) void k_host_flags(const Event* __restrict__ ev,
   if (i < n) {
     e = ev[i];
     if (e.kind == LK_APP && (e.mask & (PM_AUTR_MAP | PM_SW_NAME))) ab = e.len;
-    defer = split && hf_needs_bytes(e);
+    defer = hf_needs_bytes(e);
     front = defer && e.kind == LK_APP;
   }
-  if (split) {  // (uniform: every lane takes part in both appends)
-    const uint32_t f = wave_append(front, &list_n[0]);
-    const uint32_t b = wave_append(defer && !front, &list_n[1]);
-    if (front) list[f] = i;
-    if (defer && !front) list[cap - 1 - b] = i;
-  }
+  // (every lane takes part in both appends)
+  const uint32_t f = wave_append(front, &list_n[0]);
+  const uint32_t b = wave_append(defer && !front, &list_n[1]);
+  if (front) list[f] = i;
+  if (defer && !front) list[cap - 1 - b] = i;
   if (i < n && !defer) {
-    uint8_t fl;
-    if constexpr (SPLIT) fl = (uint8_t)(hf_fields(e, bytes + e.off, 0, aud, i, bytewise) | app_bits(e));
-    else fl = hf_event(e, i, bytes, chunk_file, file_fkey, aud, stage, bytewise, staged);
+    const uint8_t fl = (uint8_t)(hf_fields(e, bytes + e.off, 0, aud, i) | app_bits(e));
     flag[i] = fl;
     val[i] = sel_pack(fl);
   }
@@ -590,7 +568,7 @@ __global__ __launch_bounds__(TB) void k_host_flags_bytes(const Event* __restrict
                                                          const uint32_t* __restrict__ chunk_file,
                                                          const uint64_t* __restrict__ file_fkey,
                                                          uint8_t* __restrict__ flag, uint64_t* __restrict__ val,
-                                                         AudF* __restrict__ aud, uint32_t cap, int bytewise, int staged,
+                                                         AudF* __restrict__ aud, uint32_t cap,
                                                          const uint32_t* __restrict__ list,
                                                          const uint32_t* __restrict__ list_n) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[TB * HF_PITCH];
@@ -601,7 +579,7 @@ __global__ __launch_bounds__(TB) void k_host_flags_bytes(const Event* __restrict
   if (t >= cap || (t >= nf && t < cap - nb)) return;
   const uint32_t i = list[t];
   const Event e = ev[i];
-  const uint8_t fl = hf_event(e, i, bytes, chunk_file, file_fkey, aud, stage, bytewise, staged);
+  const uint8_t fl = hf_event(e, i, bytes, chunk_file, file_fkey, aud, stage);
   flag[i] = fl;
   val[i] = sel_pack(fl);
 }
@@ -1206,12 +1184,9 @@ __global__ __launch_bounds__(TB) void k_claim(DJArgs a) {
     if (b && (threadIdx.x & (APM_WAVE - 1)) == lead) atomicAdd(&a.counts->n_keys_new, (uint32_t)__popcll(b));
   }
   a.op_slot[i] = key;
-  if (a.group_sort) {
-    a.op_idx[i] = i;
-  } else {  // push onto the key's list (the op that finds it empty leads the group)
-    if (i == 0) { a.big[0] = 0; a.big[1] = 0; }
-    a.op_idx[i] = key < cap ? atomicExch(&a.slot_head[key], i) : ~0u;
-  }
+  // push onto the key's list (the op that finds it empty leads the group)
+  if (i == 0) { a.big[0] = 0; a.big[1] = 0; }
+  a.op_idx[i] = key < cap ? atomicExch(&a.slot_head[key], i) : ~0u;
   if (op.op != JOP_NONE && (op.flags & JF_HAS_SVC)) {
     const uint64_t k = regkey_of(op.svc, op.server);
     uint32_t h = home_of(k, a.reg_mask);
@@ -1551,19 +1526,8 @@ __global__ __launch_bounds__(TB) void k_group_walk(DJArgs a) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.n_ev) return;
   const uint32_t cap = a.table_mask + 1;
-  if (a.group_sort) {
-    const uint32_t slot = a.op_slot_sorted[i];
-    if (slot > cap) return;  // no op
-    if (slot == cap) { walk_direct(a, a.op_idx_sorted[i]); return; }
-    if (i > 0 && a.op_slot_sorted[i - 1] == slot) return;  // not the first op of its key
-    uint32_t g = 1;
-    while (i + g < a.n_ev && a.op_slot_sorted[i + g] == slot) ++g;
-    const uint32_t* m = a.op_idx_sorted + i;
-    walk_group(a, slot, [m](uint32_t q) { return m[q]; }, g);
-    return;
-  }
   const uint32_t slot = a.op_slot[i];
-  if (slot > cap) return;
+  if (slot > cap) return;  // no op
   if (slot == cap) { walk_direct(a, i); return; }
   if (a.op_idx[i] != ~0u) return;  // not the group's leader (its list was not empty)
   GwRow m;
@@ -2548,66 +2512,47 @@ int apm_dj_take_marks(double* t, const char** names, int cap) {
   return k;
 }
 
-size_t apm_dj_tmp_bytes(uint32_t max_ev, uint32_t max_out, int table_bits) {
-  size_t a = 0, b = 0, c = 0, d = 0, e = 0;
-  const size_t n = std::max<size_t>(max_ev, 1) + 1;
-  HIP_OK(rocprim::exclusive_scan(nullptr, a, (uint8_t*)nullptr, (uint32_t*)nullptr, 0u, n, rocprim::plus<uint32_t>(),
-                                 (hipStream_t)0));
-  HIP_OK(rocprim::radix_sort_pairs<OpSortCfg>(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                   (uint32_t*)nullptr, n, 0, op_sort_bits(table_bits), (hipStream_t)0));
-  {
-    size_t b11 = 0;
-    HIP_OK(rocprim::radix_sort_pairs<OpSortCfg11>(nullptr, b11, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                  (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, op_sort_bits(table_bits),
-                                                  (hipStream_t)0));
-    b = std::max(b, b11);
-  }
-  HIP_OK(rocprim::radix_sort_pairs(nullptr, c, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
-                                   (uint32_t*)nullptr, n, 0, 64, (hipStream_t)0));
-  HIP_OK(rocprim::exclusive_scan(nullptr, d, (U4*)nullptr, (U4*)nullptr, U4{0, 0, 0, 0}, (size_t)max_out + 1, U4Plus(),
-                                 (hipStream_t)0));
-  HIP_OK(rocprim::inclusive_scan(nullptr, e, (int64_t*)nullptr, (int64_t*)nullptr, (size_t)max_out + 1,
-                                 rocprim::maximum<int64_t>(), (hipStream_t)0));
-  size_t f = 0;
-  HIP_OK(rocprim::exclusive_scan(nullptr, f, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n,
-                                 rocprim::plus<uint64_t>(), (hipStream_t)0));
-  return std::max(std::max(std::max(a, b), std::max(c, d)), std::max(e, f)) + 4096;
+// The join's device-wide primitives, each written once: the launchers pass the scratch, and
+// apm_dj_tmp_bytes passes a size-only PrimScratch and null data pointers.
+static int dj_sort_keys(PrimScratch& sc, const uint64_t* key, uint64_t* key_sorted, const uint32_t* val,
+                        uint32_t* val_sorted, size_t n, hipStream_t s) {
+  return prim_sort_pairs(sc, key, key_sorted, val, val_sorted, n, s);
+}
+static int dj_scan_counts(PrimScratch& sc, const uint32_t* cnt, uint32_t* pos, size_t n, hipStream_t s) {
+  return prim_exclusive_scan(sc, cnt, pos, 0u, n, rocprim::plus<uint32_t>(), s);
+}
+static int dj_scan_lens(PrimScratch& sc, const U4* lens, U4* offs, size_t n, hipStream_t s) {
+  return prim_exclusive_scan(sc, lens, offs, U4{0, 0, 0, 0}, n, U4Plus(), s);
+}
+static int dj_scan_bucket_max(PrimScratch& sc, const int64_t* bucket, int64_t* bmax, size_t n, hipStream_t s) {
+  return prim_inclusive_scan(sc, bucket, bmax, n, rocprim::maximum<int64_t>(), s);
 }
 
-static int pre_bytewise() {
-  static const int v = [] { const char* e = std::getenv("APM_PRE_BYTEWISE"); return e && e[0] == '1' ? 1 : 0; }();
-  return v;
+size_t apm_dj_tmp_bytes(uint32_t max_ev, uint32_t max_out) {
+  PrimScratch q;
+  const size_t n = std::max<size_t>(max_ev, 1) + 1;
+  dj_sort_keys(q, nullptr, nullptr, nullptr, nullptr, n, 0);
+  dj_scan_counts(q, nullptr, nullptr, n, 0);
+  dj_scan_lens(q, nullptr, nullptr, (size_t)max_out + 1, 0);
+  dj_scan_bucket_max(q, nullptr, nullptr, (size_t)max_out + 1, 0);
+  return q.need + 4096;
 }
-static int hf_split() {
-  static const int v = [] { const char* e = std::getenv("APM_HF_SPLIT"); return e && e[0] == '0' ? 0 : 1; }();
-  return v;
-}
-static int hf_staged() {
-  static const int v = [] { const char* e = std::getenv("APM_HF_STAGE"); return e && e[0] == '0' ? 0 : 1; }();
-  return v;
-}
+
 int apm_dj_select_host(DJArgs* a, const uint32_t* d_n_ev, uint32_t max_ev, hipStream_t s) {
   HIP_OK(hipMemsetAsync(a->n_host, 0, sizeof(SelCount), s));
   if (max_ev == 0) return 0;
   // the listed byte events: scratch in sel_pos (written by the selection scan only afterwards;
   // max_ev + 64 u64 words hold the max_ev u32 list entries and the two counts)
-  const int split = hf_split();
   uint32_t* list = reinterpret_cast<uint32_t*>(a->sel_pos);
   uint32_t* list_n = list + max_ev;
-  if (split) HIP_OK(hipMemsetAsync(list_n, 0, 8, s));
+  HIP_OK(hipMemsetAsync(list_n, 0, 8, s));
   const dim3 grid((max_ev + TB - 1) / TB);
-  if (split)
-    hipLaunchKernelGGL(k_host_flags<true>, grid, dim3(TB), 0, s, a->ev, d_n_ev, a->bytes, a->chunk_file, a->file_fkey,
-                       a->host_flag, a->sel_val, a->aud, a->n_host, max_ev, pre_bytewise(), hf_staged(), list, list_n);
-  else
-    hipLaunchKernelGGL(k_host_flags<false>, grid, dim3(TB), 0, s, a->ev, d_n_ev, a->bytes, a->chunk_file, a->file_fkey,
-                       a->host_flag, a->sel_val, a->aud, a->n_host, max_ev, pre_bytewise(), hf_staged(), list, list_n);
+  hipLaunchKernelGGL(k_host_flags, grid, dim3(TB), 0, s, a->ev, d_n_ev, a->bytes, a->host_flag, a->sel_val, a->aud,
+                     a->n_host, max_ev, list, list_n);
   dj_check(s, "k_host_flags");
-  if (split) {
-    hipLaunchKernelGGL(k_host_flags_bytes, grid, dim3(TB), 0, s, a->ev, a->bytes, a->chunk_file, a->file_fkey,
-                       a->host_flag, a->sel_val, a->aud, max_ev, pre_bytewise(), hf_staged(), list, list_n);
-    dj_check(s, "k_host_flags_bytes");
-  }
+  hipLaunchKernelGGL(k_host_flags_bytes, grid, dim3(TB), 0, s, a->ev, a->bytes, a->chunk_file, a->file_fkey,
+                     a->host_flag, a->sel_val, a->aud, max_ev, list, list_n);
+  dj_check(s, "k_host_flags_bytes");
   // sel_pos: the tile sums, then the packed total (sel_pos has max_ev + 64 entries)
   uint64_t* total = a->sel_pos + (max_ev + DS_TILE - 1) / DS_TILE + 1;
   if (ds_scan_apply<uint64_t>(SelValF{a->sel_val},
@@ -2627,12 +2572,8 @@ static int apm_dj_audit(DJArgs* a, bool filled, hipStream_t s) {
   if (N) {
     hipLaunchKernelGGL(k_aud_keys, dim3((N + TB - 1) / TB), dim3(TB), 0, s, *a);
     dj_check(s, "k_aud_keys");
-    size_t need = 0;
-    HIP_OK(rocprim::radix_sort_pairs(nullptr, need, a->aud_key, a->aud_key_sorted, a->aud_ord, a->aud_ord_sorted,
-                                     (size_t)N, 0, 64, s));
-    if (need > a->tmp_bytes) return -1;
-    HIP_OK(rocprim::radix_sort_pairs(a->tmp, need, a->aud_key, a->aud_key_sorted, a->aud_ord, a->aud_ord_sorted,
-                                     (size_t)N, 0, 64, s));
+    PrimScratch sc(a->tmp, a->tmp_bytes);
+    if (dj_sort_keys(sc, a->aud_key, a->aud_key_sorted, a->aud_ord, a->aud_ord_sorted, N, s) != 0) return -1;
     dj_check(s, "rocprim_radix_sort_pairs");
     hipLaunchKernelGGL(k_aud_autr, dim3((N + TB - 1) / TB), dim3(TB), 0, s, *a);
     dj_check(s, "k_aud_autr");
@@ -2652,7 +2593,7 @@ static int apm_dj_audit(DJArgs* a, bool filled, hipStream_t s) {
 
 int apm_dj_join(DJArgs* a, hipStream_t s) {
   const uint32_t n = a->n_ev;
-  const uint32_t cap = a->table_mask + 1;
+  PrimScratch sc(a->tmp, a->tmp_bytes);
   static_assert(offsetof(JoinCounts, ejb_unmatched) % 4 == 0, "JoinCounts zero range");
   const uint32_t zw = (uint32_t)(offsetof(JoinCounts, ejb_unmatched) / 4);
   if (n) {
@@ -2679,45 +2620,18 @@ int apm_dj_join(DJArgs* a, hipStream_t s) {
     dj_check(s, "k_soap_apply");
     hipLaunchKernelGGL(k_claim, dim3((n + TB - 1) / TB), dim3(TB), 0, s, *a);
     dj_check(s, "k_claim");
-    size_t need = 0;
-    if (!a->group_sort) {
-      // (slot lists: no sort)
-    } else if (opsort11(a->table_bits)) {
-      HIP_OK(rocprim::radix_sort_pairs<OpSortCfg11>(nullptr, need, a->op_slot, a->op_slot_sorted, a->op_idx,
-                                                    a->op_idx_sorted, (size_t)n, 0, op_sort_bits(a->table_bits), s));
-      if (need > a->tmp_bytes) return -1;
-      HIP_OK(rocprim::radix_sort_pairs<OpSortCfg11>(a->tmp, need, a->op_slot, a->op_slot_sorted, a->op_idx,
-                                                    a->op_idx_sorted, (size_t)n, 0, op_sort_bits(a->table_bits), s));
-    } else {
-      HIP_OK(rocprim::radix_sort_pairs<OpSortCfg>(nullptr, need, a->op_slot, a->op_slot_sorted, a->op_idx,
-                                                  a->op_idx_sorted, (size_t)n, 0, op_sort_bits(a->table_bits), s));
-      if (need > a->tmp_bytes) return -1;
-      HIP_OK(rocprim::radix_sort_pairs<OpSortCfg>(a->tmp, need, a->op_slot, a->op_slot_sorted, a->op_idx,
-                                                  a->op_idx_sorted, (size_t)n, 0, op_sort_bits(a->table_bits), s));
-    }
   }
-  (void)cap;
   // expiry first: its outputs precede every line emission, and it must read the expiring entries
   // before this batch's region allocations (disjoint by construction) and drains
   const uint32_t E = a->n_exp_entries;
   if (E) {
     hipLaunchKernelGGL(k_exp_keys, dim3((E + TB - 1) / TB), dim3(TB), 0, s, *a);
     dj_check(s, "k_exp_keys");
-    size_t need = 0;
-    HIP_OK(rocprim::radix_sort_pairs(nullptr, need, a->exp_key, a->exp_key_sorted, a->exp_idx, a->exp_idx_sorted,
-                                     (size_t)E, 0, 64, s));
-    if (need > a->tmp_bytes) return -1;
-    HIP_OK(rocprim::radix_sort_pairs(a->tmp, need, a->exp_key, a->exp_key_sorted, a->exp_idx, a->exp_idx_sorted,
-                                     (size_t)E, 0, 64, s));
+    if (dj_sort_keys(sc, a->exp_key, a->exp_key_sorted, a->exp_idx, a->exp_idx_sorted, E, s) != 0) return -1;
     dj_check(s, "rocprim_radix_sort_pairs");
     hipLaunchKernelGGL(k_exp_count, dim3((E + 1 + TB - 1) / TB), dim3(TB), 0, s, *a);
     dj_check(s, "k_exp_count");
-    need = 0;
-    HIP_OK(rocprim::exclusive_scan(nullptr, need, a->exp_cnt, a->exp_pos, 0u, (size_t)E + 1,
-                                   rocprim::plus<uint32_t>(), s));
-    if (need > a->tmp_bytes) return -1;
-    HIP_OK(rocprim::exclusive_scan(a->tmp, need, a->exp_cnt, a->exp_pos, 0u, (size_t)E + 1,
-                                   rocprim::plus<uint32_t>(), s));
+    if (dj_scan_counts(sc, a->exp_cnt, a->exp_pos, (size_t)E + 1, s) != 0) return -1;
     dj_check(s, "rocprim_exclusive_scan");
   }
   hipLaunchKernelGGL(k_exp_emit, dim3((std::max<uint32_t>(E, 1) + TB - 1) / TB), dim3(TB), 0, s, *a);
@@ -2725,16 +2639,10 @@ int apm_dj_join(DJArgs* a, hipStream_t s) {
   if (n) {
     hipLaunchKernelGGL(k_group_walk, dim3((n + TB - 1) / TB), dim3(TB), 0, s, *a);
     dj_check(s, "k_group_walk");
-    if (!a->group_sort) {  // (a few idle workgroups when no group is big)
-      hipLaunchKernelGGL(k_group_walk_big, dim3(32), dim3(GWB_THREADS), 0, s, *a);
-      dj_check(s, "k_group_walk_big");
-    }
-    size_t need = 0;
-    HIP_OK(rocprim::exclusive_scan(nullptr, need, a->out_cnt, a->out_pos, 0u, (size_t)n + 1,
-                                   rocprim::plus<uint32_t>(), s));
-    if (need > a->tmp_bytes) return -1;
-    HIP_OK(rocprim::exclusive_scan(a->tmp, need, a->out_cnt, a->out_pos, 0u, (size_t)n + 1,
-                                   rocprim::plus<uint32_t>(), s));
+    // (a few idle workgroups when no group is big)
+    hipLaunchKernelGGL(k_group_walk_big, dim3(32), dim3(GWB_THREADS), 0, s, *a);
+    dj_check(s, "k_group_walk_big");
+    if (dj_scan_counts(sc, a->out_cnt, a->out_pos, (size_t)n + 1, s) != 0) return -1;
     dj_check(s, "rocprim_exclusive_scan");
     hipLaunchKernelGGL(k_place, dim3((2 * n + TB - 1) / TB), dim3(TB), 0, s, *a);
     dj_check(s, "k_place");
@@ -2754,12 +2662,9 @@ int apm_dj_plan(DJFormatArgs* f, hipStream_t s) {
   const uint32_t n = f->n_out;
   hipLaunchKernelGGL(k_resolve_len, dim3((n + 1 + TB - 1) / TB), dim3(TB), 0, s, *f);
   dj_check(s, "k_resolve_len");
-  size_t need = 0;
-  U4* lens = reinterpret_cast<U4*>(f->lens);
-  U4* offs = reinterpret_cast<U4*>(f->offs);
-  HIP_OK(rocprim::exclusive_scan(nullptr, need, lens, offs, U4{0, 0, 0, 0}, (size_t)n + 1, U4Plus(), s));
-  if (need > f->tmp_bytes) return -1;
-  HIP_OK(rocprim::exclusive_scan(f->tmp, need, lens, offs, U4{0, 0, 0, 0}, (size_t)n + 1, U4Plus(), s));
+  PrimScratch sc(f->tmp, f->tmp_bytes);
+  if (dj_scan_lens(sc, reinterpret_cast<const U4*>(f->lens), reinterpret_cast<U4*>(f->offs), (size_t)n + 1, s) != 0)
+    return -1;
   dj_check(s, "rocprim_exclusive_scan (plan)");
   hipLaunchKernelGGL(k_plan_totals, dim3(1), dim3(1), 0, s, *f);
   dj_check(s, "k_plan_totals");
@@ -2774,10 +2679,8 @@ int apm_dj_write(DJFormatArgs* f, hipStream_t s) {
   if (!n) return 0;
   hipLaunchKernelGGL(k_write, dim3((n + TXW_LINES - 1) / TXW_LINES), dim3(TXW_THREADS), 0, s, *f);
   dj_check(s, "k_write");
-  size_t need = 0;
-  HIP_OK(rocprim::inclusive_scan(nullptr, need, f->tx_bucket, f->tx_bmax, (size_t)n, rocprim::maximum<int64_t>(), s));
-  if (need > f->tmp_bytes) return -1;
-  HIP_OK(rocprim::inclusive_scan(f->tmp, need, f->tx_bucket, f->tx_bmax, (size_t)n, rocprim::maximum<int64_t>(), s));
+  PrimScratch sc(f->tmp, f->tmp_bytes);
+  if (dj_scan_bucket_max(sc, f->tx_bucket, f->tx_bmax, (size_t)n, s) != 0) return -1;
   dj_check(s, "rocprim_inclusive_scan (bucket max)");
   hipLaunchKernelGGL(k_cands, dim3((n + TB - 1) / TB), dim3(TB), 0, s, *f);
   hipLaunchKernelGGL(k_reset_first, dim3((n + TB - 1) / TB), dim3(TB), 0, s, *f);
@@ -2791,16 +2694,22 @@ struct KeyLive {
 };
 }  // namespace
 
+static int dj_select_live(PrimScratch& sc, const KeyState* table, uint32_t cap, KeyState* out, uint32_t* d_n,
+                          hipStream_t s) {
+  return prim_select(sc, table, out, d_n, cap, KeyLive(), s);
+}
+
 size_t apm_dj_live_tmp_bytes(uint32_t cap) {
-  size_t b = 0;
-  HIP_OK(rocprim::select(nullptr, b, (const KeyState*)nullptr, (KeyState*)nullptr, (uint32_t*)nullptr, cap, KeyLive(),
-                         (hipStream_t)0));
-  return b;
+  PrimScratch q;
+  dj_select_live(q, nullptr, cap, nullptr, nullptr, 0);
+  return q.need;
 }
 
 void apm_dj_live_compact(const KeyState* table, uint32_t cap, KeyState* out, uint32_t* d_n, void* tmp,
                          size_t tmp_bytes, hipStream_t s) {
-  HIP_OK(rocprim::select(tmp, tmp_bytes, table, out, d_n, cap, KeyLive(), s));
+  PrimScratch sc(tmp, tmp_bytes);
+  if (dj_select_live(sc, table, cap, out, d_n, s) != 0)
+    throw std::runtime_error("live compaction: scratch smaller than apm_dj_live_tmp_bytes(cap)");
 }
 
 size_t apm_dj_rebuild_scratch_bytes(uint32_t cap) { return ((size_t)cap / RB_SEG + 1) * 4; }
@@ -2943,11 +2852,8 @@ void apm_dj_arena_grow(const NeedEnt* old, uint32_t old_cap, NeedEnt* fresh, uin
 int apm_dj_gather_plan(const int64_t* gid, int64_t n_upper, const int64_t* d_n, uint32_t* lens, uint32_t* offs,
                        void* tmp, size_t tmp_bytes, hipStream_t s) {
   hipLaunchKernelGGL(k_gather_len, dim3((unsigned)((n_upper + 1 + TB - 1) / TB)), dim3(TB), 0, s, gid, n_upper, d_n, lens);
-  size_t need = 0;
-  HIP_OK(rocprim::exclusive_scan(nullptr, need, lens, offs, 0u, (size_t)n_upper + 1, rocprim::plus<uint32_t>(), s));
-  if (need > tmp_bytes) return -1;
-  HIP_OK(rocprim::exclusive_scan(tmp, need, lens, offs, 0u, (size_t)n_upper + 1, rocprim::plus<uint32_t>(), s));
-  return 0;
+  PrimScratch sc(tmp, tmp_bytes);
+  return dj_scan_counts(sc, lens, offs, (size_t)n_upper + 1, s);
 }
 
 void apm_dj_gather_copy(const int64_t* gid, int64_t n, const char* ring, uint64_t ring_cap, const uint32_t* offs,

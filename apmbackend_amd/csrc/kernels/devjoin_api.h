@@ -106,18 +106,16 @@ struct DJArgs {
   uint32_t* seg_in;               // incoming state per segment
   uint64_t* chain_hash;           // per chunk: carried context hash of its file
   SoapState* soap_state;          // [max files] carried per file
-  // ---- grouping.  Default (slot lists): k_claim pushes each op onto its key's list
+  // ---- grouping (slot lists): k_claim pushes each op onto its key's list
   // (slot_head[slot] <- op, op_idx[op] = the previous head); the op that found the list empty
   // leads the group -- it collects and orders the members (k_group_walk; groups of more than
   // GW_SMALL ops go to k_group_walk_big, one workgroup each) and empties the list again.
-  // APM_OPSORT=sort: the stable radix sort of (slot, op) pairs (the round-4 form, for A/B).
   uint32_t* op_slot;              // [n_ev] table slot / DIRECT / NONE
-  uint32_t* op_slot_sorted;       // sort: sorted slots; lists: the big groups' leaders
-  uint32_t* op_idx;               // sort: op indices; lists: the next (earlier-pushed) member
-  uint32_t* op_idx_sorted;        // sort: sorted op indices; lists: the big groups' members
-  uint32_t* slot_head;            // lists: [table cap] list heads, ~0u between batches
-  uint32_t* big;                  // lists: [2] big groups, their members (zeroed by k_claim)
-  int group_sort;                 // 1: the radix-sort grouping
+  uint32_t* op_slot_sorted;       // the big groups' leaders
+  uint32_t* op_idx;               // the next (earlier-pushed) member of the op's list
+  uint32_t* op_idx_sorted;        // the big groups' members, sorted per group
+  uint32_t* slot_head;            // [table cap] list heads, ~0u between batches
+  uint32_t* big;                  // [2] big groups, their members (zeroed by k_claim)
   void* tmp;                      // rocprim scratch
   size_t tmp_bytes;
   KeyState* table;
@@ -126,7 +124,6 @@ struct DJArgs {
   // against 256 MB); only the winning slot's payload is read or initialised
   uint64_t* keys;
   uint32_t table_mask;
-  int table_bits;
   RegSlot* reg;
   uint32_t reg_mask;
   RegMiss* miss;
@@ -207,7 +204,7 @@ struct DJFormatArgs {
 }  // namespace apm
 
 extern "C" {
-size_t apm_dj_tmp_bytes(uint32_t max_ev, uint32_t max_out, int table_bits);
+size_t apm_dj_tmp_bytes(uint32_t max_ev, uint32_t max_out);
 // APM_DJ_MARKS=1: host clock (ms, steady clock) after each launch of the join chain since the
 // last call, with the launch names; returns the count (at most cap)
 int apm_dj_take_marks(double* t, const char** names, int cap);

@@ -199,21 +199,5 @@ __host__ __device__ inline int baf_account(const uint8_t* p, int a, int b, uint8
   return n;
 }
 
-// split(/<|>/)[2] of the ASCII-trimmed line [0, len): field between the 2nd and 3rd delimiter.
-__host__ __device__ inline void angle_field2(const uint8_t* p, int len, int& fs, int& fe) {
-  int a = 0, b = len;
-  while (a < b && (p[a] == ' ' || (p[a] >= 9 && p[a] <= 13))) ++a;
-  while (b > a && (p[b - 1] == ' ' || (p[b - 1] >= 9 && p[b - 1] <= 13))) --b;
-  int field = 0, start = a;
-  fs = fe = -1;
-  for (int i = a; i <= b; ++i) {
-    if (i == b || p[i] == '<' || p[i] == '>') {
-      if (field == 2) { fs = start; fe = i; return; }
-      ++field;
-      start = i + 1;
-    }
-  }
-}
-
 }  // namespace dj
 }  // namespace apm

@@ -16,7 +16,7 @@
 #include "devjoin_dev.h"
 #include "textout.h"
 
-#include <rocprim/rocprim.hpp>
+#include "prim.h"
 
 #include <cstdlib>
 
@@ -150,7 +150,7 @@ constexpr int FMT_WAVE_LINES = 64;
 // Stage layouts that avoid the stores' bank conflicts (odd-pitch per-line slots, rows rotated by
 // index: 0.6-0.7 conflict cycles per LDS instruction against 5.1-6.6 here) measured slower: more
 // LDS per block, or computed store addresses (no immediate offsets) that took the writer from 105
-// to 162 VGPRs (profiles/r5_q .. r5_u).  APM_FMT_STAGE=0 / 8 / 12 / 16 / 24 forces one.
+// to 162 VGPRs (profiles/r5_q .. r5_u).
 constexpr uint32_t FMT_LDS = 8192;
 
 __device__ __forceinline__ void wave_copy_out(const char* __restrict__ lds, char* __restrict__ out, uint32_t g0,
@@ -170,7 +170,7 @@ __device__ __forceinline__ void wave_copy_out(const char* __restrict__ lds, char
 
 template <uint32_t LDS>
 __global__ __launch_bounds__(FMT_WAVE_LINES) void k_format_write(FormatArgs a, int32_t st_blocks) {
-  __shared__ __align__(16) char stage[LDS ? LDS : 16];
+  __shared__ __align__(16) char stage[LDS];
   const bool is_st = (int32_t)blockIdx.x < st_blocks;
   const int32_t nl = is_st ? a.n : a.n * a.n_lags;
   const int32_t j0 = (is_st ? (int32_t)blockIdx.x : (int32_t)blockIdx.x - st_blocks) * FMT_WAVE_LINES;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(FMT_WAVE_LINES) void k_format_write(FormatArgs a, i
   const uint32_t* off = is_st ? a.st_off : a.fs_off;
   char* out = is_st ? a.st_out : a.fs_out;
   const uint32_t g0 = off[j0], g1 = off[j1];
-  const bool lds = LDS != 0 && (g1 - (g0 & ~3u)) <= LDS;  // uniform across the block
+  const bool lds = (g1 - (g0 & ~3u)) <= LDS;  // uniform across the block
   if (j < j1) {
     bool fb = false;
     OutT<true> o(lds ? stage + (off[j] - (g0 & ~3u)) : out + off[j]);
@@ -254,19 +254,12 @@ constexpr uint32_t FLEET_LDS = 16384;
 // Rows per wave (the other lanes carry none): a row's formatting is a long dependent chain per
 // lane, and 64 rows a wave left ~313 waves for the headline's 20k rows -- a third of the chip's
 // 1024 SIMDs with one latency-bound wave each (101 us isolated, profiles/r5_v).  16 rows a wave
-// put four times the waves in flight.  APM_FB_RPW (16 / 32 / 64) for A/B.
-int fleet_rows_per_wave() {
-  static const int v = [] {
-    const char* e = std::getenv("APM_FB_RPW");
-    const int r = e ? std::atoi(e) : 16;
-    return (r == 8 || r == 16 || r == 32 || r == 64) ? r : 16;
-  }();
-  return v;
-}
+// put four times the waves in flight.
+constexpr int FLEET_RPW = 16;
 
-__global__ __launch_bounds__(FMT_WAVE_LINES) void k_fleet_len(FleetFormatArgs a, int rpw) {
+__global__ __launch_bounds__(FMT_WAVE_LINES) void k_fleet_len(FleetFormatArgs a) {
   const int32_t n = a.n_slots * a.n_lags;
-  const int32_t i = (int)threadIdx.x < rpw ? (int32_t)blockIdx.x * rpw + (int32_t)threadIdx.x : n;
+  const int32_t i = (int)threadIdx.x < FLEET_RPW ? (int32_t)blockIdx.x * FLEET_RPW + (int32_t)threadIdx.x : n;
   bool fb = false;
   uint32_t len = i < n ? fleet_row<false>(a, i, nullptr, fb) : 0u;
   if (fb) atomicAdd(a.fallback, 1);  // (counted here only)
@@ -275,10 +268,10 @@ __global__ __launch_bounds__(FMT_WAVE_LINES) void k_fleet_len(FleetFormatArgs a,
   if (threadIdx.x == 0) a.status[blockIdx.x] = len;
 }
 
-__global__ __launch_bounds__(FMT_WAVE_LINES) void k_fleet_rows(FleetFormatArgs a, int rpw) {
+__global__ __launch_bounds__(FMT_WAVE_LINES) void k_fleet_rows(FleetFormatArgs a) {
   __shared__ __align__(16) char stage[FLEET_LDS];
   const int32_t n = a.n_slots * a.n_lags;
-  const int32_t i = (int)threadIdx.x < rpw ? (int32_t)blockIdx.x * rpw + (int32_t)threadIdx.x : n;
+  const int32_t i = (int)threadIdx.x < FLEET_RPW ? (int32_t)blockIdx.x * FLEET_RPW + (int32_t)threadIdx.x : n;
   const int lane = (int)threadIdx.x;
   bool fb = false;
   const uint32_t len = i < n ? fleet_row<false>(a, i, nullptr, fb) : 0u;
@@ -328,11 +321,14 @@ __global__ void k_fixed_batch(const double* x, int n, int f, char* out) {
 extern "C" {
 using namespace apm;
 
+static int fmt_scan_lens(PrimScratch& sc, const uint32_t* len, uint32_t* off, size_t n, hipStream_t stream) {
+  return prim_exclusive_scan(sc, len, off, 0u, n, rocprim::plus<uint32_t>(), stream);
+}
+
 size_t apm_format_tmp_bytes(int32_t n_max) {
-  size_t b = 0;
-  rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n_max + 1,
-                          rocprim::plus<uint32_t>(), (hipStream_t)0);
-  return b;
+  PrimScratch q;
+  fmt_scan_lens(q, nullptr, nullptr, (size_t)n_max + 1, 0);
+  return q.need;
 }
 
 // Lengths + scan: afterwards st_off/fs_off[0..n] hold exclusive offsets, [n] = total bytes.
@@ -342,15 +338,9 @@ int apm_format_plan(FormatArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stre
   // a->fallback accumulates (values beyond 2^127, printed inexactly) and is never reset here
   const int32_t lanes = a->n * a->n_lags + 1;  // >= n + 1 (n_lags >= 1)
   hipLaunchKernelGGL(k_format_len, dim3((lanes + 255) / 256), dim3(256), 0, stream, *a);
-  size_t need = tmp_bytes;
-  if (rocprim::exclusive_scan(tmp, need, a->st_len, a->st_off, 0u, (size_t)a->n + 1, rocprim::plus<uint32_t>(),
-                              stream) != hipSuccess)
-    return -1;
-  need = tmp_bytes;
-  if (rocprim::exclusive_scan(tmp, need, a->fs_len, a->fs_off, 0u, (size_t)a->n * a->n_lags + 1,
-                              rocprim::plus<uint32_t>(), stream) != hipSuccess)
-    return -1;
-  return 0;
+  PrimScratch sc(tmp, tmp_bytes);
+  if (fmt_scan_lens(sc, a->st_len, a->st_off, (size_t)a->n + 1, stream) != 0) return -1;
+  return fmt_scan_lens(sc, a->fs_len, a->fs_off, (size_t)a->n * a->n_lags + 1, stream);
 }
 
 // Test hook: nf(x[i], f) into 32-byte NUL-terminated slots.
@@ -359,8 +349,7 @@ void apm_format_fixed_batch(const double* d_x, int n, int f, char* d_out, hipStr
 }
 
 uint32_t apm_fleet_format_blocks(int32_t n_rows) {
-  const int32_t rpw = fleet_rows_per_wave();
-  return (uint32_t)((std::max<int32_t>(n_rows, 1) + rpw - 1) / rpw);
+  return (uint32_t)((std::max<int32_t>(n_rows, 1) + FLEET_RPW - 1) / FLEET_RPW);
 }
 
 // two launches; afterwards *a->total holds the bytes written (device)
@@ -371,9 +360,8 @@ void apm_fleet_format(FleetFormatArgs* a, hipStream_t stream) {
     return;
   }
   const dim3 grid(apm_fleet_format_blocks(n));
-  const int rpw = fleet_rows_per_wave();
-  hipLaunchKernelGGL(k_fleet_len, grid, dim3(FMT_WAVE_LINES), 0, stream, *a, rpw);
-  hipLaunchKernelGGL(k_fleet_rows, grid, dim3(FMT_WAVE_LINES), 0, stream, *a, rpw);
+  hipLaunchKernelGGL(k_fleet_len, grid, dim3(FMT_WAVE_LINES), 0, stream, *a);
+  hipLaunchKernelGGL(k_fleet_rows, grid, dim3(FMT_WAVE_LINES), 0, stream, *a);
 }
 
 void apm_format_write(FormatArgs* a, hipStream_t stream) {
@@ -382,14 +370,8 @@ void apm_format_write(FormatArgs* a, hipStream_t stream) {
   const int32_t fs_blocks = a->want_fs ? (a->n * a->n_lags + FMT_WAVE_LINES - 1) / FMT_WAVE_LINES : 0;
   const dim3 grid(st_blocks + fs_blocks);
   if (grid.x == 0) return;
-  static const int forced = [] {
-    const char* e = std::getenv("APM_FMT_STAGE");  // diagnostic: stage KB (0 = no LDS stage)
-    return e ? std::atoi(e) : -1;
-  }();
-  const uint32_t want = forced >= 0 ? (uint32_t)forced * 1024u : (a->stage_hint ? a->stage_hint : 12288u);
-  if (forced == 0)
-    hipLaunchKernelGGL(k_format_write<0>, grid, dim3(FMT_WAVE_LINES), 0, stream, *a, st_blocks);
-  else if (want <= 7168)
+  const uint32_t want = a->stage_hint ? a->stage_hint : 12288u;
+  if (want <= 7168)
     hipLaunchKernelGGL(k_format_write<FMT_LDS>, grid, dim3(FMT_WAVE_LINES), 0, stream, *a, st_blocks);
   else if (want <= 12800)
     hipLaunchKernelGGL(k_format_write<12288>, grid, dim3(FMT_WAVE_LINES), 0, stream, *a, st_blocks);

@@ -16,7 +16,7 @@
 // host copy (runtime/devjoin.cpp).
 #include "kernel_api.h"
 
-#include <rocprim/rocprim.hpp>
+#include "prim.h"
 
 #include "devscan.h"
 
@@ -1225,12 +1225,9 @@ int apm_parse_batch(const uint8_t* d_bytes, uint64_t n_bytes, const uint32_t* d_
   const uint32_t nl_blocks = (tiles + NL_PER - 1) / NL_PER;
   hipLaunchKernelGGL(k_nl_count, dim3(nl_blocks), dim3(NL_BLOCK), 0, stream, d_bytes, n_bytes, tile_counts,
                      const_cast<uint8_t*>(d_bytes) + n_bytes, tiles);
-  size_t tmp_bytes = 0;
-  HIP_OK(rocprim::exclusive_scan(nullptr, tmp_bytes, tile_counts, tile_off, 0u, tiles + 1,
-                                 rocprim::plus<uint32_t>(), stream));
-  if (tmp_bytes > APM_SCAN_TMP) return -1;
-  HIP_OK(rocprim::exclusive_scan(scan_tmp, tmp_bytes, tile_counts, tile_off, 0u, tiles + 1,
-                                 rocprim::plus<uint32_t>(), stream));
+  PrimScratch sc(scan_tmp, APM_SCAN_TMP);
+  if (prim_exclusive_scan(sc, tile_counts, tile_off, 0u, (size_t)tiles + 1, rocprim::plus<uint32_t>(), stream) != 0)
+    return -1;
   hipLaunchKernelGGL(k_nl_write, dim3(nl_blocks), dim3(NL_BLOCK), 0, stream, d_bytes, n_bytes, tile_off, line_end,
                      d_n_lines, tiles);
 

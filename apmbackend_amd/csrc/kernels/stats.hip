@@ -19,7 +19,7 @@
 // instead of a scan of the whole list per series.
 #include "kernel_api.h"
 
-#include <rocprim/rocprim.hpp>
+#include "prim.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(WS_WAVES * APM_WAVE) void k_window_stats(WindowArgs
   }
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  if (n <= APM_WAVE && !a.lds_sort) {
+  if (n <= APM_WAVE) {
     // The usual window (~20 samples): one sample per lane, a bitonic network over the lanes in
     // registers -- 21 shuffle + min/max steps, no LDS round trips or wave barriers (the LDS
     // network padded every series to 64 and cost 21 LDS passes; profiles/r4_pm: 100 us per
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(WS_WAVES * APM_WAVE) void k_window_stats(WindowArgs
 // prefix scans / sorting network run 32 lanes wide (5 + 15 shuffle steps instead of 6 + 21, each
 // step serving two series).  Windows of at most 32 samples (nearly all) are sorted in registers;
 // up to 512 by the half in LDS; larger ones go to the block pass, NaN windows to the JS pass.
-// APM_K8_H2=0 keeps the one-series-per-wave kernel (A/B).
+// Wider windows keep the one-series-per-wave kernel (k_window_stats).
 constexpr int HW = 32;                 // lanes per series
 constexpr int H2_TILE = WS_TILE / 2;   // samples per half in LDS
 
@@ -546,23 +546,6 @@ __device__ __forceinline__ void half_sort_regs(int32_t* t, int n, int hl) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 }
 
-__device__ inline void half_bitonic(int32_t* a, int n, int hl) {
-  for (int k = 2; k <= n; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = hl; i < n; i += HW) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const int32_t x = a[i], y = a[ixj];
-          const bool up = (i & k) == 0;
-          if ((x > y) == up) { a[i] = y; a[ixj] = x; }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    }
-  }
-}
-
 __global__ __launch_bounds__(WS_WAVES * APM_WAVE) void k_window_stats_h2(WindowArgs a) {
   __shared__ int32_t tile[WS_WAVES * 2][H2_TILE];
   const int lane = threadIdx.x & 63;
@@ -664,15 +647,8 @@ __global__ __launch_bounds__(WS_WAVES * APM_WAVE) void k_window_stats_h2(WindowA
     }
     return;
   }
-  // 32 < n <= 512: this half sorts its tile in registers (APM_K8_LDS=2: the LDS network, A/B)
-  if (a.lds_sort == 2) {
-    int np2 = HW;
-    while (np2 < n) np2 <<= 1;
-    for (int i = n + hl; i < np2; i += HW) t[i] = 0x7fffffff;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    half_bitonic(t, np2, hl);
-  } else if (n <= 2 * HW) {
+  // 32 < n <= 512: this half sorts its tile in registers
+  if (n <= 2 * HW) {
     half_sort_regs<2>(t, n, hl);
   } else if (n <= 4 * HW) {
     half_sort_regs<4>(t, n, hl);
@@ -1131,8 +1107,7 @@ void apm_nan_mark(const TxRec* d_tx, uint32_t n, StatsState* st, hipStream_t str
 
 // big_n / nan_n must be zero on entry (the engine clears them with the rollover's other counters)
 void apm_window_stats(WindowArgs* a, hipStream_t stream) {
-  static const bool h2 = [] { const char* e = std::getenv("APM_K8_H2"); return !(e && e[0] == '0'); }();
-  if (h2 && a->n_win <= HW && a->lds_sort != 1) {
+  if (a->n_win <= HW) {
     const int blocks2 = (a->n_series + 2 * WS_WAVES - 1) / (2 * WS_WAVES);
     if (blocks2 == 0) return;
     hipLaunchKernelGGL(k_window_stats_h2, dim3(blocks2), dim3(WS_WAVES * APM_WAVE), 0, stream, *a);
@@ -1159,29 +1134,28 @@ int key_bits(int32_t S) {
 }
 }  // namespace
 
-size_t apm_spill_sort_tmp_bytes(int32_t spill_cap, int32_t S, int32_t nslot) {
-  size_t need = 0;
+// (series, value) pairs of every slot's spill list sorted by series; spill_n == nullptr (the size
+// query): empty segments
+static int spill_sort(PrimScratch& sc, int32_t spill_cap, int32_t S, int32_t nslot, const int32_t* spill_n,
+                      const int32_t* series, int32_t* series_out, const int32_t* val, int32_t* val_out,
+                      hipStream_t stream) {
   const auto beg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0), SpillOff{nullptr, spill_cap});
-  const auto end = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0), SpillOff{nullptr, spill_cap});
-  HIP_OK(rocprim::segmented_radix_sort_pairs(nullptr, need, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
-                                             (int32_t*)nullptr, (size_t)nslot * spill_cap, (unsigned)nslot, beg, end, 0,
-                                             key_bits(S), (hipStream_t)0));
-  return need + 4096;
+  const auto end = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0), SpillOff{spill_n, spill_cap});
+  return prim_segmented_sort_pairs(sc, series, series_out, val, val_out, (size_t)nslot * spill_cap, (unsigned)nslot, beg,
+                                   end, 0, key_bits(S), stream);
+}
+
+size_t apm_spill_sort_tmp_bytes(int32_t spill_cap, int32_t S, int32_t nslot) {
+  PrimScratch q;
+  spill_sort(q, spill_cap, S, nslot, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+  return q.need + 4096;
 }
 
 int apm_spill_sort(const StatsState* st, int32_t* series_out, int32_t* val_out, void* tmp, size_t tmp_bytes,
                    hipStream_t stream) {
-  size_t need = 0;
-  const auto beg = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0), SpillOff{nullptr, st->spill_cap});
-  const auto end = rocprim::make_transform_iterator(rocprim::make_counting_iterator(0), SpillOff{st->spill_n, st->spill_cap});
-  HIP_OK(rocprim::segmented_radix_sort_pairs(nullptr, need, st->spill_series, series_out, st->spill_val, val_out,
-                                             (size_t)st->nslot * st->spill_cap, (unsigned)st->nslot, beg, end, 0, key_bits(st->S),
-                                             stream));
-  if (need > tmp_bytes) return -1;
-  HIP_OK(rocprim::segmented_radix_sort_pairs(tmp, need, st->spill_series, series_out, st->spill_val, val_out,
-                                             (size_t)st->nslot * st->spill_cap, (unsigned)st->nslot, beg, end, 0, key_bits(st->S),
-                                             stream));
-  return 0;
+  PrimScratch sc(tmp, tmp_bytes);
+  return spill_sort(sc, st->spill_cap, st->S, st->nslot, st->spill_n, st->spill_series, series_out, st->spill_val,
+                    val_out, stream);
 }
 
 void apm_pool_append(const TxRec* d_tx, uint32_t lo, uint32_t hi, const int64_t* d_gid, int64_t* tail_end,
@@ -1191,43 +1165,38 @@ void apm_pool_append(const TxRec* d_tx, uint32_t lo, uint32_t hi, const int64_t*
                      tail_end, tail_gid, base);
 }
 
-size_t apm_release_tmp_bytes(int64_t cap) {
-  size_t a = 0, b = 0;
-  HIP_OK(rocprim::radix_sort_pairs(nullptr, a, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr,
-                                   (int64_t*)nullptr, (size_t)cap, 0, 64, (hipStream_t)0));
-  HIP_OK(rocprim::merge(nullptr, b, (int64_t*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr,
-                        (int64_t*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr, (size_t)cap, (size_t)cap,
-                        rocprim::less<int64_t>(), (hipStream_t)0));
-  return std::max(a, b) + 4096;
+// out = merge(pool[0..n_pool), sort(tail[0..n_tail)))   (stable: pool entries first on ties)
+static int release_merge(PrimScratch& sc, const int64_t* pool_end, const int64_t* pool_gid, int64_t n_pool,
+                         const int64_t* tail_end, const int64_t* tail_gid, int64_t n_tail, int64_t* sort_end,
+                         int64_t* sort_gid, int64_t* out_end, int64_t* out_gid, hipStream_t stream) {
+  if (n_tail > 0 && prim_sort_pairs(sc, tail_end, sort_end, tail_gid, sort_gid, (size_t)n_tail, stream) != 0) return -1;
+  if (n_pool + n_tail == 0) return 0;
+  return prim_merge(sc, pool_end, (const int64_t*)sort_end, out_end, pool_gid, (const int64_t*)sort_gid, out_gid,
+                    (size_t)n_pool, (size_t)n_tail, rocprim::less<int64_t>(), stream);
 }
 
-// out = merge(pool[0..n_pool), sort(tail[0..n_tail)))   (stable: pool entries first on ties)
+size_t apm_release_tmp_bytes(int64_t cap) {
+  PrimScratch q;
+  release_merge(q, nullptr, nullptr, cap, nullptr, nullptr, cap, nullptr, nullptr, nullptr, nullptr, 0);
+  return q.need + 4096;
+}
+
 int apm_release_merge(const int64_t* pool_end, const int64_t* pool_gid, int64_t n_pool, const int64_t* tail_end,
                       const int64_t* tail_gid, int64_t n_tail, int64_t* sort_end, int64_t* sort_gid,
                       int64_t* out_end, int64_t* out_gid, void* tmp, size_t tmp_bytes, hipStream_t stream) {
-  size_t need = 0;
-  if (n_tail > 0) {
-    HIP_OK(rocprim::radix_sort_pairs(nullptr, need, tail_end, sort_end, tail_gid, sort_gid, (size_t)n_tail, 0, 64,
-                                     stream));
-    if (need > tmp_bytes) return -1;
-    HIP_OK(rocprim::radix_sort_pairs(tmp, need, tail_end, sort_end, tail_gid, sort_gid, (size_t)n_tail, 0, 64,
-                                     stream));
-  }
-  if (n_pool + n_tail == 0) return 0;
-  HIP_OK(rocprim::merge(nullptr, need, pool_end, sort_end, out_end, pool_gid, sort_gid, out_gid, (size_t)n_pool,
-                        (size_t)n_tail, rocprim::less<int64_t>(), stream));
-  if (need > tmp_bytes) return -1;
-  HIP_OK(rocprim::merge(tmp, need, pool_end, sort_end, out_end, pool_gid, sort_gid, out_gid, (size_t)n_pool,
-                        (size_t)n_tail, rocprim::less<int64_t>(), stream));
-  return 0;
+  PrimScratch sc(tmp, tmp_bytes);
+  return release_merge(sc, pool_end, pool_gid, n_pool, tail_end, tail_gid, n_tail, sort_end, sort_gid, out_end, out_gid,
+                       stream);
 }
 
+static int ck_scan_lens(PrimScratch& sc, const uint32_t* lens, uint32_t* offs, size_t n, hipStream_t s) {
+  return prim_exclusive_scan(sc, lens, offs, 0u, n, rocprim::plus<uint32_t>(), s);
+}
 
 size_t apm_ck_pack_tmp_bytes(uint64_t n_entries) {
-  size_t b = 0;
-  HIP_OK(rocprim::exclusive_scan(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n_entries + 1,
-                                 rocprim::plus<uint32_t>(), (hipStream_t)0));
-  return b;
+  PrimScratch q;
+  ck_scan_lens(q, nullptr, nullptr, (size_t)n_entries + 1, 0);
+  return q.need;
 }
 
 int apm_ck_pack_cells(const int32_t* counts, const int32_t* cells, const int32_t* d_slots, int k, int32_t n, int32_t S,
@@ -1235,10 +1204,8 @@ int apm_ck_pack_cells(const int32_t* counts, const int32_t* cells, const int32_t
                       hipStream_t s) {
   const uint64_t N = (uint64_t)k * n;
   hipLaunchKernelGGL(k_ck_lens, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, counts, d_slots, k, n, S, cap, lens);
-  size_t need = 0;
-  HIP_OK(rocprim::exclusive_scan(nullptr, need, lens, offs, 0u, (size_t)N + 1, rocprim::plus<uint32_t>(), s));
-  if (need > tmp_bytes) return -1;
-  HIP_OK(rocprim::exclusive_scan(tmp, need, lens, offs, 0u, (size_t)N + 1, rocprim::plus<uint32_t>(), s));
+  PrimScratch sc(tmp, tmp_bytes);
+  if (ck_scan_lens(sc, lens, offs, (size_t)N + 1, s) != 0) return -1;
   if (N) hipLaunchKernelGGL(k_ck_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, cells, d_slots, k, n, S, cap, lens, offs, packed);
   return 0;
 }

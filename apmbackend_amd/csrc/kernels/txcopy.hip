@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include <rocprim/rocprim.hpp>
+#include "prim.h"
 
 #include "devjoin_api.h"
 #include "devjoin_dev.h"
@@ -233,15 +233,22 @@ __global__ __launch_bounds__(TC_TB) void k_txcopy_write(const int64_t* __restric
 
 using namespace apm;
 
+static int txcopy_scan_lens(PrimScratch& sc, const uint32_t* lens, uint32_t* offs, size_t n, hipStream_t s) {
+  return prim_exclusive_scan(sc, lens, offs, 0u, n, rocprim::plus<uint32_t>(), s);
+}
+// scratch bytes of the plan's scan over n lines
+static size_t txcopy_tmp_bytes(int64_t n) {
+  PrimScratch q;
+  txcopy_scan_lens(q, nullptr, nullptr, (size_t)n + 1, 0);
+  return q.need;
+}
+
 int apm_dj_txcopy_plan(const int64_t* gid, int64_t n_upper, const int64_t* d_n, const char* ring, uint64_t ring_cap,
                        uint32_t* lens, uint32_t* offs, uint32_t* fb_count, void* tmp, size_t tmp_bytes, hipStream_t s) {
   hipLaunchKernelGGL(k_txcopy_len, dim3((unsigned)((n_upper + 1 + TC_TB - 1) / TC_TB)), dim3(TC_TB), 0, s, gid, n_upper,
                      d_n, ring, ring_cap, lens, fb_count);
-  size_t need = 0;
-  HIP_OK(rocprim::exclusive_scan(nullptr, need, lens, offs, 0u, (size_t)n_upper + 1, rocprim::plus<uint32_t>(), s));
-  if (need > tmp_bytes) return -1;
-  HIP_OK(rocprim::exclusive_scan(tmp, need, lens, offs, 0u, (size_t)n_upper + 1, rocprim::plus<uint32_t>(), s));
-  return 0;
+  PrimScratch sc(tmp, tmp_bytes);
+  return txcopy_scan_lens(sc, lens, offs, (size_t)n_upper + 1, s);
 }
 
 void apm_dj_txcopy_write(const int64_t* gid, int64_t n, const char* ring, uint64_t ring_cap, const uint32_t* offs,
@@ -271,8 +278,7 @@ int apm_txcopy_lines(const char* d_text, const uint64_t* h_line_off, int64_t n, 
   HIP_OK(hipMalloc(&d_fb, 4));
   HIP_OK(hipMemset(d_fb, 0, 4));
   HIP_OK(hipMemcpy(d_gid, h_gid.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-  size_t need = 0;
-  HIP_OK(rocprim::exclusive_scan(nullptr, need, d_lens, d_offs, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), 0));
+  const size_t need = txcopy_tmp_bytes(n);
   void* tmp = nullptr;
   HIP_OK(hipMalloc(&tmp, need + 256));
   if (apm_dj_txcopy_plan(d_gid, n, nullptr, d_text, cap, d_lens, d_offs, d_fb, tmp, need + 256, 0) != 0)
@@ -332,8 +338,7 @@ std::vector<double> apm_release_bench(int64_t n, int iters, uint64_t seed) {
   HIP_OK(hipMalloc(&d_fb, 4));
   HIP_OK(hipMemset(d_fb, 0, 4));
   HIP_OK(hipMalloc(&d_out, text.size() * 3 + 64));
-  size_t need = 0;
-  HIP_OK(rocprim::exclusive_scan(nullptr, need, d_lens, d_offs, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), 0));
+  const size_t need = txcopy_tmp_bytes(n);
   void* tmp = nullptr;
   HIP_OK(hipMalloc(&tmp, need + 256));
   hipStream_t st;

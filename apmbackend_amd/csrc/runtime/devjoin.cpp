@@ -106,8 +106,7 @@ DeviceJoin::DeviceJoin(const DevJoinConfig& cfg, Dictionary* dict, const std::ve
     s.d_tx_gid = (int64_t*)dmalloc((size_t)out_cap_ * 8);
     HIP_OK(hipEventCreateWithFlags(&s.free_ev, hipEventDisableTiming));
   }
-  table_bits_ = cfg_.table_bits;
-  table_cap_ = 1u << table_bits_;
+  table_cap_ = 1u << cfg_.table_bits;
   init_table_cap_ = table_cap_;
   init_arena_cap_ = cfg_.arena_cap;
   d_table_ = (KeyState*)dmalloc((size_t)table_cap_ * sizeof(KeyState));
@@ -157,7 +156,7 @@ DeviceJoin::DeviceJoin(const DevJoinConfig& cfg, Dictionary* dict, const std::ve
   HIP_OK(hipHostMalloc((void**)&h_cand_bucket_, (size_t)out_cap_ * 8, hipHostMallocDefault));
   HIP_OK(hipHostMalloc((void**)&h_unres_, (size_t)out_cap_ * 8, hipHostMallocDefault));
   ensure_tmp();
-  sel_tmp_bytes_ = apm_dj_tmp_bytes(E, 1024, 8);
+  sel_tmp_bytes_ = apm_dj_tmp_bytes(E, 1024);
   d_sel_tmp_ = dmalloc(sel_tmp_bytes_);
   d_counts_ = (JoinCounts*)dmalloc(sizeof(JoinCounts));
   HIP_OK(hipHostMalloc((void**)&h_counts_, sizeof(JoinCounts), hipHostMallocDefault));
@@ -198,10 +197,6 @@ DeviceJoin::DeviceJoin(const DevJoinConfig& cfg, Dictionary* dict, const std::ve
   d_ring_ = (char*)dmalloc(cfg_.ring_bytes);
   d_ring_pos_ = (uint64_t*)dmalloc(8);
   d_big_ = (uint32_t*)dmalloc(8);
-  {
-    const char* e = std::getenv("APM_OPSORT");
-    group_sort_ = e && std::strcmp(e, "sort") == 0;
-  }
   HIP_OK(hipStreamSynchronize(stream_));
 }
 
@@ -697,7 +692,7 @@ void DeviceJoin::release_slot(int k, hipStream_t stats_stream) {
 
 void DeviceJoin::ensure_tmp() {
   const uint32_t E = std::max<uint32_t>(cfg_.max_events, 1024);
-  const size_t need = std::max(apm_dj_tmp_bytes(E, out_cap_, table_bits_), apm_dj_tmp_bytes(cfg_.arena_cap, out_cap_, table_bits_));
+  const size_t need = std::max(apm_dj_tmp_bytes(E, out_cap_), apm_dj_tmp_bytes(cfg_.arena_cap, out_cap_));
   if (need <= tmp_bytes_ && d_tmp_) return;
   if (d_tmp_) {
     HIP_OK(hipStreamSynchronize(stream_));
@@ -707,13 +702,11 @@ void DeviceJoin::ensure_tmp() {
   d_tmp_ = dmalloc(tmp_bytes_);
 }
 
-// Reinsert the live keys (acct / record not expired, or a live need entry) into a clean table of
-// `new_cap` slots.  Same size: the spare buffer (no allocation on the ingest path).
+// Drop the dead keys (the live ones: acct / record not expired, or a live need entry).  Same size:
+// in place; another size: the live keys are reinserted into a clean table of `new_cap` slots.
 void DeviceJoin::rebuild_table(double now, uint32_t new_cap) {
   hipStream_t st = stream_;
-  KeyState* fresh;
-  const bool same = new_cap == table_cap_;
-  if (same && !rebuild_copy()) {  // in place (apm_dj_rebuild_inplace), then wait for the count
+  if (new_cap == table_cap_) {  // in place (apm_dj_rebuild_inplace), then wait for the count
     rebuild_inplace(now);
     sync_keys();
     HIP_OK(hipMemcpyAsync(h_live_, d_live_, 8, hipMemcpyDeviceToHost, st));
@@ -724,32 +717,23 @@ void DeviceJoin::rebuild_table(double now, uint32_t new_cap) {
     ++table_rebuilds_;
     return;
   }
-  if (same && d_table_spare_) fresh = d_table_spare_;
-  else fresh = (KeyState*)dmalloc((size_t)new_cap * sizeof(KeyState));
+  KeyState* fresh = (KeyState*)dmalloc((size_t)new_cap * sizeof(KeyState));
   HIP_OK(hipMemsetAsync(fresh, 0, (size_t)new_cap * sizeof(KeyState), st));
   HIP_OK(hipMemsetAsync(d_live_, 0, 8, st));
   apm_dj_rebuild(d_table_, table_cap_, fresh, new_cap - 1, d_arena_, cfg_.arena_cap, now, d_counts_, d_live_, d_pool_,
                  d_pool_ring_, pool_n_ - 1, st);
   HIP_OK(hipMemcpyAsync(h_live_, d_live_, 8, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
-  if (same) {
-    d_table_spare_ = d_table_;
-    spare_clean_ = false;
-  } else {
-    dfree(d_table_, (size_t)table_cap_ * sizeof(KeyState));
-    if (d_table_spare_) dfree(d_table_spare_, (size_t)table_cap_ * sizeof(KeyState));
-    d_table_spare_ = nullptr;
-    ++table_grows_;
-  }
+  dfree(d_table_, (size_t)table_cap_ * sizeof(KeyState));
+  if (d_table_spare_) dfree(d_table_spare_, (size_t)table_cap_ * sizeof(KeyState));
+  d_table_spare_ = nullptr;
+  ++table_grows_;
   d_table_ = fresh;
   table_cap_ = new_cap;
-  table_bits_ = 0;
-  while ((1u << table_bits_) < table_cap_) ++table_bits_;
   keys_live_ = *h_live_;
   keys_since_rebuild_ = 0;
   live_pending_ = false;
   ++table_rebuilds_;
-  ensure_tmp();  // the grouping sort's key width follows the table
   sync_keys();
 }
 
@@ -771,12 +755,7 @@ void DeviceJoin::sync_keys() {
 // with the batch's own syncs and is read at the next capacity check.  (A synchronous rebuild
 // stalled the ingest thread ~0.5 ms every ~32 batches at the headline rate: the p99 step.)  It
 // compacts the table's clusters in place (apm_dj_rebuild_inplace): no second table to zero and
-// fill.  APM_REBUILD_COPY=1 keeps the reinsert-into-the-spare form (A/B).
-bool DeviceJoin::rebuild_copy() {
-  static const bool copy = [] { const char* e = std::getenv("APM_REBUILD_COPY"); return e && e[0] == '1'; }();
-  return copy;
-}
-
+// fill.
 void DeviceJoin::rebuild_inplace(double now) {
   const size_t need = apm_dj_rebuild_scratch_bytes(table_cap_);
   if (need > rb_scratch_bytes_) {
@@ -791,19 +770,7 @@ void DeviceJoin::rebuild_inplace(double now) {
 
 void DeviceJoin::rebuild_table_async(double now) {
   hipStream_t st = stream_;
-  if (rebuild_copy()) {
-    HIP_OK(hipMemsetAsync(d_live_, 0, 8, st));
-    KeyState* fresh = d_table_spare_;
-    if (!fresh) fresh = (KeyState*)dmalloc((size_t)table_cap_ * sizeof(KeyState));  // (zeroed)
-    else if (!spare_clean_) HIP_OK(hipMemsetAsync(fresh, 0, (size_t)table_cap_ * sizeof(KeyState), st));
-    apm_dj_rebuild(d_table_, table_cap_, fresh, table_cap_ - 1, d_arena_, cfg_.arena_cap, now, d_counts_, d_live_,
-                   d_pool_, d_pool_ring_, pool_n_ - 1, st);
-    d_table_spare_ = d_table_;  // (zeroed later, in an idle gap of the join stream)
-    spare_clean_ = false;
-    d_table_ = fresh;
-  } else {
-    rebuild_inplace(now);
-  }
+  rebuild_inplace(now);
   sync_keys();  // (the join stream's idle gap, with the rebuild)
   HIP_OK(hipMemcpyAsync(h_live_, d_live_, 8, hipMemcpyDeviceToHost, st));
   if (!live_ev_) HIP_OK(hipEventCreateWithFlags(&live_ev_, hipEventDisableTiming));
@@ -816,21 +783,12 @@ void DeviceJoin::rebuild_table_async(double now) {
 // After a batch's last sync the join stream idles while the host finishes the batch (hand-off,
 // clocks) and starts the next one: the key table's upkeep runs there instead of in front of the
 // next batch's kernels -- the rebuild when the next batch (estimated as large as this one) would
-// trigger it, else zeroing the spare table so a later rebuild skips its memset.  The clock is
-// this batch's: only entries expired at it are dropped (later expiries are checked by the kernels).
+// trigger it.  The clock is this batch's: only entries expired at it are dropped (later expiries
+// are checked by the kernels).
 void DeviceJoin::idle_upkeep(double now, uint32_t n_next) {
-  static const int mode = [] {  // APM_IDLE_UPKEEP: 0 off, 1 spare zeroing only, 2 (default) + rebuild
-    const char* e = std::getenv("APM_IDLE_UPKEEP");
-    return e ? std::atoi(e) : 2;
-  }();
-  if (mode == 0 || live_pending_) return;  // (a rebuild's count is still unread)
-  if (mode >= 2 && (keys_live_ + keys_since_rebuild_ + n_next) * 2 > table_cap_ && table_rebuilds_ > 0 &&
-      async_rebuild_fits(n_next)) {
+  if (live_pending_) return;  // (a rebuild's count is still unread)
+  if ((keys_live_ + keys_since_rebuild_ + n_next) * 2 > table_cap_ && table_rebuilds_ > 0 && async_rebuild_fits(n_next))
     rebuild_table_async(now);
-  } else if (rebuild_copy() && d_table_spare_ && !spare_clean_) {
-    HIP_OK(hipMemsetAsync(d_table_spare_, 0, (size_t)table_cap_ * sizeof(KeyState), stream_));
-    spare_clean_ = true;
-  }
 }
 
 // Need entries at virtual [lo, arena_head_) move to the same virtual slots of a bigger ring; the
@@ -983,13 +941,13 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
   if (hops_.size() > h_hops_cap_) {
     if (h_hops_) HIP_OK(hipHostFree(h_hops_));
     h_hops_cap_ = hops_.size() * 2 + 65536;
-    HIP_OK(hipHostMalloc((void**)&h_hops_, h_hops_cap_ * sizeof(HostOp), host_flags_()));
+    HIP_OK(hipHostMalloc((void**)&h_hops_, h_hops_cap_ * sizeof(HostOp), hipHostMallocDefault));
     HIP_OK(hipHostGetDevicePointer((void**)&hd_hops_, h_hops_, 0));
   }
   if (hbuf_.size() > h_hbuf_cap_) {
     if (h_hbuf_) HIP_OK(hipHostFree(h_hbuf_));
     h_hbuf_cap_ = hbuf_.size() * 2 + (4 << 20);
-    HIP_OK(hipHostMalloc((void**)&h_hbuf_, h_hbuf_cap_, host_flags_()));
+    HIP_OK(hipHostMalloc((void**)&h_hbuf_, h_hbuf_cap_, hipHostMallocDefault));
     HIP_OK(hipHostGetDevicePointer((void**)&hd_hbuf_, h_hbuf_, 0));
   }
   span("u.hostgrow");
@@ -1068,15 +1026,15 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
   a.soap_state = d_soap_;
   a.op_slot = d_op_slot_; a.op_slot_sorted = d_op_slot_sorted_; a.op_idx = d_op_idx_; a.op_idx_sorted = d_op_idx_sorted_;
   a.tmp = d_tmp_; a.tmp_bytes = tmp_bytes_;
-  if (!group_sort_ && heads_cap_ != table_cap_) {  // (the join stream is ordered after any rebuild)
+  if (heads_cap_ != table_cap_) {  // (the join stream is ordered after any rebuild)
     if (d_slot_head_) { HIP_OK(hipStreamSynchronize(st)); dfree(d_slot_head_, (size_t)heads_cap_ * 4); }
     d_slot_head_ = (uint32_t*)dmalloc((size_t)table_cap_ * 4);
     HIP_OK(hipMemsetAsync(d_slot_head_, 0xff, (size_t)table_cap_ * 4, st));
     heads_cap_ = table_cap_;
   }
-  a.slot_head = d_slot_head_; a.big = d_big_; a.group_sort = group_sort_ ? 1 : 0;
+  a.slot_head = d_slot_head_; a.big = d_big_;
   if (keys_stale_ || keys_cap_ != table_cap_) sync_keys();
-  a.table = d_table_; a.keys = d_keys_; a.table_mask = table_cap_ - 1; a.table_bits = table_bits_;
+  a.table = d_table_; a.keys = d_keys_; a.table_mask = table_cap_ - 1;
   a.pool = d_pool_; a.pool_ring = d_pool_ring_; a.pool_mask = pool_n_ - 1;
   a.reg = d_reg_; a.reg_mask = (1u << cfg_.reg_bits) - 1; a.miss = d_miss_; a.miss_cap = miss_cap_;
   a.arena = d_arena_; a.arena_cap = cfg_.arena_cap; a.arena_base = arena_head_; a.arena_limit = arena_limit;
@@ -1103,7 +1061,7 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
       d_aud_ord_sorted_ = (uint32_t*)dmalloc((size_t)aud_key_cap_ * 4);
     }
     if (N > std::max<uint32_t>(cfg_.max_events, cfg_.arena_cap)) {  // the key sort's scratch
-      const size_t need = apm_dj_tmp_bytes(N, out_cap_, table_bits_);
+      const size_t need = apm_dj_tmp_bytes(N, out_cap_);
       if (need > tmp_bytes_) {
         HIP_OK(hipStreamSynchronize(st));
         dfree(d_tmp_, tmp_bytes_);
@@ -1196,22 +1154,6 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
   };
   auto write_and_copy = [&] {
     if (apm_dj_write(&f, st) != 0) throw std::runtime_error("device join: scan scratch too small");
-    static const bool seg = [] {  // A/B: APM_DJ_SEGCOPY=0 -> a blit per array
-      const char* e = std::getenv("APM_DJ_SEGCOPY");
-      return !e || std::atoi(e) != 0;
-    }();
-    if (!seg) {
-      if (spec) {
-        HIP_OK(hipMemcpyAsync(h_cand_, d_cand_, (size_t)spec * 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_cand_bucket_, d_cand_bucket_, (size_t)spec * 8, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(h_unres_, d_unres_, (size_t)spec * 8, hipMemcpyDeviceToHost, st));
-      }
-      if (spec_tx) HIP_OK(hipMemcpyAsync(h_txt_, d_txt_tx_, spec_tx, hipMemcpyDeviceToHost, st));
-      if (spec_db) HIP_OK(hipMemcpyAsync(h_txt_ + spec_tx, d_txt_db_, spec_db, hipMemcpyDeviceToHost, st));
-      HIP_OK(hipMemcpyAsync(h_counts_, d_counts_, sizeof(JoinCounts), hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));  // ---- sync C
-      return;
-    }
     CopySegs cs;
     if (spec) {
       cs.add(mapped(h_cand_), d_cand_, (size_t)spec * 4);
@@ -1331,10 +1273,9 @@ size_t DeviceJoin::trim(double now) {
     const uint64_t want = std::max<uint64_t>(init_table_cap_, pow2_at_least(std::max<uint64_t>(keys_live_ * 4, 8)));
     if (want < table_cap_) rebuild_table(now, (uint32_t)want);  // reinserts into a fresh, smaller table
   }
-  if (d_table_spare_) {  // (re-made on demand: checkpoint compaction, APM_REBUILD_COPY)
+  if (d_table_spare_) {  // (re-made on demand by the checkpoint's compaction)
     dfree(d_table_spare_, (size_t)table_cap_ * sizeof(KeyState));
     d_table_spare_ = nullptr;
-    spare_clean_ = false;
   }
   if (d_slot_head_) {  // sized by the table: re-made by the next batch
     dfree(d_slot_head_, (size_t)heads_cap_ * 4);
@@ -1458,9 +1399,6 @@ void DeviceJoin::save_tables(BinWriter& w) {
     live_off = w.mem_pos();
     write_dev(w, out, (size_t)n_live * sizeof(KeyState), st, h_ck_bounce_, kCkBounce);
     HIP_OK(hipFree(tmp));
-    // (the compaction scratch: only the reinsert rebuild (APM_REBUILD_COPY=1) targets the spare
-    // and needs it zeroed again; the in-place rebuild never reads it)
-    if (rebuild_copy()) spare_clean_ = false;
   }
   span("ck.j.table");
   // needNumRecordCache regions + their arena entries (arena capacity first: the table's `need`
@@ -1653,8 +1591,6 @@ void DeviceJoin::load(BinReader& rd) {
       if (d_table_spare_) dfree(d_table_spare_, (size_t)table_cap_ * sizeof(KeyState));
       d_table_spare_ = nullptr;
       table_cap_ = (uint32_t)cap;
-      table_bits_ = 0;
-      while ((1u << table_bits_) < table_cap_) ++table_bits_;
       d_table_ = (KeyState*)dmalloc((size_t)table_cap_ * sizeof(KeyState));
       ensure_tmp();
     } else {

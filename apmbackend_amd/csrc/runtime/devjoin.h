@@ -211,7 +211,6 @@ class DeviceJoin {
   }
   void ensure_rest(uint32_t n_ev, uint64_t bytes);  // ensure_capacity after the key table
   void rebuild_inplace(double now);                  // same-size rebuild, queued (count -> d_live_)
-  static bool rebuild_copy();                        // APM_REBUILD_COPY=1: reinsert into the spare (A/B)
   void idle_upkeep(double now, uint32_t n_next);    // end of a batch: table upkeep while the host works
   void grow_arena(uint32_t new_cap, uint64_t lo);
   void grow_pool(uint64_t need_free);
@@ -225,15 +224,6 @@ class DeviceJoin {
   const std::vector<FileInfo>* files_;
   const std::vector<std::string>* servers_;
   hipStream_t stream_ = nullptr;  // join stream
-  // flags of the host-op staging (read by a kernel over the host link): APM_HOPS_NC=1 allocates it
-  // non-coherent (the GPU may then fetch whole cache lines)
-  static unsigned host_flags_() {
-    static const unsigned f = [] {
-      const char* e = std::getenv("APM_HOPS_NC");
-      return (e && e[0] == '1') ? (unsigned)hipHostMallocNonCoherent : (unsigned)hipHostMallocDefault;
-    }();
-    return f;
-  }
   size_t device_bytes_ = 0;
   uint8_t* d_stage_bytes_ = nullptr;  // two-ahead H2D target (d_stage / swap_stage)
   std::vector<void*> allocs_;
@@ -275,13 +265,11 @@ class DeviceJoin {
   uint32_t cstats_cap_ = 0, cstats_last_cap_ = 0;
   hipEvent_t cstats_ev_ = nullptr;
   bool cstats_pending_ = false, cstats_have_ = false;
-  KeyState* d_table_spare_ = nullptr;  // same-size rebuild target (no allocation per rebuild)
+  KeyState* d_table_spare_ = nullptr;  // the checkpoint's compaction target (kept between checkpoints)
   uint32_t table_cap_ = 0;
-  int table_bits_ = 0;
   uint64_t keys_since_rebuild_ = 0, keys_live_ = 0;
   bool live_pending_ = false;  // an in-order rebuild's live count is on its way to h_live_
   hipEvent_t live_ev_ = nullptr;  // recorded after that count's D2H
-  bool spare_clean_ = false;   // d_table_spare_ is zeroed (the next rebuild skips its memset)
   uint32_t* d_rb_scratch_ = nullptr;  // per-segment cluster starts of the in-place rebuild
   size_t rb_scratch_bytes_ = 0;
   uint8_t* d_pool_ = nullptr;          // chain blocks
@@ -364,7 +352,6 @@ class DeviceJoin {
   uint32_t* d_slot_head_ = nullptr;
   uint32_t heads_cap_ = 0;
   uint32_t* d_big_ = nullptr;
-  bool group_sort_ = false;  // APM_OPSORT=sort
   uint64_t write_regrows_ = 0;      // write passes redone after the text staging grew
   void ensure_txt(size_t bytes);
   void* d_tmp_ = nullptr;

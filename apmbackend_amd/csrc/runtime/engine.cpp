@@ -345,15 +345,8 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     HIP_OK(hipHostMalloc((void**)&ps.h_watermark, 8, hipHostMallocDefault));
     if (dev()) continue;  // the device join keeps events on the GPU
     HIP_OK(hipHostMalloc((void**)&ps.h_events, (size_t)cfg_.max_lines * sizeof(Event), hipHostMallocDefault));
-    // APM_EVENTS_ZEROCOPY=1: the compaction kernel writes the events straight into this pinned
-    // slot (the copy rides along with the prefetched parse) instead of a 15 MB D2H the ingest
-    // thread waits for.  Measured A/B on MI355X (tools/ab_env.sh, 4 alternating rounds): -0.3 ms
-    // parse but +0.3 ms host join (the join then reads lines the GPU wrote over PCIe), i.e. no
-    // net change, so the DMA copy stays the default.
-    const char* zc = std::getenv("APM_EVENTS_ZEROCOPY");
-    void* dp = nullptr;
-    if (zc && std::atoi(zc) != 0 && hipHostGetDevicePointer(&dp, ps.h_events, 0) == hipSuccess)
-      ps.d_events_host = (Event*)dp;
+    // (Writing the events straight into this pinned slot from the compaction kernel was measured:
+    // -0.3 ms parse, +0.3 ms host join reading lines the GPU wrote over PCIe.  The DMA copy stays.)
   }
   d_parse_ws_ = dmalloc(apm_parse_workspace_bytes(cfg_.max_batch_bytes, cfg_.max_lines, cfg_.max_chunks));
   if (!dev()) d_events_ = (Event*)dmalloc((size_t)cfg_.max_lines * sizeof(Event));
@@ -431,20 +424,8 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   HIP_OK(hipHostMalloc((void**)&h_fmt_meta_, 64, hipHostMallocDefault));
   HIP_OK(hipHostGetDevicePointer((void**)&hd_fmt_meta_, h_fmt_meta_, 0));
   {
-    const char* e = std::getenv("APM_FMT_HOST");
-    fmt_host_ = e && e[0] == '1';
     const char* f = std::getenv("APM_TXCOPY_FORCE_FALLBACK");
     txcopy_force_fb_ = f && f[0] == '1';
-    const char* d = std::getenv("APM_D2H_KERNEL");
-    d2h_kernel_ = d && d[0] == '1';
-    const char* rl = std::getenv("APM_REL_LANE");
-    rel_lane_on_ = !(rl && rl[0] == '0');
-    const char* sp = std::getenv("APM_D2H_SPLIT");
-    d2h_split_ = sp ? std::max(1, std::atoi(sp)) : 1;
-    const char* sd = std::getenv("APM_D2H_SDMA");
-    d2h_sdma_ = sd && sd[0] == '1';
-    const char* b = std::getenv("APM_D2H_BLOCKS");
-    d2h_blocks_ = b ? (uint32_t)std::max(1, std::atoi(b)) : 32u;
   }
   // alerts
   d_alerts_ = (AlertRec*)dmalloc((size_t)cfg_.max_alerts * sizeof(AlertRec));
@@ -473,7 +454,7 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_pool_gid_[i] = (int64_t*)dmalloc((size_t)cfg_.pool_cap * 8);
   }
   release_tmp_bytes_ = apm_release_tmp_bytes(cfg_.pool_cap);
-  if (dev()) release_tmp_bytes_ = std::max(release_tmp_bytes_, apm_dj_tmp_bytes((uint32_t)cfg_.pool_cap + 2, 1024, 8));
+  if (dev()) release_tmp_bytes_ = std::max(release_tmp_bytes_, apm_dj_tmp_bytes((uint32_t)cfg_.pool_cap + 2, 1024));
   d_release_tmp_ = dmalloc(release_tmp_bytes_);
   for (int k = 0; k < 2; ++k) {
     HIP_OK(hipHostMalloc((void**)&h_release_gid_[k], (size_t)cfg_.pool_cap * 8, hipHostMallocDefault));
@@ -501,11 +482,8 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   // The rollover lane mode is fixed before the first batch: node_round derives its candidate
   // cutoff from it, so every rank must use the same rule from round 0 (and the ingest thread must
   // never read a lane pointer the stats thread creates).  sx rows are decided on the stats thread.
-  {
-    const char* e = std::getenv("APM_ROLL_LANE");
-    roll_lane_mode_ = (!e || e[0] != '0') && !want(OUT_SX);
-    if (roll_lane_mode_) roll_lane_.reset(new TaskLane());
-  }
+  roll_lane_mode_ = !want(OUT_SX);
+  if (roll_lane_mode_) roll_lane_.reset(new TaskLane());
   stats_thread_ = std::thread([this, st_cpu]() {
     if (st_cpu >= 0) pin_current_thread(st_cpu);
     hipSetDevice(cfg_.device);
@@ -587,12 +565,6 @@ Engine::~Engine() {
   hipHostFree(h_n_alerts_); hipEventDestroy(ev_alerts_); hipEventDestroy(ev_release_); hipHostFree(h_tx_); hipHostFree(h_gid_);
   for (int k = 0; k < 2; ++k) {
     hipHostFree(h_release_gid_[k]);
-    {  // the sink's references to the staging buffers (its writers drain them; bounded wait)
-      FmtHolds& hs = *fmt_holds_;
-      std::unique_lock<std::mutex> lk(hs.mu);
-      if (!hs.cv.wait_for(lk, std::chrono::seconds(60), [&] { return hs.n[k] == 0; })) continue;
-    }
-    if (h_fmt_out_[k]) hipHostFree(h_fmt_out_[k]);
     if (h_fs_off_[k]) hipHostFree(h_fs_off_[k]);
     hipEventDestroy(ev_rel_[k]);
     hipEventDestroy(ev_fmt_[k]);
@@ -624,7 +596,6 @@ Engine::~Engine() {
   }
   hipStreamSynchronize(out_stream_);
   hipStreamDestroy(out_stream_);
-  if (out_stream2_) { hipStreamSynchronize(out_stream2_); hipStreamDestroy(out_stream2_); }
   if (rel_stream_) { hipStreamSynchronize(rel_stream_); hipStreamDestroy(rel_stream_); }
   hipHostFree(h_fmt_meta_);
   for (int k = 0; k < kStage; ++k) {
@@ -918,7 +889,7 @@ void Engine::launch_parse(ParseSlot& ps, const uint8_t* host_bytes, uint64_t n_b
   in_stage_src_ = nullptr;
   in_stage_n_ = 0;
   uint8_t* dbytes = dev() ? dj_->d_bytes(k) : d_bytes_;
-  Event* devents = dev() ? dj_->d_events(k) : (ps.d_events_host ? ps.d_events_host : d_events_);
+  Event* devents = dev() ? dj_->d_events(k) : d_events_;
   if (!staged) HIP_OK(hipMemcpyAsync(dbytes, ps.hb, off, hipMemcpyHostToDevice, parse_stream_));
   // (apm_parse_batch zeroes the 64 bytes after the batch inside its first kernel)
   h2d(d_chunk_begin_[k], ps.h_chunk_begin, (n_chunks + 1) * 4, parse_stream_);
@@ -939,7 +910,7 @@ void Engine::launch_parse(ParseSlot& ps, const uint8_t* host_bytes, uint64_t n_b
   // batch's host join instead of on the ingest thread's critical path (15 MB, ~0.3 ms), and
   // finish_parse copies only what the guess missed.
   ps.spec_copied = 0;
-  if (speculative && !dev() && !ps.d_events_host && spec_events_) {
+  if (speculative && !dev() && spec_events_) {
     ps.spec_copied = std::min<uint32_t>(spec_events_, cfg_.max_lines);
     HIP_OK(hipMemcpyAsync(ps.h_events, d_events_, (size_t)ps.spec_copied * sizeof(Event), hipMemcpyDeviceToHost,
                           parse_stream_));
@@ -976,7 +947,7 @@ void Engine::finish_parse(ParseSlot& ps) {
   metrics_.events += ps.n_events;
   if (dev()) {
     dj_->finish_select((int)(&ps - pslot_), parse_stream_);
-  } else if (ps.n_events > ps.spec_copied && !ps.d_events_host) {
+  } else if (ps.n_events > ps.spec_copied) {
     const uint32_t lo = ps.spec_copied;
     HIP_OK(hipMemcpyAsync(ps.h_events + lo, d_events_ + lo, (size_t)(ps.n_events - lo) * sizeof(Event),
                           hipMemcpyDeviceToHost, parse_stream_));
@@ -1209,11 +1180,10 @@ void Engine::process_batch_dev_tail(ParseSlot& ps, double t0, double now_overrid
       trace_event("next parse+prepass", ta, now_ms(), 3);
     });
   };
-  static const bool ahead_on = [] { const char* e = std::getenv("APM_PREPASS_AHEAD"); return !e || e[0] != '0'; }();
   // while this batch's join kernels run: the next batch's parse / pre-pass (ahead lane) and the
   // previous batches' fleet exchange (collective, enqueued on the coll stream in round order --
   // before this batch's lock-step all-reduce, as when it ran after the previous hand-off)
-  const bool do_ahead = prefetched_ && ahead_on;
+  const bool do_ahead = prefetched_;
   const std::function<void()> meanwhile = [this, &ahead, do_ahead]() {
     if (do_ahead) ahead();
     if (coll_ && fleet_due_ > fleet_rounds_) {
@@ -1620,7 +1590,6 @@ uint64_t Engine::post_out(std::function<void()> fn) {
 }
 
 uint64_t Engine::post_rel(std::function<void()> fn) {
-  if (!rel_lane_on_) return post_out(std::move(fn));
   if (!rel_lane_) {
     rel_lane_.reset(new TaskLane());
     HIP_OK(hipStreamCreateWithFlags(&rel_stream_, hipStreamNonBlocking));
@@ -1629,7 +1598,6 @@ uint64_t Engine::post_rel(std::function<void()> fn) {
 }
 
 void Engine::rel_wait(uint64_t task) {
-  if (!rel_lane_on_) { out_wait(task); return; }
   if (rel_lane_ && task) rel_lane_->wait(task);
 }
 
@@ -2167,37 +2135,10 @@ void Engine::h2d(void* d, const void* h, size_t n, hipStream_t s) {
 
 void Engine::lane_d2h(void* h, const void* d, size_t n, hipStream_t s) {
   if (!n) return;
-  if (s && s != out_stream_) {  // the release lane's stream: one blit copy
-    HIP_OK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s));
-    return;
-  }
-  if (d2h_split_ > 1 && n >= ((size_t)4 << 20)) {
-    // APM_D2H_SPLIT=N: N pieces over two streams, so two copies run at once on the host link
-    if (!out_stream2_) HIP_OK(hipStreamCreateWithFlags(&out_stream2_, hipStreamNonBlocking));
-    const size_t piece = ((n + d2h_split_ - 1) / d2h_split_ + 4095) & ~(size_t)4095;
-    int i = 0;
-    for (size_t off = 0; off < n; off += piece, ++i) {
-      const size_t m = std::min(piece, n - off);
-      HIP_OK(hipMemcpyAsync((char*)h + off, (const char*)d + off, m, hipMemcpyDeviceToHost,
-                            (i & 1) ? out_stream2_ : out_stream_));
-    }
-    return;
-  }
-  if (d2h_kernel_) {
-    void* hv = nullptr;
-    HIP_OK(hipHostGetDevicePointer(&hv, h, 0));
-    apm_copy_capped(hv, d, n, d2h_blocks_, out_stream_);
-  } else if (d2h_sdma_) {  // a copy engine instead of ROCclr's blit kernel (A/B)
-    HIP_OK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToDeviceNoCU, out_stream_));
-  } else {
-    HIP_OK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, out_stream_));
-  }
+  HIP_OK(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s ? s : out_stream_));
 }
 
-void Engine::lane_sync() {
-  HIP_OK(hipStreamSynchronize(out_stream_));
-  if (out_stream2_) HIP_OK(hipStreamSynchronize(out_stream2_));
-}
+void Engine::lane_sync() { HIP_OK(hipStreamSynchronize(out_stream_)); }
 
 void Engine::d2h(void* h, const void* d, size_t n, hipStream_t s) {
   if (n == 0) return;
@@ -2370,12 +2311,6 @@ void Engine::do_rollover(int64_t L, double batch_t0) {
     }
   }
   wa.tpm_div = (double)cfg_.window * cfg_.interval_len / 60.0;
-  {
-    // APM_K8_LDS=1: the LDS bitonic for every window; =2: only the two-series kernel's windows
-    // of 33-512 samples (A/B of its register network)
-    static const int lds = [] { const char* e = std::getenv("APM_K8_LDS"); return e && (e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0; }();
-    wa.lds_sort = lds;
-  }
   wa.out = d_win_;
   wa.big_list = d_big_list_;
   wa.big_n = d_big_n_;
@@ -2446,7 +2381,7 @@ void Engine::do_rollover(int64_t L, double batch_t0) {
   roll_round_ = stats_round_;
   roll_ring_base_ = cur_dj_ ? cur_dj_->ring_base : (dj_ ? dj_->ring_head() : 0);
   // The decision runs on the rollover lane as soon as the GPU chain is done, while this thread
-  // goes on (APM_ROLL_LANE=0: decide right here, the previous behaviour; sx rows always here).
+  // goes on (sx rows are decided right here).
   if (roll_lane_mode_) {
     roll_pending_ = false;
     roll_posted_ = true;
@@ -2592,13 +2527,8 @@ void Engine::release_device_finish() {
         HIP_OK(hipHostMalloc((void**)&h, h_rel_text_cap_[rk], hipHostMallocDefault));
       }
       const double tl0 = now_ms();
-      if (rel_lane_on_) {
-        lane_d2h(h, d_rel_text_[k], total, rel_stream_);
-        HIP_OK(hipStreamSynchronize(rel_stream_));
-      } else {
-        lane_d2h(h, d_rel_text_[k], total);
-        lane_sync();
-      }
+      lane_d2h(h, d_rel_text_[k], total, rel_stream_);
+      HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
         std::string enc[5];
@@ -3013,24 +2943,9 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   trace_event("fmt.wait_lane", tf1, now_ms(), 1);
   const size_t st_cap = fa.want_st ? (size_t)n * (176 + max_name_len_) : 0;
   const size_t fs_cap = fa.want_fs ? (size_t)n * cfg_.n_lags * (fs_copy_ ? 720 + 2 * max_name_len_ : 560 + max_name_len_) : 0;
-  if (fmt_host_) {
-    // the kernel writes into the pinned buffer itself: the sink must be done with its contents
-    const double th = now_ms();
-    wait_fmt_holds(k);
-    trace_event("fmt.wait_holds", th, now_ms(), 1);
-    if (st_cap + fs_cap + 64 > h_fmt_cap_[k]) {
-      if (h_fmt_out_[k]) HIP_OK(hipHostFree(h_fmt_out_[k]));
-      h_fmt_cap_[k] = (st_cap + fs_cap + 64) * 5 / 4;
-      HIP_OK(hipHostMalloc((void**)&h_fmt_out_[k], h_fmt_cap_[k], hipHostMallocDefault));
-      HIP_OK(hipHostGetDevicePointer((void**)&hd_fmt_out_[k], h_fmt_out_[k], 0));
-    }
-    fa.st_out = hd_fmt_out_[k];
-    fa.fs_out = hd_fmt_out_[k] + st_cap;
-  } else {
-    if (st_cap + fs_cap + 64 > fmt_out_cap_[k]) d_fmt_out_[k] = (char*)regrow(d_fmt_out_[k], fmt_out_cap_[k], st_cap + fs_cap + 64);
-    fa.st_out = d_fmt_out_[k];
-    fa.fs_out = d_fmt_out_[k] + st_cap;
-  }
+  if (st_cap + fs_cap + 64 > fmt_out_cap_[k]) d_fmt_out_[k] = (char*)regrow(d_fmt_out_[k], fmt_out_cap_[k], st_cap + fs_cap + 64);
+  fa.st_out = d_fmt_out_[k];
+  fa.fs_out = d_fmt_out_[k] + st_cap;
   const double tpl = now_ms();
   if (apm_format_plan(&fa, d_fmt_tmp_, fmt_tmp_bytes_, stream_) != 0) throw std::runtime_error("format scan failed");
   const double tpw = now_ms();
@@ -3060,24 +2975,6 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   trace_event("fmt.plan", tf0, now_ms(), 1);
   char* dst = d_fmt_out_[k];
   const size_t n_st = fa.want_st ? (size_t)n : 0, n_fs = fa.want_fs ? (size_t)n * cfg_.n_lags : 0;
-  if (fmt_host_) {
-    fmt_task_[k] = post_out([this, k, st_cap, n_st, n_fs]() {
-      const double tl0 = now_ms();
-      HIP_OK(hipEventSynchronize(ev_fmt_[k]));  // the text is in host memory once K12 completed
-      const size_t st_total = h_fmt_meta_[4 * k], fs_total = h_fmt_meta_[4 * k + 1];
-      note_fmt_block(st_total, n_st, fs_total, n_fs);
-      {
-        std::lock_guard<std::mutex> g(out_mu_);
-        formatted_bytes_lane_ += st_total + fs_total;
-      }
-      const double tl1 = now_ms();
-      emit_bytes(OUT_ST, h_fmt_out_[k], st_total);
-      emit_bytes_held(OUT_FS, h_fmt_out_[k] + st_cap, fs_total, k, fs_rows_[k] ? h_fs_off_[k] : nullptr, fs_rows_[k]);
-      trace_event("lane st/fs wait (direct)", tl0, tl1, 4);
-      trace_event("lane st/fs emit", tl1, now_ms(), 4);
-    });
-    return;
-  }
   const int hk = fmt_ring_k_;
   fmt_ring_k_ = (fmt_ring_k_ + 1) % FMT_RING;
   fmt_task_[k] = post_out([this, k, hk, dst, st_cap, n_st, n_fs]() {
@@ -3529,8 +3426,6 @@ void Engine::fleet_setup(int32_t cap, bool lockstep) {
   HIP_OK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
   const char* pe = std::getenv("APM_COLL_PRIO");  // diagnostic: 0 = default-priority collective stream
   HIP_OK(hipStreamCreateWithPriority(&coll_stream_, hipStreamNonBlocking, pe && pe[0] == '0' ? prio_lo : prio_hi));
-  const char* se = std::getenv("APM_FLEET_SKIP_SOLO");  // diagnostic: skip the one-rank (identity) all-reduce
-  fleet_skip_solo_ = nranks == 1 && se && se[0] == '1';
   fleet_nranks_ = nranks;
   lockstep_ = lockstep;
   if (lockstep_) {
@@ -3698,11 +3593,9 @@ void Engine::fleet_pack_locked() {
   pack_edge_[slot] = metrics_.rollovers != last_edge_seen_ ? last_edge_ts_ : 0;
   last_edge_seen_ = metrics_.rollovers;
   const double t0 = now_ms();
-  // APM_FLEET_ATOMIC=1: the per-series fp64 atomic scatter instead of the MFMA Gram pack (A/B)
-  static const bool atomic_pack = [] { const char* x = std::getenv("APM_FLEET_ATOMIC"); return x && x[0] == '1'; }();
   pack_nlags_[slot] = cfg_.n_lags;
   for (int l = 0; l < MAX_LAGS; ++l) pack_lags_[slot][l] = cfg_.lags[l];
-  pack_moments_locked(fleet_buf_[slot], fleet_cap_, stream_, atomic_pack);
+  pack_moments_locked(fleet_buf_[slot], fleet_cap_, stream_);
   trace_event("fleet.pack", t0, now_ms(), 1);
   HIP_OK(hipEventRecord(pack_ev_[slot], stream_));
   ++fleet_packed_;
@@ -3720,7 +3613,7 @@ void Engine::fleet_exchange_upto(uint64_t rounds) {
     const size_t per_svc = (size_t)pack_nlags_[slot] * NSTAT * 3;
     const size_t n_red = lockstep_ ? std::min<size_t>(reg_names_.size(), (size_t)fleet_cap_) * per_svc
                                    : (size_t)fleet_cap_ * per_svc;
-    if (!fleet_skip_solo_ && n_red) coll_->all_reduce_f64(fleet_buf_[slot], n_red, /*max=*/false, coll_stream_);
+    if (n_red) coll_->all_reduce_f64(fleet_buf_[slot], n_red, /*max=*/false, coll_stream_);
     // fb rows: every rank its slice, on the fb stream behind this all-reduce -- the next batch's
     // clock all-reduce on this in-order stream never waits for formatting
     bool fb_queued = false;

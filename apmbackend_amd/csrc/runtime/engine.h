@@ -499,7 +499,7 @@ class Engine {
   // with the next batch instead of waiting for its GPU chain.  The next rollover (or flush) waits
   // for it first; series_mu_ guards series_ growth against the lane's reads.
   std::unique_ptr<TaskLane> roll_lane_;
-  bool roll_lane_mode_ = false;  // fixed at construction (APM_ROLL_LANE, outputs): same on every rank
+  bool roll_lane_mode_ = false;  // fixed at construction (off with sx output): same on every rank
   uint64_t roll_task_ = 0;
   bool roll_posted_ = false;
   std::mutex series_mu_;
@@ -524,7 +524,7 @@ class Engine {
   struct FmtHolds {  // shared with the holds: a release after the engine is gone stays safe
     std::mutex mu;
     std::condition_variable cv;
-    // st/fs device-written staging 0, 1 (APM_FMT_HOST); fb staging 2, 3; released db text 4, 5;
+    // 0, 1 unused; fb staging 2, 3; released db text 4, 5;
     // st/fs host ring 6 .. 6 + FMT_RING; released db text ring after it
     int n[6 + FMT_RING + REL_RING] = {};
   };
@@ -584,7 +584,6 @@ class Engine {
   hipEvent_t fleet_ev_[2] = {nullptr, nullptr};    // all-reduce of the slot done (coll stream)
   hipEvent_t pack_ev_[2] = {nullptr, nullptr};     // pack of the slot done (comm stream)
   int fleet_nranks_ = 0;
-  bool fleet_skip_solo_ = false;
   std::vector<int64_t> shard_maxb_;  // per-shard newest bucket (one cache line each), lock-step clock
   uint64_t fleet_rounds_ = 0;  // exchanges issued (ingest thread)
   uint64_t fleet_posted_ = 0;  // batches posted since fleet_init (ingest thread)
@@ -836,7 +835,6 @@ class Engine {
     uint8_t* h_chunk_kind = nullptr;
     uint32_t* h_chunk_file = nullptr;
     Event* h_events = nullptr;
-    Event* d_events_host = nullptr;             // device alias of h_events (zero-copy compaction)
     uint32_t* h_counts = nullptr;               // [0]=n_events [1]=n_lines
     unsigned long long* h_watermark = nullptr;
     const uint8_t* hb = nullptr;                // bytes the join reads (caller's or staging)
@@ -1128,12 +1126,11 @@ class Engine {
   int64_t* h_release_gid_[2] = {nullptr, nullptr};  // ping-pong D2H targets of released ids
   hipEvent_t ev_rel_[2] = {nullptr, nullptr};
   uint64_t rel_task_[2] = {0, 0};                    // output-lane task that reads each buffer
-  // Released db lines get a lane (thread) and a stream of their own (APM_REL_LANE=0: the st / fs
-  // output lane, as before): their D2H + emission overlap the st / fs D2H instead of queueing
-  // behind it in one FIFO -- the production path is output-lane bound (profiles/r5_e).
+  // Released db lines get a lane (thread) and a stream of their own: their D2H + emission overlap
+  // the st / fs D2H instead of queueing behind it in one FIFO -- the production path is
+  // output-lane bound (profiles/r5_e).
   std::unique_ptr<TaskLane> rel_lane_;
   hipStream_t rel_stream_ = nullptr;
-  bool rel_lane_on_ = true;
   uint64_t post_rel(std::function<void()> fn);
   void rel_wait(uint64_t task);
   int rel_k_ = 0;
@@ -1175,12 +1172,6 @@ class Engine {
   size_t fmt_tmp_bytes_ = 0;
   char* d_fmt_out_[2] = {nullptr, nullptr};
   size_t fmt_out_cap_[2] = {0, 0};
-  char* h_fmt_out_[2] = {nullptr, nullptr};      // pinned ping-pong staging for the D2H of formatted text
-  size_t h_fmt_cap_[2] = {0, 0};
-  // APM_FMT_HOST=1: K12 writes the st/fs text straight into h_fmt_out_ (device alias hd_fmt_out_)
-  // over the host link -- no HBM round trip, no D2H copy on the output lane
-  bool fmt_host_ = false;
-  char* hd_fmt_out_[2] = {nullptr, nullptr};
   hipEvent_t ev_fmt_[2] = {nullptr, nullptr};
   uint64_t fmt_task_[2] = {0, 0};
   // Pinned st/fs staging the output lane copies into, a ring deeper than the device double
@@ -1213,19 +1204,7 @@ class Engine {
   bool db_copy_ = false;
   bool rel_copy_ = false;         // the pending release was planned as COPY rows
   bool txcopy_force_fb_ = false;
-  // APM_D2H_KERNEL=1: the output lane's D2H of st / fs / db text by the engine's copy kernel
-  // (16-byte lanes, at most APM_D2H_BLOCKS workgroups -- default 32 -- into the mapped pinned
-  // buffer) instead of hipMemcpyAsync (ROCclr's blit: one 512-lane workgroup on every CU)
-  bool d2h_kernel_ = false;
-  uint32_t d2h_blocks_ = 32;
-  // APM_D2H_SDMA=1: the same copies as hipMemcpyDeviceToDeviceNoCU into the pinned buffer (a DMA
-  // engine, no compute units)
-  bool d2h_sdma_ = false;
-  // APM_D2H_SPLIT=N: lane copies of >= 4 MB in N pieces alternating over out_stream_ and a second
-  // output stream (two copies in flight on the host link)
-  int d2h_split_ = 1;
-  hipStream_t out_stream2_ = nullptr;
-  void lane_sync();  // both output streams
+  void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
   uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0};

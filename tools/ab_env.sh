@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of one build under two environments on one GPU box (box noise cancels by alternation):
-#   A_ENV="APM_EVENTS_D2H=0" B_ENV="APM_EVENTS_D2H=1" ROUNDS=3 bash tools/ab_env.sh
+#   A_ENV="APM_STATS_PRIO=0" B_ENV="APM_STATS_PRIO=1" ROUNDS=3 bash tools/ab_env.sh
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
