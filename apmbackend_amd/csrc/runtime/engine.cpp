@@ -563,6 +563,7 @@ Engine::~Engine() {
   hipHostFree(h_alert_z_);
   if (h_series_service_) hipHostFree(h_series_service_);
   hipHostFree(h_n_alerts_); hipEventDestroy(ev_alerts_); hipEventDestroy(ev_release_); hipHostFree(h_tx_); hipHostFree(h_gid_);
+  if (ev_tx_staged_) hipEventDestroy(ev_tx_staged_);
   for (int k = 0; k < 2; ++k) {
     hipHostFree(h_release_gid_[k]);
     if (h_fs_off_[k]) hipHostFree(h_fs_off_[k]);
@@ -1929,6 +1930,10 @@ void Engine::stats_for_batch(std::vector<TxOut>& txs, double batch_t0) {
   const int64_t latest_at_start = latest_;
   const bool w_tx = want(OUT_TRANSACTIONS), w_audit = want(OUT_AUDIT_DB), w_db = want(OUT_DB);
   std::vector<std::string>& text = *cur_text_;
+  // h_tx_ / h_gid_ are rewritten below: the previous batch's asynchronous copy out of them must
+  // have run (small batches posted back to back put the host a batch ahead of the stream, and
+  // that batch's tx then carried this batch's records)
+  if (ev_tx_staged_) HIP_OK(hipEventSynchronize(ev_tx_staged_));
   // Each shard's text arena of this batch becomes a release block (zero copy): the pool payload
   // of a pending tx addresses its line inside the arena, gid = block << 44 | offset << 12 | len.
   const size_t n_arena = text.size();
@@ -2007,6 +2012,8 @@ void Engine::stats_for_batch(std::vector<TxOut>& txs, double batch_t0) {
   if (n == 0) return;
   HIP_OK(hipMemcpyAsync(d_tx_, h_tx_, (size_t)n * sizeof(TxRec), hipMemcpyHostToDevice, stream_));
   HIP_OK(hipMemcpyAsync(d_gid_, h_gid_, (size_t)n * 8, hipMemcpyHostToDevice, stream_));
+  if (!ev_tx_staged_) HIP_OK(hipEventCreateWithFlags(&ev_tx_staged_, hipEventDisableTiming));
+  HIP_OK(hipEventRecord(ev_tx_staged_, stream_));
   {
     StatsState st = stats_state();
     apm_nan_mark(d_tx_, n, &st, stream_);

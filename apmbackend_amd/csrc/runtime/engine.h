@@ -1115,6 +1115,7 @@ class Engine {
   TxRec* h_tx_ = nullptr;
   int64_t* d_gid_ = nullptr;
   int64_t* h_gid_ = nullptr;
+  hipEvent_t ev_tx_staged_ = nullptr;  // the last H2D out of h_tx_ / h_gid_ (host join): waited on before they are rewritten
   int64_t *d_tail_end_ = nullptr, *d_tail_gid_ = nullptr, *d_sort_end_ = nullptr, *d_sort_gid_ = nullptr;
   int64_t *d_pool_end_[2] = {nullptr, nullptr}, *d_pool_gid_[2] = {nullptr, nullptr};
   int pool_cur_ = 0;

@@ -102,3 +102,19 @@ def test_import_then_continue_produces_stats_rows():
     first_round = [l.split("|")[2:4] for l in st if l.split("|")[1] == first_ts]
     want = [list(k) for k in eng.eng.export_series()]
     assert first_round[:len(want)] == want[:len(first_round)]
+    # ... with the values a StatsOracle seeded from the same exported documents computes from the
+    # tx the resumed engine saw (exact: every st row of the first rollover after the import)
+    from apmbackend_amd.models.oracle import StatsOracle
+    sc = C["streamCalcStats"]
+    oracle_st = []
+    so = StatsOracle(oracle_st.append, lambda _l: None, int(sc["intervalLengthInSeconds"]),
+                     int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]))
+    so.latest = int(stats["latestBucket"])
+    for srv, doc in stats["servers"].items():
+        node = so.servers.setdefault(srv, collections.OrderedDict())
+        for svc, sv in doc["services"].items():
+            node[svc] = {int(b): [int(v) for v in vals] for b, vals in sv["buckets"].items()}
+    for line in eng2.take("transactions"):
+        so.consume(line)
+    assert [l for l in oracle_st if l.split("|")[1] == first_ts] == [l for l in st if l.split("|")[1] == first_ts]
+    assert len(first_round) >= len(want)
