@@ -571,15 +571,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[5];
-    int64_t counts[5] = {0, 0, 0, 0, 0};
+    std::string out[6];
+    int64_t counts[6] = {0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[5] = {"tx", "fs", "al", "jx", "fb"};
-    for (int k = 0; k < 5; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[6] = {"tx", "fs", "al", "jx", "fb", "lh"};
+    for (int k = 0; k < 6; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -692,6 +692,11 @@ PYBIND11_MODULE(_apm_native, m) {
     return py::object(py::float_(v));
   });
   m.def("js_round_fixed", [](double x, int f) { return js_round_fixed(x, f); });
+  // lh histogram (hist.hip): the device bin rule as the host compiles it, and the sample count
+  // up to which the count pass keeps a series in its 32-lane group (tests bracket it)
+  m.def("hist_bin", [](int32_t v) { return hist_bin(v); });
+  m.def("hist_lower", [](int b) { return hist_lower(b); });
+  m.def("hist_group_max", []() { return apm_hist_group_max(); });
 
   register_tailer(m);
   register_synth(m);

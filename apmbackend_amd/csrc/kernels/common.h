@@ -85,6 +85,20 @@ __host__ __device__ inline double js_round_fixed(double x, int f) {
   return neg ? -r : r;
 }
 
+// lh latency histogram bins (docs/HISTOGRAM.md; utils/records.py hist_bin / hist_lower hold the
+// same rule): integers only, four sub-bins per power of two, 120 bins over the int32 range.
+// v <= 0 -> 0; 1..3 -> v; else e = floor(log2 v), sub = the two bits below the leading one,
+// bin = 4 * (e - 1) + sub (continuous at 4; INT32_MAX -> 119).  Relative bin width <= 25 %.
+constexpr int HIST_BINS = 120;
+__host__ __device__ inline int hist_bin(int32_t v) {
+  if (v < 4) return v <= 0 ? 0 : v;
+  const int e = 31 - __builtin_clz((uint32_t)v);
+  return 4 * (e - 1) + (int)(((uint32_t)v >> (e - 2)) & 3u);
+}
+__host__ __device__ inline uint32_t hist_lower(int b) {
+  return b < 4 ? (uint32_t)b : (uint32_t)(4 + (b & 3)) << (b / 4 - 1);
+}
+
 // Join-key hash, shared by the parse kernel (which hashes logIds and service names into the
 // Event) and the host join / checkpoints: word-at-a-time, one 64x64->128 multiply folded per
 // 8 bytes (wyhash-style).  FNV-1a's byte-serial multiply chain cost ~4 cycles per byte.

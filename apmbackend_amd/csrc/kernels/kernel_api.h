@@ -168,6 +168,23 @@ struct FleetFormatArgs {
   char* out;
   int32_t* fallback;
 };
+// K15 lh rows: one bucket's samples per series as a sparse histogram (hist.hip).  One row per
+// emission position whose series holds a sample in ring slot `slot`:
+//   lh|<bucket start ms>|server|service|<count>|<nan>|<lo>:<c>,<lo>:<c>,...
+struct HistArgs {
+  StatsState st;                // spill lists sorted (apm_spill_sort) before the call
+  const int32_t* perm;          // [n] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;
+  int32_t slot;                 // ring slot of the reported bucket
+  int32_t ts_len;
+  char ts[24];                  // "<bucket * 10000>|"
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  int32_t* big_list;            // [n] emission positions deferred to the block pass
+  int32_t* big_n;
+  char* out;                    // at least apm_hist_row_bound(max name bytes) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -263,6 +280,16 @@ void apm_fleet_format(apm::FleetFormatArgs* a, hipStream_t stream);
 void apm_alert_gather(const apm::AlertRec* alerts, const int32_t* n_dev, int32_t max_n, const apm::WinStat* win,
                       const apm::ZOut* const* z_by_lag, int32_t n_lags, int32_t rows, apm::AlertRec* alerts_out,
                       apm::WinStat* win_out, apm::ZOut* z_out, int32_t* n_out, hipStream_t stream);
+// hist.hip
+// sample counts of the count pass' two paths (tests bracket them): a series with more samples in
+// the bucket than apm_hist_group_max() is counted by a whole block instead of 32 lanes
+int32_t apm_hist_group_max();
+size_t apm_hist_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes
+size_t apm_hist_row_bound(size_t name_bytes);
+// count pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_hist_plan(apm::HistArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_hist_write(apm::HistArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

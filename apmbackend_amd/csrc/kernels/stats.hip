@@ -20,6 +20,7 @@
 #include "kernel_api.h"
 
 #include "prim.h"
+#include "spill.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -221,21 +222,7 @@ __global__ void k_clear_slot(StatsState st, int slot) {
 }
 
 // --------------------------------------------------------------------------------- K8
-// first position of series s in a slot's sorted spill list [0, n)
-__device__ __forceinline__ int spill_lower(const int32_t* keys, int n, int32_t s) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (keys[mid] < s) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-// the run of series s's spilled samples in slot sl: [*first, *first + cnt - cap)
-__device__ __forceinline__ const int32_t* spill_run(const StatsState& st, int sl, int s) {
-  const size_t base = (size_t)sl * st.spill_cap;
-  const int ns = min(st.spill_n[sl], st.spill_cap);
-  return st.spill_val + base + spill_lower(st.spill_series + base, ns, s);
-}
+// (spill_lower / spill_run: spill.h)
 
 __device__ __forceinline__ void percentile_ranks(int n, int pct, int& lo, int& hi) {
   // calcPercentile: idx = p/100*n - 1; integral -> a[idx]; else ceil, last -> a[last],

@@ -663,7 +663,7 @@ void Engine::write_small_sections(BinWriter& w) {
   w.end();
 
   w.begin(SEC_OUTPUTS);
-  for (int k = 0; k < N_OUT; ++k) w.str(blob_[k]);
+  for (int k = 0; k < N_OUT_CKPT; ++k) w.str(blob_[k]);
   w.end();
 
   w.begin(SEC_METRICS);
@@ -1003,7 +1003,7 @@ std::string Engine::load_small_state(const std::string& path) {
   rebuild_cool();
 
   rd.begin(SEC_OUTPUTS);
-  for (int k = 0; k < N_OUT; ++k) blob_[k] = rd.str();
+  for (int k = 0; k < N_OUT_CKPT; ++k) blob_[k] = rd.str();
 
   rd.begin(SEC_METRICS);
   {

@@ -198,8 +198,8 @@ void fs_row_json(std::string& out, const Fields& a) {
 
 }  // namespace
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[5]*/) {
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[6]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -266,6 +266,34 @@ int encode_line(std::string_view line, std::string* out /*[5]*/) {
     copy_escape(o, js);
     o += '\n';
     return 4;
+  }
+  if (t == "lh") {  // latency histogram: timestamp, server, service, count, nan, bins json
+    std::string& o = out[5];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    c_num(o, a.has(4) ? js::parse_int(a.f[4]) : js::nan()); o += '\t';
+    c_num(o, a.has(5) ? js::parse_int(a.f[5]) : js::nan()); o += '\t';
+    std::string js = "{";
+    std::string_view rest = a.has(6) ? a.f[6] : std::string_view();
+    while (!rest.empty()) {
+      const size_t e = rest.find(',');
+      const std::string_view pr = rest.substr(0, e);
+      rest = e == std::string_view::npos ? std::string_view() : rest.substr(e + 1);
+      const size_t c = pr.find(':');
+      const double lo = js::parse_int(pr.substr(0, c));
+      const double n = c == std::string_view::npos ? js::nan() : js::parse_int(pr.substr(c + 1));
+      if (lo != lo || n != n) continue;  // (a malformed pair is dropped)
+      if (js.size() > 1) js += ',';
+      js += '"';
+      js::append_num(js, lo);
+      js += "\":";
+      js::append_num(js, n);
+    }
+    js += '}';
+    copy_escape(o, js);
+    o += '\n';
+    return 5;
   }
   if (t == "jx") {
     std::string& o = out[3];

@@ -423,6 +423,16 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   d_fmt_tmp_ = dmalloc(fmt_tmp_bytes_);
   HIP_OK(hipHostMalloc((void**)&h_fmt_meta_, 64, hipHostMallocDefault));
   HIP_OK(hipHostGetDevicePointer((void**)&hd_fmt_meta_, h_fmt_meta_, 0));
+  if (want(OUT_LH)) {  // K15
+    d_hist_len_ = (uint32_t*)dmalloc((size_t)(S + 1) * 4);
+    d_hist_off_ = (uint32_t*)dmalloc((size_t)(S + 1) * 4);
+    d_hist_big_ = (int32_t*)dmalloc((size_t)(S + 1) * 4);
+    hist_tmp_bytes_ = apm_hist_tmp_bytes(S);
+    d_hist_tmp_ = dmalloc(hist_tmp_bytes_);
+    HIP_OK(hipHostMalloc((void**)&h_hist_total_, 64, hipHostMallocDefault));
+    HIP_OK(hipHostGetDevicePointer((void**)&hd_hist_total_, h_hist_total_, 0));
+    for (int k = 0; k < 2; ++k) HIP_OK(hipEventCreateWithFlags(&ev_hist_[k], hipEventDisableTiming));
+  }
   {
     const char* f = std::getenv("APM_TXCOPY_FORCE_FALLBACK");
     txcopy_force_fb_ = f && f[0] == '1';
@@ -577,6 +587,11 @@ Engine::~Engine() {
     if (h_fmt_ring_[r]) hipHostFree(h_fmt_ring_[r]);
   }
   if (h_roll_out_) hipHostFree(h_roll_out_);
+  if (h_hist_total_) hipHostFree(h_hist_total_);
+  for (int k = 0; k < 2; ++k) {
+    if (h_hist_text_[k]) hipHostFree(h_hist_text_[k]);
+    if (ev_hist_[k]) hipEventDestroy(ev_hist_[k]);
+  }
   if (cool_ev_) { hipEventSynchronize(cool_ev_); hipEventDestroy(cool_ev_); }
   if (h_cool_idx_) { hipHostFree(h_cool_idx_); hipHostFree(h_cool_val_); }
   if (dj_) {
@@ -2047,7 +2062,7 @@ void Engine::stats_for_batch(std::vector<TxOut>& txs, double batch_t0) {
   int64_t cur_latest = latest_at_start;
   for (auto& tr : triggers) {
     append(seg_lo, tr.first, cur_latest);
-    do_rollover(tr.second, batch_t0);
+    do_rollover(tr.second, batch_t0, cur_latest);
     cur_latest = tr.second;
     seg_lo = tr.first;
   }
@@ -2118,7 +2133,7 @@ void Engine::stats_for_batch_dev(DevJoinBatch& b, double batch_t0) {
   int64_t cur_latest = latest_at_start;
   for (auto& tr : triggers) {
     append(seg_lo, tr.first, cur_latest);
-    do_rollover(tr.second, batch_t0);
+    do_rollover(tr.second, batch_t0, cur_latest);
     cur_latest = tr.second;
     seg_lo = tr.first;
   }
@@ -2200,7 +2215,7 @@ void Engine::refresh_unseen_active() {
     if (h_unseen_flag_[i]) h_active_[unseen_[i]] = 1;
 }
 
-void Engine::do_rollover(int64_t L, double batch_t0) {
+void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   finish_rollover();  // a previous rollover of this job still owns the candidate buffers
   const int64_t keep_iv = cfg_.window + cfg_.buffer;
   // the decision's clock, fixed before K11 so its cooldown pre-filter and the host decide alike
@@ -2328,6 +2343,7 @@ void Engine::do_rollover(int64_t L, double batch_t0) {
   wa.n_series = n_series_;
   HIP_OK(hipMemsetAsync(d_big_n_, 0, 12, stream_));  // big / nan windows, alert candidates
   apm_window_stats(&wa, stream_);
+  if (want(OUT_LH)) hist_rollover(L, prev);  // K15: the buckets that entered the window (sorted spill lists)
   // ---- K10 z-score per LAG, K11 alert eval (a streamed checkpoint's rows first: copy-before-overwrite)
   ck_guard_rollover(rollover_idx_);
   for (int l = 0; l < cfg_.n_lags; ++l) {
@@ -2538,8 +2554,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[5];
-        int64_t counts[5] = {0, 0, 0, 0, 0};
+        std::string enc[6];
+        int64_t counts[6] = {0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3015,6 +3031,65 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   });
 }
 
+// ---- K15: lh rows.  A rollover from `prev` to L reports every bucket that K8 reads now and did
+// not read at the previous rollover: max(prev - buffer, L - keep - 1) < b <= L - buffer, ascending
+// (one bucket unless `latest` jumped).  A bucket without a ring slot holds no sample: no launch.
+void Engine::hist_rollover(int64_t L, int64_t prev) {
+  const int64_t keep_iv = cfg_.window + cfg_.buffer;
+  const int64_t lo = std::max(prev - cfg_.buffer, L - keep_iv - 1);
+  for (int64_t b = lo + 1; b <= L - cfg_.buffer; ++b) {
+    const int slot = (int)(((b % nslot_) + nslot_) % nslot_);
+    if (slot_bucket_[slot] == b) hist_bucket(b, slot);
+  }
+}
+
+void Engine::hist_bucket(int64_t b, int slot) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();
+  HistArgs ha{};
+  ha.st = stats_state();
+  ha.perm = d_perm_;
+  ha.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ha.names = d_names_;
+  ha.n = n;
+  ha.slot = slot;
+  ha.ts_len = std::snprintf(ha.ts, sizeof ha.ts, "%lld|", (long long)(b * 10000));
+  ha.len = d_hist_len_;
+  ha.off = d_hist_off_;
+  ha.big_list = d_hist_big_;
+  ha.big_n = d_hist_big_ + cfg_.max_series;
+  const int k = hist_k_;
+  hist_k_ ^= 1;
+  out_wait(hist_task_[k]);  // slot k's previous D2H + emission is done
+  // the output bound needs no length pass: every row is at most apm_hist_row_bound bytes
+  const size_t cap = (size_t)n * apm_hist_row_bound(max_name_len_) + 64;
+  if (cap > hist_out_cap_[k]) d_hist_out_[k] = (char*)regrow(d_hist_out_[k], hist_out_cap_[k], cap);
+  ha.out = d_hist_out_[k];
+  if (apm_hist_plan(&ha, d_hist_tmp_, hist_tmp_bytes_, stream_) != 0) throw std::runtime_error("histogram scan failed");
+  apm_hist_write(&ha, stream_);
+  {
+    ExportArgs ex{};
+    ex.add(ha.off + n, hd_hist_total_ + k, 4);
+    apm_export(&ex, stream_);
+  }
+  HIP_OK(hipEventRecord(ev_hist_[k], stream_));
+  const char* dst = d_hist_out_[k];
+  hist_task_[k] = post_out([this, k, dst]() {
+    HIP_OK(hipEventSynchronize(ev_hist_[k]));
+    const size_t total = h_hist_total_[k];
+    if (!total) return;
+    if (total > h_hist_text_cap_[k]) {
+      if (h_hist_text_[k]) HIP_OK(hipHostFree(h_hist_text_[k]));
+      h_hist_text_cap_[k] = total * 2 + (1 << 20);
+      HIP_OK(hipHostMalloc((void**)&h_hist_text_[k], h_hist_text_cap_[k], hipHostMallocDefault));
+    }
+    lane_d2h(h_hist_text_[k], dst, total);
+    lane_sync();
+    emit_bytes(OUT_LH, h_hist_text_[k], total);
+  });
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3155,7 +3230,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh"};
   return n[k];
 }
 
@@ -3582,9 +3657,10 @@ int64_t Engine::lockstep_latest(int slot) {
 // reference stats process rolls over on the first tx of a new bucket from any JVM.
 void Engine::apply_latest_locked(int64_t g, double batch_t0) {
   if (g == INT64_MIN || g <= latest_) return;
+  const int64_t prev = latest_;
   latest_ = g;
   ++metrics_.lockstep_rollovers;
-  do_rollover(g, batch_t0);
+  do_rollover(g, batch_t0, prev);
 }
 
 // Stats thread: pack this batch's moments into its slot (after the slot's previous all-reduce).

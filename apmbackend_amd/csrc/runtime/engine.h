@@ -138,9 +138,12 @@ struct EngineConfig {
 //   FS            z -> alerts/db  fs lines (one per series per LAG)
 //   AL            alerts -> db    al lines
 //   SX            new: per-JVM rollup fused with JMX / VM gauges (K14), one line per server
-enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, N_OUT };
-// streams written by the engine's output lane (released tx, st, fs); the stats thread owns the rest
-constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS);
+enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, N_OUT };
+// Streams whose pending text a checkpoint stores (checkpoint.cpp).  The version-9 layout holds
+// exactly these; lh rows are taken by their consumer before a checkpoint and are not persisted.
+constexpr int N_OUT_CKPT = OUT_FB + 1;
+// streams written by the engine's output lane (released tx, st, fs, lh); the stats thread owns the rest
+constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH);
 const char* out_kind_name(int k);
 int out_kind_of(const std::string& name);
 
@@ -486,7 +489,7 @@ class Engine {
   void refresh_unseen_active();
   std::string ring_text(const int64_t* d_gid, int64_t n);  // pending lines out of the HBM ring
   void ensure_bucket_slot(int64_t b);
-  void do_rollover(int64_t L, double batch_t0);
+  void do_rollover(int64_t L, double batch_t0, int64_t prev);  // prev: `latest` before this rollover
   void flush_alerts(int64_t edge_ts);
   void finish_rollover();
   bool roll_pending_ = false;  // do_rollover queued; its decision is made by finish_rollover
@@ -710,7 +713,7 @@ class Engine {
   std::mutex out_pool_mu_;
   bool st_has_job_ = false, st_busy_ = false, st_stop_ = false;
   std::string st_error_;
-  // output lane: FIFO of emit tasks; it owns the db / st / fs streams (kLaneKinds)
+  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh streams (kLaneKinds)
   std::thread out_thread_;
   std::mutex out_mu_;
   std::condition_variable out_cv_;
@@ -1197,9 +1200,26 @@ class Engine {
   size_t fs_rows_[2] = {0, 0};
   uint32_t* hd_fmt_meta_ = nullptr;
 
+  // K15 lh rows (hist.hip), allocated when the stream is on: every bucket is reported once, at the
+  // rollover that first has it in the K8 window.  Two device / pinned slots, as for st / fs.
+  uint32_t *d_hist_len_ = nullptr, *d_hist_off_ = nullptr;  // [S + 1]
+  int32_t* d_hist_big_ = nullptr;                            // [S] block-pass list, [S] its length
+  void* d_hist_tmp_ = nullptr;
+  size_t hist_tmp_bytes_ = 0;
+  char* d_hist_out_[2] = {nullptr, nullptr};
+  size_t hist_out_cap_[2] = {0, 0};
+  char* h_hist_text_[2] = {nullptr, nullptr};  // pinned (output lane)
+  size_t h_hist_text_cap_[2] = {0, 0};
+  uint32_t *h_hist_total_ = nullptr, *hd_hist_total_ = nullptr;  // pinned [2]: bytes of slot k's rows
+  hipEvent_t ev_hist_[2] = {nullptr, nullptr};
+  uint64_t hist_task_[2] = {0, 0};
+  int hist_k_ = 0;
+  void hist_rollover(int64_t L, int64_t prev);
+  void hist_bucket(int64_t b, int slot);
+
   // text outputs
   std::string blob_[N_OUT];
-  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
   std::shared_ptr<ByteSink> byte_sink_[N_OUT];
   bool fs_copy_ = false;
   bool db_copy_ = false;
@@ -1208,7 +1228,7 @@ class Engine {
   void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
-  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   // K14 server rollup + exogenous context
   std::vector<double> h_ctx_;                    // [servers][CTX_FIELDS] (stats thread)
   bool ctx_dirty_ = false;

@@ -132,7 +132,7 @@ struct Input {
   std::string pend_text;
   // alerts / outputs / metrics
   std::vector<std::pair<std::string, double>> cool;
-  std::string blob[N_OUT];
+  std::string blob[N_OUT_CKPT];
   uint64_t metrics[11] = {};
   std::string extra;
   int64_t n() const { return (int64_t)sr.size(); }
@@ -825,7 +825,7 @@ MergeResult merge_checkpoints(const std::vector<std::string>& inputs, const std:
   // undelivered output: the lines of the kept servers (the server field of each record type);
   // fb rows (node-wide, no server) from the inputs whose first server this rank keeps
   w.begin(SEC_OUTPUTS);
-  for (int k = 0; k < N_OUT; ++k) {
+  for (int k = 0; k < N_OUT_CKPT; ++k) {
     const int field = (k == OUT_TRANSACTIONS || k == OUT_AUDIT_DB || k == OUT_DB) ? 1
                     : (k == OUT_ST || k == OUT_FS || k == OUT_SX) ? 2 : (k == OUT_AL ? 3 : -1);
     std::string b;

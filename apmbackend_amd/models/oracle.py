@@ -26,8 +26,9 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import zscore_lag_settings
-from ..utils.records import AlertEntry, FullStatEntry, StatEntry, TxEntry, entry_from_csv
+from ..utils.config import as_bool, gpu_opt, zscore_lag_settings
+from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, StatEntry, TxEntry, entry_from_csv, hist_bin,
+                             hist_lower)
 from ..utils.timeparse import TzOffset, convert_string_date_to_ms, default_tz
 
 NAN = float("nan")
@@ -666,7 +667,8 @@ class StatsOracle:
     """``StatParser`` + ``consumeMsg`` of stream_calc_stats.js."""
 
     def __init__(self, emit_stat: Callable[[str], None], emit_db: Callable[[str], None],
-                 interval_len=10, window=30, buffer=6):
+                 interval_len=10, window=30, buffer=6, emit_hist: Optional[Callable[[str], None]] = None):
+        self.emit_hist = emit_hist  # lh rows (docs/HISTOGRAM.md); None = stream off
         self.emit_stat = emit_stat
         self.emit_db = emit_db
         self.interval_len = interval_len
@@ -696,8 +698,8 @@ class StatsOracle:
         if lab is None:
             return  # NaN/short endTs: the reference would wedge its heap (fix)
         if lab > self.latest:
-            self.latest = lab
-            self.rollover()
+            prev, self.latest = self.latest, lab
+            self.rollover(prev)
         srv = self.servers.setdefault(tx.server, OrderedDict())
         svc = srv.setdefault(tx.service, {})
         svc.setdefault(lab, []).append(jsfmt.parse_int(tx.elapsed))
@@ -707,10 +709,35 @@ class StatsOracle:
         """Multi-rank lock-step (parallel/dist): another rank saw bucket ``latest`` -- roll
         over as the single reference stats process would have at that tx."""
         if latest > self.latest:
-            self.latest = latest
-            self.rollover()
+            prev, self.latest = self.latest, latest
+            self.rollover(prev)
 
-    def rollover(self):
+    def hist_rows(self, prev: int) -> List[str]:
+        """The lh rows of the rollover from ``prev`` to ``self.latest``: every bucket that enters
+        the window now (max(prev - buffer, latest - keep - 1) < b <= latest - buffer), ascending;
+        inside a bucket the series in st order, those with a sample in it only."""
+        rows = []
+        lo = max(prev - self.buffer, self.latest - self.keep - 1)
+        for b in range(lo + 1, self.latest - self.buffer + 1):
+            for server, srv in self.servers.items():
+                for service, svc in srv.items():
+                    arr = svc.get(b)
+                    if not arr:
+                        continue
+                    bins: Dict[int, int] = {}
+                    nan = 0
+                    for v in arr:
+                        # the engine stores int32; anything else is its NaN sentinel (engine.cpp)
+                        if v != v or not -2147483647 <= v <= 2147483647:
+                            nan += 1
+                        else:
+                            k = hist_bin(int(v))
+                            bins[k] = bins.get(k, 0) + 1
+                    rows.append(LatencyHistEntry(b * 10000, server, service, len(arr), nan,
+                                                 [(hist_lower(k), bins[k]) for k in sorted(bins)]).to_csv())
+        return rows
+
+    def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
             for svc in srv.values():
@@ -719,6 +746,9 @@ class StatsOracle:
         edge_ts = (self.latest - self.buffer - 1) * 10000
         for tx in self.heap.pop_all_le(edge_ts):
             self.emit_db(tx.to_csv())
+        if self.emit_hist is not None:
+            for row in self.hist_rows(self.latest - 1 if prev is None else prev):
+                self.emit_hist(row)
         for server, srv in self.servers.items():
             for service, svc in srv.items():
                 win: List[List[int]] = []
@@ -967,13 +997,15 @@ class PipelineOracle:
         self.fs: List[str] = []
         self.al: List[str] = []
         self.tx_out: List[str] = []
+        self.lh: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
         self.alerts = AlertsOracle(cfg, alert_clock, cooldown_key=g.get("cooldownKey", "service"))
         sc = cfg["streamCalcStats"]
         self.st = StatsOracle(self._on_st, self.tx_db.append, int(sc["intervalLengthInSeconds"]),
-                              int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]))
+                              int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
+                              emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None)
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

@@ -28,7 +28,9 @@ log = logging.getLogger("apm.pipeline")
 KIND_CODE = {"SOAP": 0, "SERVER": 1, "APP": 2}
 
 # Output streams (engine.h OutKind); the bit index is the position in this tuple.
-OUT_KINDS = ("transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb")
+OUT_KINDS = ("transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh")
+# keep_text=True materialises these; lh (K15 latency histograms) is opt-in through `outputs` only
+KEEP_TEXT_KINDS = tuple(k for k in OUT_KINDS if k != "lh")
 # What the reference persists (db_insert queue): released + audit tx, fs, al.  `transactions`
 # and `st` are internal hand-offs that only the AMQP bridge needs.
 DB_OUTPUTS = ("audit_db", "db", "fs", "al")
@@ -45,7 +47,9 @@ def output_mask(kinds) -> int:
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
                   **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
-    materialises every stream; `outputs` (iterable of OUT_KINDS) selects explicitly."""
+    materialises every stream but the opt-in lh; `outputs` (iterable of OUT_KINDS) selects explicitly.
+    The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
+    existed, `outputs` was ignored under keep_text)."""
     g = cfg.get("gpu", {})
     zc = cfg["streamCalcZScore"]
     ac = cfg["streamProcessAlerts"]
@@ -110,7 +114,7 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         # keep it proportional to their batch size
         "tx_ring_bytes": min(int(g.get("txTextRingMB", 4096)), max(256, (128 * int(g.get("batchBytes", 32 << 20))) >> 20)) << 20,
         "max_raw_services": max(int(g.get("maxRawServices", 1 << 18)), 2 * int(g.get("maxSeries", 1 << 17))),
-        "outputs": output_mask(OUT_KINDS if keep_text else (outputs or ())),
+        "outputs": output_mask(KEEP_TEXT_KINDS if keep_text else ()) | output_mask(outputs or ()),
     }
     # intervalLengthInSeconds only scales the TPM divisor: the bucket label is endTs without its
     # last 4 digits whatever the interval (stream_calc_stats.js:89-96, :186), as here

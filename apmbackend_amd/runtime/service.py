@@ -40,7 +40,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 from ..models.oracle import file_kind, server_of
 from ..models.pipeline import DB_OUTPUTS, KIND_CODE, OUT_KINDS, APMEngine
 from ..parallel.dist import dist_env, shard_servers
-from ..utils.config import ConfigWatcher, as_bool, read_apm_config
+from ..utils.config import ConfigWatcher, as_bool, gpu_opt, read_apm_config
 from . import logger as apmlog
 from .notifier import AlertNotifier
 from .sinks import DBInserter
@@ -147,6 +147,8 @@ class IngestService:
         outs = set(DB_OUTPUTS)
         if as_bool(g.get("serverRollup", False)):  # K14 per-JVM rollup fused with JMX gauges
             outs.add("sx")
+        if as_bool(gpu_opt(self.cfg, "latencyHistogram")):  # K15 per-interval latency histograms
+            outs.add("lh")
         if self.world > 1 and engine == "native" and as_bool(g.get("fleetBaseline", True)) \
                 and as_bool(g.get("fleetBaselineRows", True)):
             outs.add("fb")  # fleet-merged per-service baselines (rank 0 emits them)
@@ -267,6 +269,8 @@ class IngestService:
                     self.producers[q] = self.qm.get_queue(qmap[q], "p")
             if "fb" in self.outs_set:  # not a db_insert record type of the reference: own queue
                 self.producers["fleet"] = self.qm.get_queue(g.get("fleetQueue", "fleet_baseline"), "p")
+            if "lh" in self.outs_set:  # likewise (stream_insert_db.js does not know the type)
+                self.producers["hist"] = self.qm.get_queue(gpu_opt(self.cfg, "histQueue"), "p")
             self.qm.on("pause", lambda: log.info("queue backpressure: pausing ingest"))
         elif self.mode != "none":
             raise ValueError(f"unknown gpu.outputMode {self.mode!r}")
@@ -820,11 +824,13 @@ class IngestService:
             counts[k] = blob.count(b"\n")
             if k == "al" and self.notifier:
                 self.notifier.add_lines(blob.decode("utf-8").split("\n"))
-            if self.inserter is not None and (k in DB_OUTPUTS or k == "fb"):
+            if self.inserter is not None and (k in DB_OUTPUTS or k in ("fb", "lh")):
                 self.inserter.consume_bytes(blob)
             elif self.qm is not None:
                 if k == "fb":
                     prod = self.producers.get("fleet")
+                elif k == "lh":
+                    prod = self.producers.get("hist")
                 elif k in DB_OUTPUTS:
                     prod = self.producers["db"]
                 elif k == "transactions":

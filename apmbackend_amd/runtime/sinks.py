@@ -54,8 +54,12 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
                           "beanpoolmaxsize"]),
     # fleet-merged per-service baselines (fb records, rank 0): not part of the reference schema
     "fb": ("dbFleetTable", ["timestamp", "service", "lag", "nseries", "stats"]),
+    # per-interval latency histograms (lh records, gpu.latencyHistogram): not part of the reference schema
+    "lh": ("dbHistTable", ["timestamp", "server", "service", "count", "nan", "bins"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh")
+# tables of the record types the reference does not know (its config has no key for them)
+DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -139,9 +143,9 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = None
         elif c in _TS_COLS:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
-        elif c in ("stats", "entry"):
+        elif c in ("stats", "entry", "bins"):
             out[c] = json.loads(v)
-        elif c in ("tpm", "elapsed", "acctnum", "nseries") or rtype == "jx" and c not in ("server",):
+        elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan") or rtype == "jx" and c not in ("server",):
             f = float(v)
             out[c] = int(f) if f.is_integer() and "." not in v and "e" not in v else f
         else:
@@ -324,9 +328,10 @@ def make_writer(ins_cfg: Dict[str, Any]) -> Writer:
 def save_resume(path: str, buffers: Dict[str, Deque[Dict[str, Any]]]):
     """util_methods.saveToResumeFile with the Map replacer: {"dataType":"Map","value":[...]}
     (atomic: tmp + rename)."""
-    # the reference's four buffers always; the fleet buffer (our addition) only when it holds rows
+    # the reference's four buffers always; the fleet and histogram buffers (our additions) only
+    # when they hold rows
     doc = {"dataType": "Map", "value": [[t, [_json_row(r) for r in rows]] for t, rows in buffers.items()
-                                        if t != "fb" or rows]}
+                                        if t not in DEFAULT_TABLES or rows]}
     tmp = path + ".tmp"
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     with open(tmp, "w") as f:
@@ -431,7 +436,7 @@ class DBInserter:
         self.cfg = cfg
         self._limit = int(ic.get("dbInsertBufferLimit", 1000))
         self._max_wait_s = float(ic.get("dbMaxTimeBetweenInsertsMs", 5000)) / 1000.0
-        self.tables = {t: ic.get(key, "apm_fleet_stats" if t == "fb" else t) for t, (key, _cols) in COLUMNS.items()}
+        self.tables = {t: ic.get(key, DEFAULT_TABLES.get(t, t)) for t, (key, _cols) in COLUMNS.items()}
         self.clock = clock
         self.stats = stats or DBStats(float(cfg.get("statLogIntervalInSeconds", 60)))
         self.buffers: Dict[str, Deque[Dict[str, Any]]] = {t: deque() for t in TYPES}

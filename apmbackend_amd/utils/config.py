@@ -80,6 +80,19 @@ GPU_DEFAULTS: Dict[str, Any] = {
     "faultInjection": {},             # {"rank", "dropBatchEvery", "duplicateBatchEvery", "exitAtBatch"}
 }
 
+# Opt-in keys of the gpu section that have no entry in a config that does not name them (the
+# loaded default config stays byte for byte what it was, and with it the config text the recorded
+# reference answers under tests/golden/refjs are keyed by): read with gpu_opt(cfg, key).
+GPU_OPTIONAL: Dict[str, Any] = {
+    "latencyHistogram": False,        # K15 "lh" stream: per-interval latency histograms (docs/HISTOGRAM.md)
+    "histQueue": "latency_hist",      # amqp mode: the queue the lh records go to
+}
+
+def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
+    """An optional gpu key's value, GPU_OPTIONAL's default when the config does not name it."""
+    return (cfg.get("gpu") or {}).get(key, GPU_OPTIONAL[key])
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -105,11 +118,11 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         return None
     cfg["apmConfigFilePath"] = path
     cfg.setdefault("gpu", {})
-    unknown = set(cfg["gpu"]) - set(GPU_DEFAULTS)
+    unknown = set(cfg["gpu"]) - set(GPU_DEFAULTS) - set(GPU_OPTIONAL)
     for k in sorted(unknown):
         log.warning("unknown key gpu.%s in %s (ignored)", k, path)
     merged = dict(GPU_DEFAULTS)
-    merged.update({k: v for k, v in cfg["gpu"].items() if k in GPU_DEFAULTS})
+    merged.update({k: v for k, v in cfg["gpu"].items() if k in GPU_DEFAULTS or k in GPU_OPTIONAL})
     cfg["gpu"] = merged
     return cfg
 

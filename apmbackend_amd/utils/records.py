@@ -269,6 +269,52 @@ class FleetEntry:
                 "stats": {k: _num_or_none(v) for k, v in zip(keys, self.stats)}}
 
 
+# ---- lh: per-interval latency histogram (docs/HISTOGRAM.md).  Integer-only log-linear bins:
+# four sub-bins per power of two, 120 bins for the int32 range (the device rule: kernels/common.h).
+HIST_BINS = 120
+
+
+def hist_bin(v: int) -> int:
+    """Bin of an elapsed value (the stored int32): v <= 0 -> 0, 1..3 -> v, else 4 * (e - 1) + sub
+    with e = floor(log2 v) and sub the two bits below the leading one."""
+    v = int(v)
+    if v <= 0:
+        return 0
+    if v < 4:
+        return v
+    e = v.bit_length() - 1
+    return 4 * (e - 1) + ((v >> (e - 2)) & 3)
+
+
+def hist_lower(b: int) -> int:
+    """Smallest value of bin b (bin 0 also holds everything below 1)."""
+    return b if b < 4 else (4 + b % 4) << (b // 4 - 1)
+
+
+@dataclass
+class LatencyHistEntry:
+    """``lh|bucketStartMs|server|service|count|nan|lo:c,lo:c,...`` -- the elapsed times of one
+    (10 s bucket, series) as a sparse histogram (no reference counterpart).  ``count`` includes the
+    ``nan`` samples; ``bins`` holds (bin lower bound, samples) pairs, non-zero bins ascending."""
+    timestamp: Num
+    server: str
+    service: str
+    count: Num
+    nan: Num
+    bins: List[tuple]
+    type: str = "lh"
+
+    def to_csv(self) -> str:
+        pairs = ",".join(f"{lo}:{c}" for lo, c in self.bins)
+        return (f"lh|{js_str(self.timestamp)}|{self.server}|{self.service}|{js_str(self.count)}|"
+                f"{js_str(self.nan)}|{pairs}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "count": _num_or_none(self.count), "nan": _num_or_none(self.nan),
+                "bins": {str(lo): c for lo, c in self.bins}}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -302,7 +348,16 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
             p = _pad(g.split(":") if g is not None else [], 2)
             st += [parse_float(p[0]), parse_float(p[1])]
         return FleetEntry(parse_int(a[1]), a[2], a[3], parse_int(a[4]), st)
+    if t == "lh":
+        a = _pad(arr, 7)
+        bins = []
+        for pr in (a[6] or "").split(","):
+            lo, _sep, c = pr.partition(":")
+            lo, c = parse_int(lo), parse_int(c)
+            if lo == lo and c == c:  # (a malformed pair is dropped, as copyenc.cpp does)
+                bins.append((int(lo), int(c)))
+        return LatencyHistEntry(parse_int(a[1]), a[2], a[3], parse_int(a[4]), parse_int(a[5]), bins)
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh")
