@@ -271,6 +271,18 @@ extern "C" const char* apm_csrc_hash();  // build/native/provenance.cpp (generat
 PYBIND11_MODULE(_apm_native, m) {
   m.doc() = "apm-mi355x native runtime (HIP kernels for gfx950 + host runtime)";
   m.def("csrc_hash", []() { return std::string(apm_csrc_hash()); });
+  // process-wide live GPU resources over every owner (runtime/hipres.h): leak checks in the tests
+  m.def("live_resources", []() {
+    const LiveResources& L = live_resources();
+    py::dict d;
+    d["device_blocks"] = L.device_blocks.load();
+    d["device_bytes"] = L.device_bytes.load();
+    d["pinned_blocks"] = L.pinned_blocks.load();
+    d["pinned_bytes"] = L.pinned_bytes.load();
+    d["events"] = L.events.load();
+    d["streams"] = L.streams.load();
+    return d;
+  });
   m.attr("EVENT_SIZE") = (int)sizeof(Event);
   m.def("hash_bytes", [](py::bytes b, uint64_t seed) {
     const std::string s = b;

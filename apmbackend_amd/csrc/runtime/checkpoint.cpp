@@ -271,7 +271,7 @@ uint64_t Engine::dump_state(const std::string& path, const std::string& reason) 
   num("rollover_idx", (double)rollover_idx_);
   num("n_series", (double)n_series_);
   num("max_series", (double)cfg_.max_series);
-  num("device_bytes", (double)device_bytes_);
+  num("device_bytes", (double)res_.device_bytes());
   num("batches", (double)m.batches); num("lines", (double)m.lines); num("bytes", (double)m.bytes);
   num("events", (double)m.events); num("tx", (double)m.tx); num("tx_dropped", (double)m.tx_dropped);
   num("rollovers", (double)m.rollovers); num("alerts", (double)m.alerts); num("released", (double)m.released);
@@ -392,9 +392,8 @@ void Engine::write_series_dump(BinWriter& w) {
 uint64_t Engine::save_state(const std::string& path, const std::string& extra) {
   checkpoint_wait();  // an asynchronous checkpoint in flight finishes first
   checkpoint_quiesce("save_state");
-  void* bounce = nullptr;
-  HIP_OK(hipHostMalloc(&bounce, kBounce, hipHostMallocDefault));
-  struct Guard { void* p; ~Guard() { hipHostFree(p); } } guard{bounce};
+  ScopedPinned guard(res_, kBounce);
+  void* bounce = guard.p;
   BinWriter w(path);
   write_small_sections(w);
   // rings: every row of every LAG, synchronously through the bounce buffer
@@ -420,7 +419,7 @@ uint64_t Engine::save_state(const std::string& path, const std::string& extra) {
 // Every section but the rings.  Device arrays are read synchronously (the engine is quiescent).
 void Engine::write_small_sections(BinWriter& w) {
   const int32_t S = cfg_.max_series, n = n_series_;
-  if (!h_ck_bounce_) HIP_OK(hipHostMalloc(&h_ck_bounce_, kBounce, hipHostMallocDefault));
+  if (!h_ck_bounce_) res_.pin(h_ck_bounce_, kBounce);
   void* bounce = h_ck_bounce_;
 
   w.begin(SEC_CONFIG);
@@ -499,7 +498,7 @@ void Engine::write_small_sections(BinWriter& w) {
       if (N + 1 > ck_pack_n_) {
         auto drop = [this]() {
           for (void** q : {(void**)&d_ck_lens_, (void**)&d_ck_offs_, (void**)&d_ck_packed_, &d_ck_ptmp_}) {
-            dfree(*q);
+            res_.dfree(*q);
             *q = nullptr;
           }
           ck_pack_n_ = 0;
@@ -508,10 +507,10 @@ void Engine::write_small_sections(BinWriter& w) {
         drop();
         const uint64_t want = (N + 1) * 5 / 4;
         const size_t tb = apm_ck_pack_tmp_bytes(want);
-        d_ck_lens_ = (uint32_t*)dmalloc_try(want * 4);
-        d_ck_offs_ = (uint32_t*)dmalloc_try(want * 4);
-        d_ck_packed_ = (int32_t*)dmalloc_try(want * (size_t)cap * 4);
-        d_ck_ptmp_ = dmalloc_try(tb);
+        d_ck_lens_ = (uint32_t*)res_.dmalloc_try(want * 4);
+        d_ck_offs_ = (uint32_t*)res_.dmalloc_try(want * 4);
+        d_ck_packed_ = (int32_t*)res_.dmalloc_try(want * (size_t)cap * 4);
+        d_ck_ptmp_ = res_.dmalloc_try(tb);
         if (d_ck_lens_ && d_ck_offs_ && d_ck_packed_ && d_ck_ptmp_) {
           ck_pack_n_ = want;
           ck_ptmp_bytes_ = tb;
@@ -519,7 +518,7 @@ void Engine::write_small_sections(BinWriter& w) {
           drop();
         }
       }
-      if (!d_ck_slots_) d_ck_slots_ = (int32_t*)dmalloc_try((size_t)nslot_ * 4);
+      if (!d_ck_slots_) d_ck_slots_ = (int32_t*)res_.dmalloc_try((size_t)nslot_ * 4);
       dev_pack = ck_pack_n_ >= N + 1 && d_ck_slots_;
     }
     if (dev_pack) {
@@ -593,9 +592,9 @@ void Engine::write_small_sections(BinWriter& w) {
     const int64_t cnt[2] = {pool_n_, tail_n_};
     const size_t n_g = (size_t)(pool_n_ + tail_n_);
     if (n_g > ck_gids_cap_) {
-      dfree(d_ck_gids_);
+      res_.dfree(d_ck_gids_);
       ck_gids_cap_ = n_g + n_g / 4 + 1024;
-      d_ck_gids_ = (int64_t*)dmalloc_try(ck_gids_cap_ * 8);
+      d_ck_gids_ = (int64_t*)res_.dmalloc_try(ck_gids_cap_ * 8);
       if (!d_ck_gids_) ck_gids_cap_ = 0;
     }
     std::vector<int64_t> gids;
@@ -625,9 +624,9 @@ void Engine::write_small_sections(BinWriter& w) {
       if (!tot[k]) continue;
       const size_t need = ((size_t)tot[k] + 15) & ~(size_t)15;
       if (need > ck_text_cap_[k]) {
-        dfree(d_ck_text_[k]);
+        res_.dfree(d_ck_text_[k]);
         ck_text_cap_[k] = need + need / 4;
-        d_ck_text_[k] = (char*)dmalloc_try(ck_text_cap_[k]);
+        d_ck_text_[k] = (char*)res_.dmalloc_try(ck_text_cap_[k]);
         if (!d_ck_text_[k]) ck_text_cap_[k] = 0;
       }
       if (d_ck_text_[k])
@@ -745,9 +744,8 @@ std::string Engine::load_state(const std::string& path) {
 }
 
 void Engine::apply_ring_file(const std::string& path) {
-  void* bounce = nullptr;
-  HIP_OK(hipHostMalloc(&bounce, kBounce, hipHostMallocDefault));
-  struct Guard { void* p; ~Guard() { hipHostFree(p); } } guard{bounce};
+  ScopedPinned guard(res_, kBounce);
+  void* bounce = guard.p;
   BinReader rd(path);
   rd.skip_to(SEC_RING);
   const int32_t S = cfg_.max_series;
@@ -785,9 +783,8 @@ std::string Engine::load_small_state(const std::string& path) {
   if (batch_no_ != 0 || n_series_ != 0 || !files_.empty())
     throw std::runtime_error("load_state needs a freshly constructed engine (no files, no batches)");
   const int32_t S = cfg_.max_series;
-  void* bounce = nullptr;
-  HIP_OK(hipHostMalloc(&bounce, kBounce, hipHostMallocDefault));
-  struct Guard { void* p; ~Guard() { hipHostFree(p); } } guard{bounce};
+  ScopedPinned guard(res_, kBounce);
+  void* bounce = guard.p;
   BinReader rd(path);
 
   rd.begin(SEC_CONFIG);
@@ -900,12 +897,11 @@ std::string Engine::load_small_state(const std::string& path) {
       for (size_t i = 0; i < h_raw_series_.size(); ++i)
         if (h_raw_series_[i] >= 0) { pairs.push_back((int32_t)i); pairs.push_back(h_raw_series_[i]); }
       if (!pairs.empty()) {
-        int32_t* d = nullptr;
-        HIP_OK(hipMalloc((void**)&d, pairs.size() * 4));
+        int32_t* d = (int32_t*)res_.dmalloc_raw(pairs.size() * 4);
         HIP_OK(hipMemcpy(d, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
         apm_dj_scatter_i32(dj_->d_raw_series(), d, (uint32_t)(pairs.size() / 2), stream_);
         HIP_OK(hipStreamSynchronize(stream_));
-        HIP_OK(hipFree(d));
+        res_.dfree(d);
       }
     } else {
       const uint64_t ns = rd.pod<uint64_t>();
@@ -1056,21 +1052,10 @@ int64_t Engine::checkpoint_async(const std::string& prefix, const std::string& e
     CkDefer def;
     constexpr size_t kMinStage = (size_t)1 << 30;
     if (ck_defer_want_ > ck_defer_cap_ || !d_ck_defer_) {
-      if (d_ck_defer_) {
-        HIP_OK(hipFree(d_ck_defer_));
-        std::lock_guard<std::mutex> g(alloc_mu_);
-        device_bytes_ -= ck_defer_cap_;
-      }
+      res_.dfree(d_ck_defer_);
       const size_t cap = std::max(ck_defer_want_ + ck_defer_want_ / 2, kMinStage);
-      if (hipMalloc((void**)&d_ck_defer_, cap) != hipSuccess) {
-        (void)hipGetLastError();
-        d_ck_defer_ = nullptr;
-        ck_defer_cap_ = 0;
-      } else {
-        ck_defer_cap_ = cap;
-        std::lock_guard<std::mutex> g(alloc_mu_);
-        device_bytes_ += cap;
-      }
+      d_ck_defer_ = (char*)res_.dmalloc_try(cap);
+      ck_defer_cap_ = d_ck_defer_ ? cap : 0;
     }
     def.stage = d_ck_defer_;
     def.cap = ck_defer_cap_;
@@ -1129,7 +1114,7 @@ int64_t Engine::checkpoint_async(const std::string& prefix, const std::string& e
     // and ck_guard_rollover copies a row aside (the other 20 %) if a rollover reaches it first.
     job->streamed = true;
     const size_t main_cap = cap / 5 * 4, side_cap = cap - main_cap;
-    if (!ck_side_ev_) HIP_OK(hipEventCreateWithFlags(&ck_side_ev_, hipEventDisableTiming));
+    if (!ck_side_ev_) ck_side_ev_ = res_.new_event();
     std::lock_guard<std::mutex> g(cks_mu_);
     cks_ = CkStream{};
     cks_.on = true;
@@ -1189,9 +1174,8 @@ int64_t Engine::checkpoint_async(const std::string& prefix, const std::string& e
     size_t full = 0;
     for (int l = 0; l < cfg_.n_lags; ++l) full += (size_t)NSTAT * cfg_.lags[l] * (size_t)S * rb;
     const size_t want = job->streamed ? need : std::min(cap, std::max(need + need / 8, full));  // (room for the series table)
-    if (hipMalloc(&d_ck_stage_, want) != hipSuccess) {
-      (void)hipGetLastError();
-      d_ck_stage_ = nullptr;
+    d_ck_stage_ = res_.dmalloc_try(want);
+    if (!d_ck_stage_) {
       {
         std::lock_guard<std::mutex> g(cks_mu_);
         cks_.on = false;
@@ -1209,8 +1193,6 @@ int64_t Engine::checkpoint_async(const std::string& prefix, const std::string& e
       return job->seq;
     }
     ck_stage_bytes_ = want;
-    std::lock_guard<std::mutex> g(alloc_mu_);
-    device_bytes_ += want;
   }
   if (job->streamed) {
     // staged rows: all NSTAT planes of a position together (the row-major file layout)
@@ -1255,7 +1237,7 @@ int64_t Engine::checkpoint_async(const std::string& prefix, const std::string& e
         }
     }
   }
-  if (!ck_ev_) HIP_OK(hipEventCreateWithFlags(&ck_ev_, hipEventDisableTiming));
+  if (!ck_ev_) ck_ev_ = res_.new_event();
   HIP_OK(hipEventRecord(ck_ev_, stream_));
   trace_event("ck.ring_stage", tring, now_ms(), 0);
   ck_ridx_ = r1;
@@ -1366,17 +1348,18 @@ void Engine::ck_guard_rollover(int64_t r) {
 
 void Engine::free_ck_stage() {
   if (!d_ck_stage_) return;
-  HIP_OK(hipFree(d_ck_stage_));
+  res_.dfree(d_ck_stage_);
   d_ck_stage_ = nullptr;
-  std::lock_guard<std::mutex> g(alloc_mu_);
-  device_bytes_ -= ck_stage_bytes_;
   ck_stage_bytes_ = 0;
 }
 
 void Engine::checkpoint_writer() {
-  if (!ck_stream_) HIP_OK(hipStreamCreateWithFlags(&ck_stream_, hipStreamNonBlocking));
-  void* bounce = nullptr;
-  HIP_OK(hipHostMalloc(&bounce, kBounce, hipHostMallocDefault));
+  if (!ck_stream_) {
+    HIP_OK(hipStreamCreateWithFlags(&ck_stream_, hipStreamNonBlocking));
+    res_.adopt(ck_stream_);
+  }
+  ScopedPinned guard(res_, kBounce);
+  void* bounce = guard.p;
   for (;;) {
     std::shared_ptr<CkJob> job;
     {
@@ -1455,7 +1438,6 @@ void Engine::checkpoint_writer() {
     }
     ck_cv_.notify_all();
   }
-  hipHostFree(bounce);
 }
 
 // Appends a written file to the chain manifest (or starts a new chain with a base) and removes
@@ -1519,12 +1501,6 @@ void Engine::checkpoint_shutdown() {
   }
   ck_cv_.notify_all();
   if (ck_thread_.joinable()) ck_thread_.join();
-  if (d_ck_stage_) { hipFree(d_ck_stage_); d_ck_stage_ = nullptr; ck_stage_bytes_ = 0; }
-  if (d_ck_defer_) { hipFree(d_ck_defer_); d_ck_defer_ = nullptr; ck_defer_cap_ = 0; }
-  if (h_ck_bounce_) { hipHostFree(h_ck_bounce_); h_ck_bounce_ = nullptr; }
-  if (ck_ev_) { hipEventDestroy(ck_ev_); ck_ev_ = nullptr; }
-  if (ck_side_ev_) { hipEventDestroy(ck_side_ev_); ck_side_ev_ = nullptr; }
-  if (ck_stream_) { hipStreamDestroy(ck_stream_); ck_stream_ = nullptr; }
 }
 
 CheckpointInfo Engine::checkpoint_info() {
@@ -1560,12 +1536,11 @@ std::string Engine::ring_text(const int64_t* d_gid, int64_t n) {
   HIP_OK(hipStreamSynchronize(stream_));
   std::string out(total, '\0');
   if (total) {
-    char* d = nullptr;
-    HIP_OK(hipMalloc((void**)&d, ((size_t)total + 15) & ~(size_t)15));
+    char* d = (char*)res_.dmalloc_raw(((size_t)total + 15) & ~(size_t)15);
     apm_dj_gather_copy(d_gid, n, dj_->ring(), dj_->ring_cap(), d_rel_offs_, d, total, stream_);
     HIP_OK(hipMemcpyAsync(&out[0], d, total, hipMemcpyDeviceToHost, stream_));
     HIP_OK(hipStreamSynchronize(stream_));
-    HIP_OK(hipFree(d));
+    res_.dfree(d);
   }
   return out;
 }

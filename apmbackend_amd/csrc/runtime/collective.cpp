@@ -1,6 +1,7 @@
 // Collective backends: RCCL (production), TCP host transport (multi-process on one GPU), and an
 // in-process rendezvous (tests).
 #include "collective.h"
+#include "hipres.h"
 
 #include <arpa/inet.h>
 #include <netinet/in.h>
@@ -296,11 +297,10 @@ class HostCollective final : public Collective {
     shutdown_all();
     if (shm_) ::munmap(shm_, shm_len_);
     for (Staged* st : pool_) {
-      if (st->done) { hipEventSynchronize(st->done); hipEventDestroy(st->done); }
-      if (st->in) hipHostFree(st->in);
-      if (st->out) hipHostFree(st->out);
+      if (st->done) hipEventSynchronize(st->done);
       delete st;
     }
+    res_.release_all();
   }
   int nranks() const override { return n_; }
   int rank() const override { return r_; }
@@ -391,6 +391,7 @@ class HostCollective final : public Collective {
   bool aborted() const override { return aborted_.load(); }
 
  private:
+  HipRes res_;  // the staged ops' pinned pairs and events
   // pinned in / out stages, reused once the H2D that read `out` has completed (`done`)
   struct Staged {
     size_t cap = 0;
@@ -411,9 +412,9 @@ class HostCollective final : public Collective {
     }
     Staged* st = new Staged();
     st->cap = std::max<size_t>(4096, bytes);
-    HIP_OK(hipHostMalloc(&st->in, st->cap, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc(&st->out, st->cap * (size_t)n_, hipHostMallocDefault));
-    HIP_OK(hipEventCreateWithFlags(&st->done, hipEventDisableTiming));
+    res_.pin(st->in, st->cap);
+    res_.pin(st->out, st->cap * (size_t)n_);
+    st->done = res_.new_event();
     pool_.push_back(st);
     return st;
   }

@@ -45,25 +45,6 @@ uint64_t pow2_at_least(uint64_t v) {
 }
 }  // namespace
 
-void* DeviceJoin::dmalloc(size_t bytes) {
-  void* p = nullptr;
-  bytes = (bytes + 255) & ~(size_t)255;
-  HIP_OK(hipMalloc(&p, bytes));
-  HIP_OK(hipMemsetAsync(p, 0, bytes, stream_));
-  allocs_.push_back(p);
-  device_bytes_ += bytes;
-  return p;
-}
-
-// the join stream must be idle (callers synchronize first)
-void DeviceJoin::dfree(void* p, size_t bytes) {
-  if (!p) return;
-  auto it = std::find(allocs_.begin(), allocs_.end(), p);
-  if (it != allocs_.end()) allocs_.erase(it);
-  HIP_OK(hipFree(p));
-  device_bytes_ -= (bytes + 255) & ~(size_t)255;
-}
-
 DeviceJoin::DeviceJoin(const DevJoinConfig& cfg, Dictionary* dict, const std::vector<FileInfo>* files,
                        const std::vector<std::string>* servers)
     : cfg_(cfg), dict_(dict), files_(files), servers_(servers) {
@@ -79,124 +60,124 @@ DeviceJoin::DeviceJoin(const DevJoinConfig& cfg, Dictionary* dict, const std::ve
     HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi));
     const char* pe = std::getenv("APM_JOIN_PRIO");
     HIP_OK(hipStreamCreateWithPriority(&stream_, hipStreamNonBlocking, pe && pe[0] == '0' ? lo : hi));
+    res_.adopt(stream_);
   }
   const uint32_t E = std::max<uint32_t>(cfg_.max_events, 1024);
   out_cap_ = 2 * E + (1u << 16);
   for (int k = 0; k < 2; ++k) {
     Slot& s = sl_[k];
-    s.d_bytes = (uint8_t*)dmalloc(cfg_.max_batch_bytes + 256);
-    s.d_events = (Event*)dmalloc((size_t)E * sizeof(Event));
-    s.host_flag = (uint8_t*)dmalloc(E + 64);
-    s.d_host_ev = (Event*)dmalloc((size_t)E * sizeof(Event));
-    s.d_host_idx = (uint32_t*)dmalloc((size_t)E * 4);
-    s.d_mh_idx = (uint32_t*)dmalloc((size_t)E * 4);
-    s.d_walk_idx = (uint32_t*)dmalloc((size_t)E * 4);
-    s.d_aud = (AudF*)dmalloc((size_t)E * sizeof(AudF));
-    s.d_n_host = (SelCount*)dmalloc(64);
-    HIP_OK(hipHostMalloc((void**)&s.h_host_ev, (size_t)E * sizeof(Event), hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&s.h_host_idx, (size_t)E * 4, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&s.h_n_host, 64, hipHostMallocDefault));
+    s.d_bytes = (uint8_t*)res_.dmalloc_on(stream_, cfg_.max_batch_bytes + 256);
+    s.d_events = (Event*)res_.dmalloc_on(stream_, (size_t)E * sizeof(Event));
+    s.host_flag = (uint8_t*)res_.dmalloc_on(stream_, E + 64);
+    s.d_host_ev = (Event*)res_.dmalloc_on(stream_, (size_t)E * sizeof(Event));
+    s.d_host_idx = (uint32_t*)res_.dmalloc_on(stream_, (size_t)E * 4);
+    s.d_mh_idx = (uint32_t*)res_.dmalloc_on(stream_, (size_t)E * 4);
+    s.d_walk_idx = (uint32_t*)res_.dmalloc_on(stream_, (size_t)E * 4);
+    s.d_aud = (AudF*)res_.dmalloc_on(stream_, (size_t)E * sizeof(AudF));
+    s.d_n_host = (SelCount*)res_.dmalloc_on(stream_, 64);
+    res_.pin(s.h_host_ev, (size_t)E * sizeof(Event));
+    res_.pin(s.h_host_idx, (size_t)E * 4);
+    res_.pin(s.h_n_host, 64);
     std::memset(s.h_n_host, 0, 64);
-    s.d_chunk_next = (int32_t*)dmalloc(((size_t)cfg_.max_chunks + 2) * 4);
-    s.d_chunk_first = (uint8_t*)dmalloc((size_t)cfg_.max_chunks + 2);
-    HIP_OK(hipHostMalloc((void**)&s.h_chunk_next, ((size_t)cfg_.max_chunks + 2) * 4, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&s.h_chunk_first, (size_t)cfg_.max_chunks + 2, hipHostMallocDefault));
-    s.d_tx = (TxRec*)dmalloc((size_t)out_cap_ * sizeof(TxRec));
-    s.d_tx_raw = (int32_t*)dmalloc((size_t)out_cap_ * 4);
-    s.d_tx_gid = (int64_t*)dmalloc((size_t)out_cap_ * 8);
-    HIP_OK(hipEventCreateWithFlags(&s.free_ev, hipEventDisableTiming));
+    s.d_chunk_next = (int32_t*)res_.dmalloc_on(stream_, ((size_t)cfg_.max_chunks + 2) * 4);
+    s.d_chunk_first = (uint8_t*)res_.dmalloc_on(stream_, (size_t)cfg_.max_chunks + 2);
+    res_.pin(s.h_chunk_next, ((size_t)cfg_.max_chunks + 2) * 4);
+    res_.pin(s.h_chunk_first, (size_t)cfg_.max_chunks + 2);
+    s.d_tx = (TxRec*)res_.dmalloc_on(stream_, (size_t)out_cap_ * sizeof(TxRec));
+    s.d_tx_raw = (int32_t*)res_.dmalloc_on(stream_, (size_t)out_cap_ * 4);
+    s.d_tx_gid = (int64_t*)res_.dmalloc_on(stream_, (size_t)out_cap_ * 8);
+    s.free_ev = res_.new_event();
   }
   table_cap_ = 1u << cfg_.table_bits;
   init_table_cap_ = table_cap_;
   init_arena_cap_ = cfg_.arena_cap;
-  d_table_ = (KeyState*)dmalloc((size_t)table_cap_ * sizeof(KeyState));
-  d_reg_ = (RegSlot*)dmalloc(((size_t)1 << cfg_.reg_bits) * sizeof(RegSlot));
+  d_table_ = (KeyState*)res_.dmalloc_on(stream_, (size_t)table_cap_ * sizeof(KeyState));
+  d_reg_ = (RegSlot*)res_.dmalloc_on(stream_, ((size_t)1 << cfg_.reg_bits) * sizeof(RegSlot));
   miss_cap_ = E;
-  d_miss_ = (RegMiss*)dmalloc((size_t)miss_cap_ * sizeof(RegMiss));
-  HIP_OK(hipHostMalloc((void**)&h_miss_, (size_t)miss_cap_ * sizeof(RegMiss), hipHostMallocDefault));
-  d_arena_ = (NeedEnt*)dmalloc((size_t)cfg_.arena_cap * sizeof(NeedEnt));
-  d_exp_lo_ = (uint64_t*)dmalloc(8 * 4096);
-  d_exp_hi_ = (uint64_t*)dmalloc(8 * 4096);
-  HIP_OK(hipHostMalloc((void**)&h_exp_, 2 * 8 * 4096, hipHostMallocDefault));
-  HIP_OK(hipHostGetDevicePointer((void**)&hd_exp_, h_exp_, 0));
+  d_miss_ = (RegMiss*)res_.dmalloc_on(stream_, (size_t)miss_cap_ * sizeof(RegMiss));
+  res_.pin(h_miss_, (size_t)miss_cap_ * sizeof(RegMiss));
+  d_arena_ = (NeedEnt*)res_.dmalloc_on(stream_, (size_t)cfg_.arena_cap * sizeof(NeedEnt));
+  d_exp_lo_ = (uint64_t*)res_.dmalloc_on(stream_, 8 * 4096);
+  d_exp_hi_ = (uint64_t*)res_.dmalloc_on(stream_, 8 * 4096);
+  res_.pin(h_exp_, 2 * 8 * 4096);
   soap_cap_ = 1u << 16;
-  d_soap_ = (SoapState*)dmalloc((size_t)soap_cap_ * sizeof(SoapState));
+  d_soap_ = (SoapState*)res_.dmalloc_on(stream_, (size_t)soap_cap_ * sizeof(SoapState));
   if (E >= (1u << 21)) throw std::runtime_error("device join: gpu.maxLinesPerBatch must be below 2^21");
-  d_sel_val_ = (uint64_t*)dmalloc(((size_t)E + 64) * 8);
-  d_sel_pos_ = (uint64_t*)dmalloc(((size_t)E + 64) * 8);
-  d_walk_lo_ = (uint32_t*)dmalloc(((size_t)cfg_.max_chunks + 2) * 4);
-  d_file_first_ = (int32_t*)dmalloc((size_t)soap_cap_ * 4);
+  d_sel_val_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)E + 64) * 8);
+  d_sel_pos_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)E + 64) * 8);
+  d_walk_lo_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)cfg_.max_chunks + 2) * 4);
+  d_file_first_ = (int32_t*)res_.dmalloc_on(stream_, (size_t)soap_cap_ * 4);
   for (AudGen& g : aud_gen_) {
-    g.carry = (AudCarry*)dmalloc((size_t)soap_cap_ * sizeof(AudCarry));
+    g.carry = (AudCarry*)res_.dmalloc_on(stream_, (size_t)soap_cap_ * sizeof(AudCarry));
     aud_reserve(g, 4096, 16384, 1u << 20);
   }
-  d_file_server_ = (int32_t*)dmalloc((size_t)soap_cap_ * 4);
-  d_file_skey_ = (uint64_t*)dmalloc((size_t)soap_cap_ * 8);
-  d_file_fkey_ = (uint64_t*)dmalloc((size_t)soap_cap_ * 8);
+  d_file_server_ = (int32_t*)res_.dmalloc_on(stream_, (size_t)soap_cap_ * 4);
+  d_file_skey_ = (uint64_t*)res_.dmalloc_on(stream_, (size_t)soap_cap_ * 8);
+  d_file_fkey_ = (uint64_t*)res_.dmalloc_on(stream_, (size_t)soap_cap_ * 8);
   h_file_skey_.reserve(soap_cap_);  // (the pre-pass lane reads them while files are added)
   h_file_fkey_.reserve(soap_cap_);
-  d_rawtab_ = (RawSvc*)dmalloc((size_t)cfg_.max_raw * sizeof(RawSvc));
-  d_raw_series_ = (int32_t*)dmalloc((size_t)cfg_.max_raw * 4);
-  d_raw_first_ = (int32_t*)dmalloc((size_t)cfg_.max_raw * 4);
+  d_rawtab_ = (RawSvc*)res_.dmalloc_on(stream_, (size_t)cfg_.max_raw * sizeof(RawSvc));
+  d_raw_series_ = (int32_t*)res_.dmalloc_on(stream_, (size_t)cfg_.max_raw * 4);
+  d_raw_first_ = (int32_t*)res_.dmalloc_on(stream_, (size_t)cfg_.max_raw * 4);
   HIP_OK(hipMemsetAsync(d_raw_series_, 0xff, (size_t)cfg_.max_raw * 4, stream_));
   HIP_OK(hipMemsetAsync(d_raw_first_, 0x7f, (size_t)cfg_.max_raw * 4, stream_));
   raw_info_.reserve(cfg_.max_raw);
-  HIP_OK(hipHostMalloc((void**)&h_rawtab_, (size_t)cfg_.max_raw * sizeof(RawSvc), hipHostMallocDefault));
-  d_reg_fill_ = (int32_t*)dmalloc((size_t)E * 8);
-  HIP_OK(hipHostMalloc((void**)&h_reg_fill_, (size_t)E * 8, hipHostMallocDefault));
-  d_out_ = (TxDev*)dmalloc((size_t)out_cap_ * sizeof(TxDev));
-  d_lens_ = (uint32_t*)dmalloc(((size_t)out_cap_ + 1) * 16);
-  d_offs_ = (uint32_t*)dmalloc(((size_t)out_cap_ + 1) * 16);
-  d_bucket_ = (int64_t*)dmalloc((size_t)out_cap_ * 8);
-  d_bmax_ = (int64_t*)dmalloc((size_t)out_cap_ * 8);
-  d_cand_ = (uint32_t*)dmalloc((size_t)out_cap_ * 4);
-  d_cand_bucket_ = (int64_t*)dmalloc((size_t)out_cap_ * 8);
-  d_unres_ = (uint32_t*)dmalloc((size_t)out_cap_ * 8);
-  HIP_OK(hipHostMalloc((void**)&h_cand_, (size_t)out_cap_ * 4, hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&h_cand_bucket_, (size_t)out_cap_ * 8, hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&h_unres_, (size_t)out_cap_ * 8, hipHostMallocDefault));
+  res_.pin(h_rawtab_, (size_t)cfg_.max_raw * sizeof(RawSvc));
+  d_reg_fill_ = (int32_t*)res_.dmalloc_on(stream_, (size_t)E * 8);
+  res_.pin(h_reg_fill_, (size_t)E * 8);
+  d_out_ = (TxDev*)res_.dmalloc_on(stream_, (size_t)out_cap_ * sizeof(TxDev));
+  d_lens_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)out_cap_ + 1) * 16);
+  d_offs_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)out_cap_ + 1) * 16);
+  d_bucket_ = (int64_t*)res_.dmalloc_on(stream_, (size_t)out_cap_ * 8);
+  d_bmax_ = (int64_t*)res_.dmalloc_on(stream_, (size_t)out_cap_ * 8);
+  d_cand_ = (uint32_t*)res_.dmalloc_on(stream_, (size_t)out_cap_ * 4);
+  d_cand_bucket_ = (int64_t*)res_.dmalloc_on(stream_, (size_t)out_cap_ * 8);
+  d_unres_ = (uint32_t*)res_.dmalloc_on(stream_, (size_t)out_cap_ * 8);
+  res_.pin(h_cand_, (size_t)out_cap_ * 4);
+  res_.pin(h_cand_bucket_, (size_t)out_cap_ * 8);
+  res_.pin(h_unres_, (size_t)out_cap_ * 8);
   ensure_tmp();
   sel_tmp_bytes_ = apm_dj_tmp_bytes(E, 1024);
-  d_sel_tmp_ = dmalloc(sel_tmp_bytes_);
-  d_counts_ = (JoinCounts*)dmalloc(sizeof(JoinCounts));
-  HIP_OK(hipHostMalloc((void**)&h_counts_, sizeof(JoinCounts), hipHostMallocDefault));
+  d_sel_tmp_ = res_.dmalloc_on(stream_, sel_tmp_bytes_);
+  d_counts_ = (JoinCounts*)res_.dmalloc_on(stream_, sizeof(JoinCounts));
+  res_.pin(h_counts_, sizeof(JoinCounts));
   std::memset(h_counts_, 0, sizeof(JoinCounts));
-  d_live_ = (unsigned long long*)dmalloc(64);
-  HIP_OK(hipHostMalloc((void**)&h_live_, 64, hipHostMallocDefault));
+  d_live_ = (unsigned long long*)res_.dmalloc_on(stream_, 64);
+  res_.pin(h_live_, 64);
   // chain-block pool (overflow of the per-key partial / parked-record / logId storage); grows
   // before any batch whose worst case exceeds its free blocks
   pool_n_ = (uint32_t)pow2_at_least(cfg_.pool_blocks ? std::max<uint32_t>(cfg_.pool_blocks, 1024)
                                                    : std::max<uint32_t>(E / 2, 1u << 16));
-  d_pool_ = (uint8_t*)dmalloc((size_t)pool_n_ * CHAIN_BLK);
-  d_pool_ring_ = (uint32_t*)dmalloc((size_t)pool_n_ * 4);
+  d_pool_ = (uint8_t*)res_.dmalloc_on(stream_, (size_t)pool_n_ * CHAIN_BLK);
+  d_pool_ring_ = (uint32_t*)res_.dmalloc_on(stream_, (size_t)pool_n_ * 4);
   apm_dj_pool_init(d_pool_ring_, pool_n_, d_counts_, stream_);
   h_counts_->pool_tail = h_counts_->pool_ptail = pool_n_;
-  d_ops_ = (JOp*)dmalloc((size_t)E * sizeof(JOp));
-  d_soap_code_ = (uint8_t*)dmalloc(E);
-  d_soap_num_ = (double*)dmalloc((size_t)E * 8);
-  d_soap_hash_ = (uint64_t*)dmalloc((size_t)E * 8);
-  d_chunk_ev_lo_ = (uint32_t*)dmalloc(((size_t)cfg_.max_chunks + 2) * 4);
-  d_seg_f_ = (uint32_t*)dmalloc(((size_t)cfg_.max_chunks + 2) * SOAP_SEGS * 4);
-  d_seg_in_ = (uint32_t*)dmalloc(((size_t)cfg_.max_chunks + 2) * SOAP_SEGS * 4);
-  d_chain_hash_ = (uint64_t*)dmalloc(((size_t)cfg_.max_chunks + 2) * 8);
-  d_op_slot_ = (uint32_t*)dmalloc(((size_t)E + 1) * 4);
-  d_op_slot_sorted_ = (uint32_t*)dmalloc(((size_t)E + 1) * 4);
-  d_op_idx_ = (uint32_t*)dmalloc(((size_t)E + 1) * 4);
-  d_op_idx_sorted_ = (uint32_t*)dmalloc(((size_t)E + 1) * 4);
+  d_ops_ = (JOp*)res_.dmalloc_on(stream_, (size_t)E * sizeof(JOp));
+  d_soap_code_ = (uint8_t*)res_.dmalloc_on(stream_, E);
+  d_soap_num_ = (double*)res_.dmalloc_on(stream_, (size_t)E * 8);
+  d_soap_hash_ = (uint64_t*)res_.dmalloc_on(stream_, (size_t)E * 8);
+  d_chunk_ev_lo_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)cfg_.max_chunks + 2) * 4);
+  d_seg_f_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)cfg_.max_chunks + 2) * SOAP_SEGS * 4);
+  d_seg_in_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)cfg_.max_chunks + 2) * SOAP_SEGS * 4);
+  d_chain_hash_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)cfg_.max_chunks + 2) * 8);
+  d_op_slot_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)E + 1) * 4);
+  d_op_slot_sorted_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)E + 1) * 4);
+  d_op_idx_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)E + 1) * 4);
+  d_op_idx_sorted_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)E + 1) * 4);
   exp_cap_ = cfg_.arena_cap;
-  d_exp_key_ = (uint64_t*)dmalloc(((size_t)exp_cap_ + 1) * 8);
-  d_exp_key_sorted_ = (uint64_t*)dmalloc(((size_t)exp_cap_ + 1) * 8);
-  d_exp_idx_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-  d_exp_idx_sorted_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-  d_exp_cnt_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-  d_exp_pos_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-  d_out_cnt_ = (uint32_t*)dmalloc(((size_t)E + 1) * 4);
-  d_out_pos_ = (uint32_t*)dmalloc(((size_t)E + 1) * 4);
-  d_stage_ = (TxDev*)dmalloc((size_t)E * 2 * sizeof(TxDev));
-  d_ovf_ = (DJOverflow*)dmalloc((size_t)DJ_OVF_CAP * sizeof(DJOverflow));
-  d_ring_ = (char*)dmalloc(cfg_.ring_bytes);
-  d_ring_pos_ = (uint64_t*)dmalloc(8);
-  d_big_ = (uint32_t*)dmalloc(8);
+  d_exp_key_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 8);
+  d_exp_key_sorted_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 8);
+  d_exp_idx_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+  d_exp_idx_sorted_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+  d_exp_cnt_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+  d_exp_pos_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+  d_out_cnt_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)E + 1) * 4);
+  d_out_pos_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)E + 1) * 4);
+  d_stage_ = (TxDev*)res_.dmalloc_on(stream_, (size_t)E * 2 * sizeof(TxDev));
+  d_ovf_ = (DJOverflow*)res_.dmalloc_on(stream_, (size_t)DJ_OVF_CAP * sizeof(DJOverflow));
+  d_ring_ = (char*)res_.dmalloc_on(stream_, cfg_.ring_bytes);
+  d_ring_pos_ = (uint64_t*)res_.dmalloc_on(stream_, 8);
+  d_big_ = (uint32_t*)res_.dmalloc_on(stream_, 8);
   HIP_OK(hipStreamSynchronize(stream_));
 }
 
@@ -205,34 +186,16 @@ DeviceJoin::DeviceJoin(const DevJoinConfig& cfg, Dictionary* dict, const std::ve
 void DeviceJoin::ensure_txt(size_t bytes) {
   if (bytes <= txt_cap_ && d_txt_tx_) return;
   const size_t cap = std::max(bytes, txt_cap_);
-  char* p = nullptr;
-  HIP_OK(hipMalloc((void**)&p, cap * 2));
-  if (d_txt_tx_) { HIP_OK(hipFree(d_txt_tx_)); device_bytes_ -= txt_cap_ * 2; }
+  char* p = (char*)res_.dmalloc_raw(cap * 2);
+  res_.dfree(d_txt_tx_);
   d_txt_tx_ = p;
   d_txt_db_ = p + cap;
   txt_cap_ = cap;
-  device_bytes_ += cap * 2;
 }
 
 DeviceJoin::~DeviceJoin() {
   hipStreamSynchronize(stream_);
-  if (live_ev_) hipEventDestroy(live_ev_);
-  for (auto& s : sl_) {
-    hipHostFree(s.h_host_ev); hipHostFree(s.h_host_idx); hipHostFree(s.h_n_host);
-    hipHostFree(s.h_chunk_next); hipHostFree(s.h_chunk_first);
-    hipEventDestroy(s.free_ev);
-  }
-  hipHostFree(h_miss_); hipHostFree(h_exp_); hipHostFree(h_rawtab_); hipHostFree(h_reg_fill_);
-  hipHostFree(h_cand_); hipHostFree(h_cand_bucket_); hipHostFree(h_unres_); hipHostFree(h_counts_); hipHostFree(h_live_);
-  if (h_cstats_) hipHostFree(h_cstats_);
-  if (cstats_ev_) hipEventDestroy(cstats_ev_);
-  if (h_hops_) hipHostFree(h_hops_);
-  if (h_hbuf_) hipHostFree(h_hbuf_);
-  if (h_txt_) hipHostFree(h_txt_);
-  if (h_ck_bounce_) hipHostFree(h_ck_bounce_);
-  if (d_txt_tx_) hipFree(d_txt_tx_);
-  for (void* p : allocs_) hipFree(p);
-  hipStreamDestroy(stream_);
+  res_.release_all();
 }
 
 // ---------------------------------------------------------------------------- parse-side hooks
@@ -639,17 +602,14 @@ void DeviceJoin::register_misses(const uint8_t* hb, uint32_t n_miss, hipStream_t
   }
   if (names_.size() > names_cap_) {
     const size_t cap = std::max<size_t>(names_.size() * 2, 1 << 20);
-    char* p = nullptr;
-    HIP_OK(hipMalloc((void**)&p, cap));
+    char* p = (char*)res_.dmalloc_raw(cap);
     if (d_names_) {
       HIP_OK(hipMemcpyAsync(p, d_names_, names_uploaded_, hipMemcpyDeviceToDevice, s));
       HIP_OK(hipStreamSynchronize(s));
-      HIP_OK(hipFree(d_names_));
-      device_bytes_ -= names_cap_;
+      res_.dfree(d_names_);
     }
     d_names_ = p;
     names_cap_ = cap;
-    device_bytes_ += cap;
   }
   if (names_.size() > names_uploaded_) {
     HIP_OK(hipMemcpyAsync(d_names_ + names_uploaded_, names_.data() + names_uploaded_, names_.size() - names_uploaded_,
@@ -696,10 +656,10 @@ void DeviceJoin::ensure_tmp() {
   if (need <= tmp_bytes_ && d_tmp_) return;
   if (d_tmp_) {
     HIP_OK(hipStreamSynchronize(stream_));
-    dfree(d_tmp_, tmp_bytes_);
+    res_.dfree(d_tmp_);
   }
   tmp_bytes_ = need;
-  d_tmp_ = dmalloc(tmp_bytes_);
+  d_tmp_ = res_.dmalloc_on(stream_, tmp_bytes_);
 }
 
 // Drop the dead keys (the live ones: acct / record not expired, or a live need entry).  Same size:
@@ -717,15 +677,15 @@ void DeviceJoin::rebuild_table(double now, uint32_t new_cap) {
     ++table_rebuilds_;
     return;
   }
-  KeyState* fresh = (KeyState*)dmalloc((size_t)new_cap * sizeof(KeyState));
+  KeyState* fresh = (KeyState*)res_.dmalloc_on(stream_, (size_t)new_cap * sizeof(KeyState));
   HIP_OK(hipMemsetAsync(fresh, 0, (size_t)new_cap * sizeof(KeyState), st));
   HIP_OK(hipMemsetAsync(d_live_, 0, 8, st));
   apm_dj_rebuild(d_table_, table_cap_, fresh, new_cap - 1, d_arena_, cfg_.arena_cap, now, d_counts_, d_live_, d_pool_,
                  d_pool_ring_, pool_n_ - 1, st);
   HIP_OK(hipMemcpyAsync(h_live_, d_live_, 8, hipMemcpyDeviceToHost, st));
   HIP_OK(hipStreamSynchronize(st));
-  dfree(d_table_, (size_t)table_cap_ * sizeof(KeyState));
-  if (d_table_spare_) dfree(d_table_spare_, (size_t)table_cap_ * sizeof(KeyState));
+  res_.dfree(d_table_);
+  if (d_table_spare_) res_.dfree(d_table_spare_);
   d_table_spare_ = nullptr;
   ++table_grows_;
   d_table_ = fresh;
@@ -742,9 +702,9 @@ void DeviceJoin::sync_keys() {
   if (keys_cap_ != table_cap_) {
     if (d_keys_) {
       HIP_OK(hipStreamSynchronize(stream_));
-      dfree(d_keys_, (size_t)keys_cap_ * 8);
+      res_.dfree(d_keys_);
     }
-    d_keys_ = (uint64_t*)dmalloc((size_t)table_cap_ * 8);
+    d_keys_ = (uint64_t*)res_.dmalloc_on(stream_, (size_t)table_cap_ * 8);
     keys_cap_ = table_cap_;
   }
   apm_dj_keys_sync(d_table_, table_cap_, d_keys_, stream_);
@@ -759,8 +719,8 @@ void DeviceJoin::sync_keys() {
 void DeviceJoin::rebuild_inplace(double now) {
   const size_t need = apm_dj_rebuild_scratch_bytes(table_cap_);
   if (need > rb_scratch_bytes_) {
-    if (d_rb_scratch_) dfree(d_rb_scratch_, rb_scratch_bytes_);
-    d_rb_scratch_ = (uint32_t*)dmalloc(need);
+    if (d_rb_scratch_) res_.dfree(d_rb_scratch_);
+    d_rb_scratch_ = (uint32_t*)res_.dmalloc_on(stream_, need);
     rb_scratch_bytes_ = need;
   }
   HIP_OK(hipMemsetAsync(d_live_, 0, 8, stream_));
@@ -773,7 +733,7 @@ void DeviceJoin::rebuild_table_async(double now) {
   rebuild_inplace(now);
   sync_keys();  // (the join stream's idle gap, with the rebuild)
   HIP_OK(hipMemcpyAsync(h_live_, d_live_, 8, hipMemcpyDeviceToHost, st));
-  if (!live_ev_) HIP_OK(hipEventCreateWithFlags(&live_ev_, hipEventDisableTiming));
+  if (!live_ev_) live_ev_ = res_.new_event();
   HIP_OK(hipEventRecord(live_ev_, st));
   keys_since_rebuild_ = 0;
   live_pending_ = true;
@@ -795,23 +755,23 @@ void DeviceJoin::idle_upkeep(double now, uint32_t n_next) {
 // table's `need` links follow them (through NeedEnt::vidx).
 void DeviceJoin::grow_arena(uint32_t new_cap, uint64_t lo) {
   hipStream_t st = stream_;
-  NeedEnt* fresh = (NeedEnt*)dmalloc((size_t)new_cap * sizeof(NeedEnt));
+  NeedEnt* fresh = (NeedEnt*)res_.dmalloc_on(stream_, (size_t)new_cap * sizeof(NeedEnt));
   apm_dj_arena_grow(d_arena_, cfg_.arena_cap, fresh, new_cap, lo, arena_head_, d_table_, table_cap_, st);
   HIP_OK(hipStreamSynchronize(st));
-  dfree(d_arena_, (size_t)cfg_.arena_cap * sizeof(NeedEnt));
+  res_.dfree(d_arena_);
   d_arena_ = fresh;
   // expiry scratch is sized by the arena
-  for (void* p : {(void*)d_exp_key_, (void*)d_exp_key_sorted_}) dfree(p, ((size_t)exp_cap_ + 1) * 8);
+  for (void* p : {(void*)d_exp_key_, (void*)d_exp_key_sorted_}) res_.dfree(p);
   for (void* p : {(void*)d_exp_idx_, (void*)d_exp_idx_sorted_, (void*)d_exp_cnt_, (void*)d_exp_pos_})
-    dfree(p, ((size_t)exp_cap_ + 1) * 4);
+    res_.dfree(p);
   cfg_.arena_cap = new_cap;
   exp_cap_ = new_cap;
-  d_exp_key_ = (uint64_t*)dmalloc(((size_t)exp_cap_ + 1) * 8);
-  d_exp_key_sorted_ = (uint64_t*)dmalloc(((size_t)exp_cap_ + 1) * 8);
-  d_exp_idx_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-  d_exp_idx_sorted_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-  d_exp_cnt_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-  d_exp_pos_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
+  d_exp_key_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 8);
+  d_exp_key_sorted_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 8);
+  d_exp_idx_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+  d_exp_idx_sorted_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+  d_exp_cnt_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+  d_exp_pos_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
   ensure_tmp();
   ++arena_grows_;
 }
@@ -824,19 +784,19 @@ void DeviceJoin::aud_reserve(AudGen& g, uint32_t autr, uint32_t items, uint64_t 
   if (!grow) return;
   HIP_OK(hipStreamSynchronize(stream_));
   if (autr > g.cap_autr) {
-    dfree(g.autr, (size_t)g.cap_autr * sizeof(AutrEnt));
+    res_.dfree(g.autr);
     g.cap_autr = std::max<uint32_t>(autr * 2, 4096);
-    g.autr = (AutrEnt*)dmalloc((size_t)g.cap_autr * sizeof(AutrEnt));
+    g.autr = (AutrEnt*)res_.dmalloc_on(stream_, (size_t)g.cap_autr * sizeof(AutrEnt));
   }
   if (items > g.cap_items) {
-    dfree(g.items, (size_t)g.cap_items * sizeof(AudItem));
+    res_.dfree(g.items);
     g.cap_items = std::max<uint32_t>(items * 2, 16384);
-    g.items = (AudItem*)dmalloc((size_t)g.cap_items * sizeof(AudItem));
+    g.items = (AudItem*)res_.dmalloc_on(stream_, (size_t)g.cap_items * sizeof(AudItem));
   }
   if (txt > g.cap_txt) {
-    dfree(g.txt, g.cap_txt);
+    res_.dfree(g.txt);
     g.cap_txt = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(txt * 2, 1u << 20), (1ull << 32) - 1);
-    g.txt = (char*)dmalloc(g.cap_txt);
+    g.txt = (char*)res_.dmalloc_on(stream_, g.cap_txt);
   }
 }
 
@@ -854,13 +814,13 @@ void DeviceJoin::grow_pool(uint64_t need_free) {
   uint64_t n = pool_n_;
   while (avail + (n - pool_n_) < need_free) n *= 2;
   if (n >= (1ull << 31)) throw std::runtime_error("device join: chain pool beyond 2^31 blocks");
-  uint8_t* pool = (uint8_t*)dmalloc((size_t)n * CHAIN_BLK);
-  uint32_t* ring = (uint32_t*)dmalloc((size_t)n * 4);
+  uint8_t* pool = (uint8_t*)res_.dmalloc_on(stream_, (size_t)n * CHAIN_BLK);
+  uint32_t* ring = (uint32_t*)res_.dmalloc_on(stream_, (size_t)n * 4);
   HIP_OK(hipMemcpyAsync(pool, d_pool_, (size_t)pool_n_ * CHAIN_BLK, hipMemcpyDeviceToDevice, st));
   apm_dj_pool_grow(d_pool_ring_, pool_n_ - 1, ring, pool_n_, (uint32_t)n, d_counts_, st);
   HIP_OK(hipStreamSynchronize(st));
-  dfree(d_pool_, (size_t)pool_n_ * CHAIN_BLK);
-  dfree(d_pool_ring_, (size_t)pool_n_ * 4);
+  res_.dfree(d_pool_);
+  res_.dfree(d_pool_ring_);
   d_pool_ = pool;
   d_pool_ring_ = ring;
   pool_n_ = (uint32_t)n;
@@ -938,32 +898,16 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
   spans.clear();
   double sp = phase_t[1];
   auto span = [&](const char* name) { const double t = clock_ms(); spans.push_back({name, {sp, t}}); sp = t; };
-  if (hops_.size() > h_hops_cap_) {
-    if (h_hops_) HIP_OK(hipHostFree(h_hops_));
-    h_hops_cap_ = hops_.size() * 2 + 65536;
-    HIP_OK(hipHostMalloc((void**)&h_hops_, h_hops_cap_ * sizeof(HostOp), hipHostMallocDefault));
-    HIP_OK(hipHostGetDevicePointer((void**)&hd_hops_, h_hops_, 0));
-  }
-  if (hbuf_.size() > h_hbuf_cap_) {
-    if (h_hbuf_) HIP_OK(hipHostFree(h_hbuf_));
-    h_hbuf_cap_ = hbuf_.size() * 2 + (4 << 20);
-    HIP_OK(hipHostMalloc((void**)&h_hbuf_, h_hbuf_cap_, hipHostMallocDefault));
-    HIP_OK(hipHostGetDevicePointer((void**)&hd_hbuf_, h_hbuf_, 0));
-  }
+  res_.reserve(h_hops_, hops_.size(), hops_.size() * 2 + 65536, true);
+  res_.reserve(h_hbuf_, hbuf_.size(), hbuf_.size() * 2 + (4 << 20), true);
   span("u.hostgrow");
   if (hops_.size() > d_hops_cap_) {
     d_hops_cap_ = hops_.size() * 2 + 65536;
-    HostOp* p = nullptr;
-    HIP_OK(hipMalloc((void**)&p, d_hops_cap_ * sizeof(HostOp)));
-    allocs_.push_back(p);
-    d_hops_ = p;  // the old buffer stays allocated (rare growth)
+    d_hops_ = (HostOp*)res_.dmalloc_raw(d_hops_cap_ * sizeof(HostOp));  // the old buffer stays allocated (rare growth)
   }
   if (hbuf_.size() > d_hbuf_cap_) {
     d_hbuf_cap_ = hbuf_.size() * 2 + (4 << 20);
-    uint8_t* p = nullptr;
-    HIP_OK(hipMalloc((void**)&p, d_hbuf_cap_));
-    allocs_.push_back(p);
-    d_hbuf_ = p;
+    d_hbuf_ = (uint8_t*)res_.dmalloc_raw(d_hbuf_cap_);
   }
   span("u.devgrow");
   // The host ops (~160 KB a batch) are read by a kernel over the host link (apm_copy on the join
@@ -973,13 +917,13 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
   if (!hops_.empty()) {
     std::memcpy(h_hops_, hops_.data(), hops_.size() * sizeof(HostOp));
     span("u.hops.memcpy");
-    apm_copy(d_hops_, hd_hops_, hops_.size() * sizeof(HostOp), st);
+    apm_copy(d_hops_, h_hops_.d, hops_.size() * sizeof(HostOp), st);
     span("u.hops.h2d");
   }
   if (!hbuf_.empty()) {
     std::memcpy(h_hbuf_, hbuf_.data(), hbuf_.size());
     span("u.hbuf.memcpy");
-    apm_copy(d_hbuf_, hd_hbuf_, hbuf_.size(), st);
+    apm_copy(d_hbuf_, h_hbuf_.d, hbuf_.size(), st);
     span("u.hbuf.h2d");
   }
   // ---- file -> server table (and the files' keys, normally synced by the parse's select_host)
@@ -1006,8 +950,8 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
     ++n_reg;
   }
   if (n_reg) {
-    apm_copy(d_exp_lo_, hd_exp_, (size_t)n_reg * 8, st);
-    apm_copy(d_exp_hi_, (const uint64_t*)hd_exp_ + 4096, (size_t)n_reg * 8, st);
+    apm_copy(d_exp_lo_, h_exp_.d, (size_t)n_reg * 8, st);
+    apm_copy(d_exp_hi_, (const uint64_t*)h_exp_.d + 4096, (size_t)n_reg * 8, st);
   }
   span("u.files+exp");
   // ---- join
@@ -1027,8 +971,8 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
   a.op_slot = d_op_slot_; a.op_slot_sorted = d_op_slot_sorted_; a.op_idx = d_op_idx_; a.op_idx_sorted = d_op_idx_sorted_;
   a.tmp = d_tmp_; a.tmp_bytes = tmp_bytes_;
   if (heads_cap_ != table_cap_) {  // (the join stream is ordered after any rebuild)
-    if (d_slot_head_) { HIP_OK(hipStreamSynchronize(st)); dfree(d_slot_head_, (size_t)heads_cap_ * 4); }
-    d_slot_head_ = (uint32_t*)dmalloc((size_t)table_cap_ * 4);
+    if (d_slot_head_) { HIP_OK(hipStreamSynchronize(st)); res_.dfree(d_slot_head_); }
+    d_slot_head_ = (uint32_t*)res_.dmalloc_on(stream_, (size_t)table_cap_ * 4);
     HIP_OK(hipMemsetAsync(d_slot_head_, 0xff, (size_t)table_cap_ * 4, st));
     heads_cap_ = table_cap_;
   }
@@ -1052,30 +996,30 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
     const uint32_t N = gin.n_autr + tot.mh;
     if (N + 1 > aud_key_cap_) {
       HIP_OK(hipStreamSynchronize(st));
-      for (void* p : {(void*)d_aud_key_, (void*)d_aud_key_sorted_}) dfree(p, (size_t)aud_key_cap_ * 8);
-      for (void* p : {(void*)d_aud_ord_, (void*)d_aud_ord_sorted_}) dfree(p, (size_t)aud_key_cap_ * 4);
+      for (void* p : {(void*)d_aud_key_, (void*)d_aud_key_sorted_}) res_.dfree(p);
+      for (void* p : {(void*)d_aud_ord_, (void*)d_aud_ord_sorted_}) res_.dfree(p);
       aud_key_cap_ = std::max<uint32_t>(2 * (N + 1), 1u << 14);
-      d_aud_key_ = (uint64_t*)dmalloc((size_t)aud_key_cap_ * 8);
-      d_aud_key_sorted_ = (uint64_t*)dmalloc((size_t)aud_key_cap_ * 8);
-      d_aud_ord_ = (uint32_t*)dmalloc((size_t)aud_key_cap_ * 4);
-      d_aud_ord_sorted_ = (uint32_t*)dmalloc((size_t)aud_key_cap_ * 4);
+      d_aud_key_ = (uint64_t*)res_.dmalloc_on(stream_, (size_t)aud_key_cap_ * 8);
+      d_aud_key_sorted_ = (uint64_t*)res_.dmalloc_on(stream_, (size_t)aud_key_cap_ * 8);
+      d_aud_ord_ = (uint32_t*)res_.dmalloc_on(stream_, (size_t)aud_key_cap_ * 4);
+      d_aud_ord_sorted_ = (uint32_t*)res_.dmalloc_on(stream_, (size_t)aud_key_cap_ * 4);
     }
     if (N > std::max<uint32_t>(cfg_.max_events, cfg_.arena_cap)) {  // the key sort's scratch
       const size_t need = apm_dj_tmp_bytes(N, out_cap_);
       if (need > tmp_bytes_) {
         HIP_OK(hipStreamSynchronize(st));
-        dfree(d_tmp_, tmp_bytes_);
+        res_.dfree(d_tmp_);
         tmp_bytes_ = need;
-        d_tmp_ = dmalloc(tmp_bytes_);
+        d_tmp_ = res_.dmalloc_on(stream_, tmp_bytes_);
         a.tmp = d_tmp_; a.tmp_bytes = tmp_bytes_;
       }
     }
     const uint32_t slots = tot.walk + gin.n_items;
     if (slots > aud_slots_cap_) {
       HIP_OK(hipStreamSynchronize(st));
-      dfree(d_aud_slots_, (size_t)aud_slots_cap_ * sizeof(AudItem));
+      res_.dfree(d_aud_slots_);
       aud_slots_cap_ = std::max<uint32_t>(2 * slots, 1u << 14);
-      d_aud_slots_ = (AudItem*)dmalloc((size_t)aud_slots_cap_ * sizeof(AudItem));
+      d_aud_slots_ = (AudItem*)res_.dmalloc_on(stream_, (size_t)aud_slots_cap_ * sizeof(AudItem));
     }
     a.n_mh = tot.mh; a.n_walk = tot.walk; a.n_files = (uint32_t)files_->size();
     a.aud = s.d_aud; a.gin = gin; a.gout = gout;
@@ -1140,18 +1084,10 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
   const uint32_t spec = std::min<uint32_t>(c.n_out, std::max<uint32_t>(2 * last_cands_, 1024));
   const size_t spec_tx = want_tx ? std::min<size_t>(txt_cap_, 2 * (size_t)last_tx_bytes_ + 65536) : 0;
   const size_t spec_db = want_db ? std::min<size_t>(txt_cap_, 2 * (size_t)last_db_bytes_ + 65536) : 0;
-  if (spec_tx + spec_db > h_txt_cap_) {
-    if (h_txt_) HIP_OK(hipHostFree(h_txt_));
-    h_txt_cap_ = (spec_tx + spec_db) * 2 + (4 << 20);
-    HIP_OK(hipHostMalloc((void**)&h_txt_, h_txt_cap_, hipHostMallocDefault));
-  }
+  res_.reserve(h_txt_, spec_tx + spec_db, (spec_tx + spec_db) * 2 + (4 << 20));
   // the read-back: one kernel writing the host-mapped buffers (a blit per array before: six
   // launches on the join lane's critical path)
-  auto mapped = [](void* h) {
-    void* d = nullptr;
-    HIP_OK(hipHostGetDevicePointer(&d, h, 0));
-    return d;
-  };
+  auto mapped = [](void* h) { return HipRes::device_alias(h); };
   auto write_and_copy = [&] {
     if (apm_dj_write(&f, st) != 0) throw std::runtime_error("device join: scan scratch too small");
     CopySegs cs;
@@ -1199,11 +1135,9 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
       HIP_OK(hipMemcpyAsync(h_unres_, d_unres_, (size_t)c3.n_unresolved * 8, hipMemcpyDeviceToHost, st));
     }
     if (tx_bytes > spec_tx || db_bytes > spec_db) {  // (both streams again, into a larger buffer)
-      if ((size_t)tx_bytes + db_bytes > h_txt_cap_) {
+      if ((size_t)tx_bytes + db_bytes > h_txt_.cap) {
         HIP_OK(hipStreamSynchronize(st));
-        if (h_txt_) HIP_OK(hipHostFree(h_txt_));
-        h_txt_cap_ = ((size_t)tx_bytes + db_bytes) * 2 + (4 << 20);
-        HIP_OK(hipHostMalloc((void**)&h_txt_, h_txt_cap_, hipHostMallocDefault));
+        res_.reserve(h_txt_, (size_t)tx_bytes + db_bytes, ((size_t)tx_bytes + db_bytes) * 2 + (4 << 20));
       }
       if (tx_bytes) HIP_OK(hipMemcpyAsync(h_txt_, d_txt_tx_, tx_bytes, hipMemcpyDeviceToHost, st));
       if (db_bytes) HIP_OK(hipMemcpyAsync(h_txt_ + tx_bytes, d_txt_db_, db_bytes, hipMemcpyDeviceToHost, st));
@@ -1263,7 +1197,7 @@ size_t DeviceJoin::trim(double now) {
     keys_live_ = *h_live_;
     live_pending_ = false;
   }
-  const size_t before = device_bytes_;
+  const size_t before = res_.device_bytes();
   const uint64_t tg = table_grows_, ag = arena_grows_;  // (a shrink is not a growth event)
   auto pow2_at_least = [](uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; };
   // key table: an exact live count first (same-size rebuild, expired keys dropped at `now`) --
@@ -1274,16 +1208,16 @@ size_t DeviceJoin::trim(double now) {
     if (want < table_cap_) rebuild_table(now, (uint32_t)want);  // reinserts into a fresh, smaller table
   }
   if (d_table_spare_) {  // (re-made on demand by the checkpoint's compaction)
-    dfree(d_table_spare_, (size_t)table_cap_ * sizeof(KeyState));
+    res_.dfree(d_table_spare_);
     d_table_spare_ = nullptr;
   }
   if (d_slot_head_) {  // sized by the table: re-made by the next batch
-    dfree(d_slot_head_, (size_t)heads_cap_ * 4);
+    res_.dfree(d_slot_head_);
     d_slot_head_ = nullptr;
     heads_cap_ = 0;
   }
   if (d_rb_scratch_) {  // sized by the table: re-made by the next in-place rebuild
-    dfree(d_rb_scratch_, rb_scratch_bytes_);
+    res_.dfree(d_rb_scratch_);
     d_rb_scratch_ = nullptr;
     rb_scratch_bytes_ = 0;
   }
@@ -1296,8 +1230,7 @@ size_t DeviceJoin::trim(double now) {
   }
   // tx / audit text staging of the write pass (re-made by the next batch that needs it)
   if (d_txt_tx_) {
-    HIP_OK(hipFree(d_txt_tx_));
-    device_bytes_ -= txt_cap_ * 2;
+    res_.dfree(d_txt_tx_);
     d_txt_tx_ = d_txt_db_ = nullptr;
     txt_cap_ = 0;
   }
@@ -1305,14 +1238,14 @@ size_t DeviceJoin::trim(double now) {
   table_grows_ = tg;
   arena_grows_ = ag;
   ++trims_;
-  return before > device_bytes_ ? before - device_bytes_ : 0;
+  return before > res_.device_bytes() ? before - res_.device_bytes() : 0;
 }
 
 std::vector<uint64_t> DeviceJoin::cache_stats(double now, bool sync) {
   if (!d_cstats_) {
-    d_cstats_ = (unsigned long long*)dmalloc(64);
-    HIP_OK(hipHostMalloc((void**)&h_cstats_, 64, hipHostMallocDefault));
-    HIP_OK(hipEventCreateWithFlags(&cstats_ev_, hipEventDisableTiming));
+    d_cstats_ = (unsigned long long*)res_.dmalloc_on(stream_, 64);
+    res_.pin(h_cstats_, 64);
+    cstats_ev_ = res_.new_event();
   }
   // A stat line (sync = false) reads the previous interval's counts when they are ready and
   // queues this interval's count on the join stream -- no host wait on the ingest path; the
@@ -1379,7 +1312,7 @@ void DeviceJoin::save_tables(BinWriter& w) {
   hipStream_t st = stream_;
   double sp = clock_ms();
   auto span = [&](const char* name) { const double t = clock_ms(); save_spans.push_back({name, {sp, t}}); sp = t; };
-  if (!h_ck_bounce_) HIP_OK(hipHostMalloc((void**)&h_ck_bounce_, kCkBounce, hipHostMallocDefault));
+  if (!h_ck_bounce_) res_.pin(h_ck_bounce_, kCkBounce);
   // live (non-empty) slots, selected on the device
   uint32_t n_live = 0;
   size_t live_off = 0;
@@ -1387,10 +1320,9 @@ void DeviceJoin::save_tables(BinWriter& w) {
     const size_t tb = apm_dj_live_tmp_bytes(table_cap_);
     // the spare table is the compaction target (kept: the in-place rebuild leaves no spare, and a
     // hipMalloc / hipFree of a table-sized buffer per checkpoint costs milliseconds and a device sync)
-    if (!d_table_spare_) d_table_spare_ = (KeyState*)dmalloc((size_t)table_cap_ * sizeof(KeyState));
+    if (!d_table_spare_) d_table_spare_ = (KeyState*)res_.dmalloc_on(stream_, (size_t)table_cap_ * sizeof(KeyState));
     KeyState* out = d_table_spare_;
-    void* tmp = nullptr;
-    HIP_OK(hipMalloc(&tmp, tb + 64));
+    void* tmp = res_.dmalloc_raw(tb + 64);
     uint32_t* d_n = (uint32_t*)((char*)tmp + tb);
     apm_dj_live_compact(d_table_, table_cap_, out, d_n, tmp, tb, st);
     HIP_OK(hipMemcpyAsync(&n_live, d_n, 4, hipMemcpyDeviceToHost, st));
@@ -1398,7 +1330,7 @@ void DeviceJoin::save_tables(BinWriter& w) {
     w.pod<uint64_t>(n_live);
     live_off = w.mem_pos();
     write_dev(w, out, (size_t)n_live * sizeof(KeyState), st, h_ck_bounce_, kCkBounce);
-    HIP_OK(hipFree(tmp));
+    res_.dfree(tmp);
   }
   span("ck.j.table");
   // needNumRecordCache regions + their arena entries (arena capacity first: the table's `need`
@@ -1435,8 +1367,7 @@ void DeviceJoin::save_tables(BinWriter& w) {
   std::vector<uint64_t> ekey(n_ents);
   {
     const size_t words = (size_t)n_live + 4 * n_ents;
-    uint32_t* d_f = nullptr;
-    if (words) HIP_OK(hipMalloc((void**)&d_f, words * 4));
+    uint32_t* d_f = words ? (uint32_t*)res_.dmalloc_raw(words * 4) : nullptr;
     apm_dj_gather_field((const char*)d_table_spare_ + offsetof(KeyState, pblk), sizeof(KeyState), n_live, 1, d_f, st);
     uint32_t* fk = d_f + n_live;
     uint32_t* fi = fk + 2 * n_ents;
@@ -1456,7 +1387,7 @@ void DeviceJoin::save_tables(BinWriter& w) {
       std::vector<uint32_t> h(words);
       HIP_OK(hipMemcpyAsync(h.data(), d_f, words * 4, hipMemcpyDeviceToHost, st));
       HIP_OK(hipStreamSynchronize(st));
-      HIP_OK(hipFree(d_f));
+      res_.dfree(d_f);
       std::memcpy(pblk.data(), h.data(), (size_t)n_live * 4);
       std::memcpy(ekey.data(), h.data() + n_live, n_ents * 8);
       std::memcpy(iblk.data(), h.data() + n_live + 2 * n_ents, n_ents * 4);
@@ -1485,10 +1416,10 @@ void DeviceJoin::save_tables(BinWriter& w) {
     size_t cap = 0;
     while (!cur.empty()) {
       if (cur.size() > cap) {
-        if (d_idx) { HIP_OK(hipFree(d_idx)); HIP_OK(hipFree(d_out)); }
+        if (d_idx) { res_.dfree(d_idx); res_.dfree(d_out); }
         cap = cur.size() * 2;
-        HIP_OK(hipMalloc((void**)&d_idx, cap * 4));
-        HIP_OK(hipMalloc((void**)&d_out, cap * CHAIN_BLK));
+        d_idx = (int32_t*)res_.dmalloc_raw(cap * 4);
+        d_out = (uint8_t*)res_.dmalloc_raw(cap * CHAIN_BLK);
       }
       HIP_OK(hipMemcpyAsync(d_idx, cur.data(), cur.size() * 4, hipMemcpyHostToDevice, st));
       apm_dj_gather_blocks(d_pool_, d_idx, (uint32_t)cur.size(), d_out, st);
@@ -1508,7 +1439,7 @@ void DeviceJoin::save_tables(BinWriter& w) {
       cur.swap(nxt);
       parent.swap(nparent);
     }
-    if (d_idx) { HIP_OK(hipFree(d_idx)); HIP_OK(hipFree(d_out)); }
+    if (d_idx) { res_.dfree(d_idx); res_.dfree(d_out); }
   }
   span("ck.j.chains");
   w.vec(blocks);
@@ -1587,25 +1518,24 @@ void DeviceJoin::load(BinReader& rd) {
     while (live.size() * 2 > cap) cap *= 2;  // the saving process may have grown its table
     HIP_OK(hipStreamSynchronize(st));
     if (cap != table_cap_) {
-      dfree(d_table_, (size_t)table_cap_ * sizeof(KeyState));
-      if (d_table_spare_) dfree(d_table_spare_, (size_t)table_cap_ * sizeof(KeyState));
+      res_.dfree(d_table_);
+      if (d_table_spare_) res_.dfree(d_table_spare_);
       d_table_spare_ = nullptr;
       table_cap_ = (uint32_t)cap;
-      d_table_ = (KeyState*)dmalloc((size_t)table_cap_ * sizeof(KeyState));
+      d_table_ = (KeyState*)res_.dmalloc_on(stream_, (size_t)table_cap_ * sizeof(KeyState));
       ensure_tmp();
     } else {
       HIP_OK(hipMemsetAsync(d_table_, 0, (size_t)table_cap_ * sizeof(KeyState), st));
     }
     if (!live.empty()) {
-      KeyState* tmp = nullptr;
-      HIP_OK(hipMalloc((void**)&tmp, live.size() * sizeof(KeyState)));
+      KeyState* tmp = (KeyState*)res_.dmalloc_raw(live.size() * sizeof(KeyState));
       HIP_OK(hipMemcpy(tmp, live.data(), live.size() * sizeof(KeyState), hipMemcpyHostToDevice));
       HIP_OK(hipMemsetAsync(d_live_, 0, 8, st));
       // every saved slot is reinserted (now = -inf keeps them all, chains included)
       apm_dj_rebuild(tmp, (uint32_t)live.size(), d_table_, table_cap_ - 1, d_arena_, cfg_.arena_cap, -__builtin_inf(),
                      d_counts_, d_live_, d_pool_, d_pool_ring_, pool_n_ - 1, st);
       HIP_OK(hipStreamSynchronize(st));
-      HIP_OK(hipFree(tmp));
+      res_.dfree(tmp);
     }
     keys_live_ = live.size();
     keys_since_rebuild_ = 0;
@@ -1616,19 +1546,19 @@ void DeviceJoin::load(BinReader& rd) {
     const uint32_t saved_cap = rd.pod<uint32_t>();
     if (saved_cap != cfg_.arena_cap) {  // the `need` links are slots of the saver's arena size
       HIP_OK(hipStreamSynchronize(st));
-      dfree(d_arena_, (size_t)cfg_.arena_cap * sizeof(NeedEnt));
+      res_.dfree(d_arena_);
       cfg_.arena_cap = saved_cap;
-      d_arena_ = (NeedEnt*)dmalloc((size_t)cfg_.arena_cap * sizeof(NeedEnt));
-      for (void* p : {(void*)d_exp_key_, (void*)d_exp_key_sorted_}) dfree(p, ((size_t)exp_cap_ + 1) * 8);
+      d_arena_ = (NeedEnt*)res_.dmalloc_on(stream_, (size_t)cfg_.arena_cap * sizeof(NeedEnt));
+      for (void* p : {(void*)d_exp_key_, (void*)d_exp_key_sorted_}) res_.dfree(p);
       for (void* p : {(void*)d_exp_idx_, (void*)d_exp_idx_sorted_, (void*)d_exp_cnt_, (void*)d_exp_pos_})
-        dfree(p, ((size_t)exp_cap_ + 1) * 4);
+        res_.dfree(p);
       exp_cap_ = saved_cap;
-      d_exp_key_ = (uint64_t*)dmalloc(((size_t)exp_cap_ + 1) * 8);
-      d_exp_key_sorted_ = (uint64_t*)dmalloc(((size_t)exp_cap_ + 1) * 8);
-      d_exp_idx_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-      d_exp_idx_sorted_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-      d_exp_cnt_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
-      d_exp_pos_ = (uint32_t*)dmalloc(((size_t)exp_cap_ + 1) * 4);
+      d_exp_key_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 8);
+      d_exp_key_sorted_ = (uint64_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 8);
+      d_exp_idx_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+      d_exp_idx_sorted_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+      d_exp_cnt_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
+      d_exp_pos_ = (uint32_t*)res_.dmalloc_on(stream_, ((size_t)exp_cap_ + 1) * 4);
       ensure_tmp();
     }
   }
@@ -1668,11 +1598,11 @@ void DeviceJoin::load(BinReader& rd) {
     uint64_t n = pool_n_;
     while (n < 2 * blocks.size() + (1u << 16)) n *= 2;
     if (n != pool_n_) {
-      dfree(d_pool_, (size_t)pool_n_ * CHAIN_BLK);
-      dfree(d_pool_ring_, (size_t)pool_n_ * 4);
+      res_.dfree(d_pool_);
+      res_.dfree(d_pool_ring_);
       pool_n_ = (uint32_t)n;
-      d_pool_ = (uint8_t*)dmalloc((size_t)pool_n_ * CHAIN_BLK);
-      d_pool_ring_ = (uint32_t*)dmalloc((size_t)pool_n_ * 4);
+      d_pool_ = (uint8_t*)res_.dmalloc_on(stream_, (size_t)pool_n_ * CHAIN_BLK);
+      d_pool_ring_ = (uint32_t*)res_.dmalloc_on(stream_, (size_t)pool_n_ * 4);
       HIP_OK(hipStreamSynchronize(st));  // (the zeroing before the null-stream copy, as above)
     }
     if (!blocks.empty())
@@ -1715,8 +1645,7 @@ void DeviceJoin::load(BinReader& rd) {
     if (!ri.empty()) HIP_OK(hipMemcpy(d_rawtab_, h_rawtab_, ri.size() * sizeof(RawSvc), hipMemcpyHostToDevice));
     if (names_.size() > names_cap_) {
       names_cap_ = std::max<size_t>(names_.size() * 2, 1 << 20);
-      HIP_OK(hipMalloc((void**)&d_names_, names_cap_));
-      device_bytes_ += names_cap_;
+      d_names_ = (char*)res_.dmalloc_raw(names_cap_);
     }
     if (!names_.empty()) HIP_OK(hipMemcpy(d_names_, names_.data(), names_.size(), hipMemcpyHostToDevice));
     names_uploaded_ = names_.size();

@@ -27,6 +27,7 @@
 
 #include "../apm_types.h"
 #include "../kernels/devjoin_api.h"
+#include "hipres.h"
 #include "join.h"
 
 namespace apm {
@@ -72,8 +73,8 @@ class DeviceJoin {
   // swap_stage(k) hands it to slot k (whose previous buffer becomes the staging buffer).
   uint8_t* d_stage() {
     if (!d_stage_bytes_) {
-      d_stage_bytes_ = (uint8_t*)dmalloc(cfg_.max_batch_bytes + 256);
-      // dmalloc's zero fill is queued on the join stream: the staged copy (another stream) must
+      d_stage_bytes_ = (uint8_t*)res_.dmalloc_on(stream_, cfg_.max_batch_bytes + 256);
+      // dmalloc_on's zero fill is queued on the join stream: the staged copy (another stream) must
       // not land before it (seen: a staged batch parsed as zeros, test_two_ahead_input_staging_*)
       HIP_OK(hipStreamSynchronize(stream_));
     }
@@ -139,7 +140,7 @@ class DeviceJoin {
   std::vector<std::pair<const char*, std::pair<double, double>>> spans;  // finer trace spans of run()
   std::vector<std::pair<const char*, std::pair<double, double>>> save_spans;  // spans of the last save()
   const JoinCounts& last_counts() const { return *h_counts_; }
-  size_t device_bytes() const { return device_bytes_; }
+  size_t device_bytes() const { return res_.device_bytes(); }
   // requestGC (join stream idle, between batches): the grow-only key table and need arena go
   // back to the smallest power of two (not below their configured size) that keeps their live
   // entries at <= 1/4 load, the spare table and text staging are released.  Returns bytes freed.
@@ -178,7 +179,6 @@ class DeviceJoin {
 
   struct RawInfo { int32_t server; int32_t norm_id; uint64_t svc; };
 
-  void* dmalloc(size_t bytes);
   // One file's share of the host pre-pass (field re-derivation of the lines of one file)
   struct PrepassTask {
     int32_t file = -1;
@@ -216,7 +216,6 @@ class DeviceJoin {
   void grow_pool(uint64_t need_free);
   uint64_t pool_avail(bool exact);
   void ensure_tmp();
-  void dfree(void* p, size_t bytes);
 
   DevJoinConfig cfg_;
   uint32_t init_table_cap_ = 0, init_arena_cap_ = 0;  // configured sizes: trim never goes below
@@ -224,9 +223,8 @@ class DeviceJoin {
   const std::vector<FileInfo>* files_;
   const std::vector<std::string>* servers_;
   hipStream_t stream_ = nullptr;  // join stream
-  size_t device_bytes_ = 0;
+  HipRes res_;  // every device / pinned block, event and the join stream (zero fills: dmalloc_on(stream_))
   uint8_t* d_stage_bytes_ = nullptr;  // two-ahead H2D target (d_stage / swap_stage)
-  std::vector<void*> allocs_;
 
   // host pre-pass output of the current batch
   std::vector<HostOp> hops_;
@@ -234,12 +232,8 @@ class DeviceJoin {
   std::vector<HostOp> hops_ahead_;  // prepass_ahead's result for slot ahead_k_
   std::string hbuf_ahead_;
   int ahead_k_ = -1;
-  HostOp* h_hops_ = nullptr;     // pinned
-  uint8_t* h_hbuf_ = nullptr;    // pinned
-  const void* hd_hops_ = nullptr;  // device views (apm_copy reads them over the host link)
-  const void* hd_hbuf_ = nullptr;
-  const void* hd_exp_ = nullptr;
-  size_t h_hops_cap_ = 0, h_hbuf_cap_ = 0;
+  PinnedBuf<HostOp> h_hops_;     // pinned, with device views (.d: apm_copy reads them over the host link)
+  PinnedBuf<uint8_t> h_hbuf_;
   HostOp* d_hops_ = nullptr;
   uint8_t* d_hbuf_ = nullptr;
   size_t d_hops_cap_ = 0, d_hbuf_cap_ = 0;
@@ -288,7 +282,7 @@ class DeviceJoin {
   std::deque<Region> regions_;   // live need regions, creation order
   uint64_t* d_exp_lo_ = nullptr;
   uint64_t* d_exp_hi_ = nullptr;
-  uint64_t* h_exp_ = nullptr;    // pinned [2][64]
+  Mapped<uint64_t> h_exp_;       // pinned [2][64]
   SoapState* d_soap_ = nullptr;
   // audit trail (K5): carry generations (batch k reads aud_gen_[aud_cur_], writes the other),
   // per-event fields, key sort, walk tables
@@ -341,8 +335,7 @@ class DeviceJoin {
   char* d_txt_tx_ = nullptr;
   char* d_txt_db_ = nullptr;
   size_t txt_cap_ = 0;
-  char* h_txt_ = nullptr;
-  size_t h_txt_cap_ = 0;
+  PinnedBuf<char> h_txt_;
   // copied back before their sizes are known (no sync between the plan and the write): the
   // previous batch's sizes x 2; a larger batch copies the rest after sync C
   uint32_t last_tx_bytes_ = 0, last_db_bytes_ = 0, last_cands_ = 0;

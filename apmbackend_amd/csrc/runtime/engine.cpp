@@ -208,40 +208,6 @@ void ThreadPool::run(int n_tasks, const std::function<void(int)>& fn, const std:
 }
 
 // ----------------------------------------------------------------------------- setup
-void* Engine::dmalloc(size_t bytes) {
-  void* p = nullptr;
-  bytes = (bytes + 255) & ~(size_t)255;
-  HIP_OK(hipMalloc(&p, bytes));
-  HIP_OK(hipMemset(p, 0, bytes));
-  // hipMemset runs on the null stream, which does not order against the engine's non-blocking
-  // streams: without this wait, a buffer regrown mid-run could be zeroed *after* the first copy
-  // into it on stream_ (seen: K12 names table read back as zeros after a regrow).  The null
-  // stream only, not the device: a device-wide sync would also wait for the collective stream
-  // (a lock-step all-reduce waiting for a peer rank).
-  HIP_OK(hipStreamSynchronize(nullptr));
-  std::lock_guard<std::mutex> g(alloc_mu_);  // the stats thread and the rollover lane allocate
-  allocations_.push_back(p);
-  alloc_bytes_[p] = bytes;
-  device_bytes_ += bytes;
-  return p;
-}
-
-// Optional scratch (checkpoint packing): nullptr instead of a throw when HBM is short, no zeroing
-// and no device-wide sync; counted in device_bytes_ and freed by dfree / the destructor.
-void* Engine::dmalloc_try(size_t bytes) {
-  void* p = nullptr;
-  bytes = (bytes + 255) & ~(size_t)255;
-  if (hipMalloc(&p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  std::lock_guard<std::mutex> g(alloc_mu_);
-  allocations_.push_back(p);
-  alloc_bytes_[p] = bytes;
-  device_bytes_ += bytes;
-  return p;
-}
-
 Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   check_window(cfg_.window, cfg_.buffer, cfg_.interval_len);
   if (cfg_.n_lags < 1 || cfg_.n_lags > MAX_LAGS)
@@ -290,9 +256,10 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       HIP_OK(hipStreamCreateWithPriority(&parse_stream_, hipStreamNonBlocking, pp ? hi : 0));
       HIP_OK(hipStreamCreateWithFlags(&out_stream_, hipStreamNonBlocking));
     }
+    for (hipStream_t st : {stream_, parse_stream_, out_stream_}) res_.adopt(st);
   }
-  HIP_OK(hipEventCreateWithFlags(&ev_a_, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&ev_b_, hipEventDisableTiming));
+  ev_a_ = res_.new_event();
+  ev_b_ = res_.new_event();
   const int32_t S = cfg_.max_series;
   // parse
   if (cfg_.device_join) {
@@ -311,165 +278,156 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     dc.tz = cfg_.tz;
     dc.device = cfg_.device;
     dj_.reset(new DeviceJoin(dc, &dict_, &files_, &servers_));  // (its bytes: device_bytes())
-    d_ring_min_ = (unsigned long long*)dmalloc(64);
+    d_ring_min_ = (unsigned long long*)res_.dmalloc(64);
     HIP_OK(hipMemset(d_ring_min_, 0xff, 8));  // (the export after each min pass restores it)
-    HIP_OK(hipHostMalloc((void**)&h_ring_min_, 64, hipHostMallocDefault));
-    HIP_OK(hipHostGetDevicePointer((void**)&hd_ring_min_, h_ring_min_, 0));
+    res_.pin(h_ring_min_, 64);
     *h_ring_min_ = ~0ULL;
-    d_rel_n_ = (int64_t*)dmalloc(64);
-    HIP_OK(hipHostMalloc((void**)&h_rel_n_, 64, hipHostMallocDefault));
-    HIP_OK(hipHostGetDevicePointer((void**)&hd_rel_n_, h_rel_n_, 0));
-    d_rel_lens_ = (uint32_t*)dmalloc(((size_t)cfg_.pool_cap + 2) * 4);
-    d_rel_offs_ = (uint32_t*)dmalloc(((size_t)cfg_.pool_cap + 2) * 4);
-    d_rel_fb_ = (uint32_t*)dmalloc(4);
+    d_rel_n_ = (int64_t*)res_.dmalloc(64);
+    res_.pin(h_rel_n_, 64);
+    d_rel_lens_ = (uint32_t*)res_.dmalloc(((size_t)cfg_.pool_cap + 2) * 4);
+    d_rel_offs_ = (uint32_t*)res_.dmalloc(((size_t)cfg_.pool_cap + 2) * 4);
+    d_rel_fb_ = (uint32_t*)res_.dmalloc(4);
     HIP_OK(hipMemset(d_rel_fb_, 0, 4));
-    HIP_OK(hipHostMalloc((void**)&h_rel_total_, 64, hipHostMallocDefault));
-    HIP_OK(hipHostGetDevicePointer((void**)&hd_rel_total_, h_rel_total_, 0));
-    d_unmapped_ = (unsigned long long*)dmalloc(64);
-    d_unseen_idx_ = (int32_t*)dmalloc((size_t)cfg_.max_series * 4);
-    d_unseen_flag_ = (uint8_t*)dmalloc((size_t)cfg_.max_series);
-    HIP_OK(hipHostMalloc((void**)&h_unseen_flag_, (size_t)cfg_.max_series, hipHostMallocDefault));
+    res_.pin(h_rel_total_, 64);
+    d_unmapped_ = (unsigned long long*)res_.dmalloc(64);
+    d_unseen_idx_ = (int32_t*)res_.dmalloc((size_t)cfg_.max_series * 4);
+    d_unseen_flag_ = (uint8_t*)res_.dmalloc((size_t)cfg_.max_series);
+    res_.pin(h_unseen_flag_, (size_t)cfg_.max_series);
   } else {
-    d_bytes_ = (uint8_t*)dmalloc(cfg_.max_batch_bytes + 256);
+    d_bytes_ = (uint8_t*)res_.dmalloc(cfg_.max_batch_bytes + 256);
   }
   for (int k = 0; k < 2; ++k) {
     ParseSlot& ps = pslot_[k];
-    HIP_OK(hipHostMalloc((void**)&ps.h_bytes, cfg_.max_batch_bytes + 256, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&ps.h_chunk_begin, (cfg_.max_chunks + 2) * 4, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&ps.h_chunk_kind, cfg_.max_chunks + 2, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&ps.h_chunk_file, (cfg_.max_chunks + 2) * 4, hipHostMallocDefault));
-    d_chunk_begin_[k] = (uint32_t*)dmalloc((cfg_.max_chunks + 2) * 4);
-    d_chunk_kind_[k] = (uint8_t*)dmalloc(cfg_.max_chunks + 2);
-    d_chunk_file_[k] = (uint32_t*)dmalloc((cfg_.max_chunks + 2) * 4);
-    HIP_OK(hipHostMalloc((void**)&ps.h_counts, 16, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&ps.h_watermark, 8, hipHostMallocDefault));
+    res_.pin(ps.h_bytes, cfg_.max_batch_bytes + 256);
+    res_.pin(ps.h_chunk_begin, (cfg_.max_chunks + 2) * 4);
+    res_.pin(ps.h_chunk_kind, cfg_.max_chunks + 2);
+    res_.pin(ps.h_chunk_file, (cfg_.max_chunks + 2) * 4);
+    d_chunk_begin_[k] = (uint32_t*)res_.dmalloc((cfg_.max_chunks + 2) * 4);
+    d_chunk_kind_[k] = (uint8_t*)res_.dmalloc(cfg_.max_chunks + 2);
+    d_chunk_file_[k] = (uint32_t*)res_.dmalloc((cfg_.max_chunks + 2) * 4);
+    res_.pin(ps.h_counts, 16);
+    res_.pin(ps.h_watermark, 8);
     if (dev()) continue;  // the device join keeps events on the GPU
-    HIP_OK(hipHostMalloc((void**)&ps.h_events, (size_t)cfg_.max_lines * sizeof(Event), hipHostMallocDefault));
+    res_.pin(ps.h_events, (size_t)cfg_.max_lines * sizeof(Event));
     // (Writing the events straight into this pinned slot from the compaction kernel was measured:
     // -0.3 ms parse, +0.3 ms host join reading lines the GPU wrote over PCIe.  The DMA copy stays.)
   }
-  d_parse_ws_ = dmalloc(apm_parse_workspace_bytes(cfg_.max_batch_bytes, cfg_.max_lines, cfg_.max_chunks));
-  if (!dev()) d_events_ = (Event*)dmalloc((size_t)cfg_.max_lines * sizeof(Event));
-  d_counts_ = (uint32_t*)dmalloc(16);
-  d_watermark_ = (unsigned long long*)dmalloc(8);
-  d_file_open_ = (uint8_t*)dmalloc(1 << 16);
+  d_parse_ws_ = res_.dmalloc(apm_parse_workspace_bytes(cfg_.max_batch_bytes, cfg_.max_lines, cfg_.max_chunks));
+  if (!dev()) d_events_ = (Event*)res_.dmalloc((size_t)cfg_.max_lines * sizeof(Event));
+  d_counts_ = (uint32_t*)res_.dmalloc(16);
+  d_watermark_ = (unsigned long long*)res_.dmalloc(8);
+  d_file_open_ = (uint8_t*)res_.dmalloc(1 << 16);
   // stats
   init_spill_cap_ = cfg_.spill_cap;
   alloc_ring(std::max(cfg_.nslot, ring_slots_for(cfg_.window, cfg_.buffer)));
-  for (auto& m : spill_mark_) HIP_OK(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
+  for (auto& m : spill_mark_) m.ev = res_.new_event();
   metrics_.spill_capacity = cfg_.spill_cap;
-  d_spill_drop_ = (unsigned long long*)dmalloc(64);
-  d_active_ = (uint8_t*)dmalloc(S);
-  d_win_ = (WinStat*)dmalloc((size_t)S * sizeof(WinStat));
-  d_big_list_ = (int32_t*)dmalloc((size_t)S * 4);
+  d_spill_drop_ = (unsigned long long*)res_.dmalloc(64);
+  d_active_ = (uint8_t*)res_.dmalloc(S);
+  d_win_ = (WinStat*)res_.dmalloc((size_t)S * sizeof(WinStat));
+  d_big_list_ = (int32_t*)res_.dmalloc((size_t)S * 4);
   // per-rollover counters in one block, cleared by one memset: [0] big, [1] nan, [2] alert candidates
-  d_big_n_ = (int32_t*)dmalloc(64);
-  d_nan_until_ = (int32_t*)dmalloc((size_t)S * 4);
+  d_big_n_ = (int32_t*)res_.dmalloc(64);
+  d_nan_until_ = (int32_t*)res_.dmalloc((size_t)S * 4);
   HIP_OK(hipMemset(d_nan_until_, 0x80, (size_t)S * 4));  // 0x80808080: far below any bucket
   ord_cap_ = std::max<int64_t>(cfg_.max_tx_per_batch, cfg_.max_lines);
-  d_ord_list_ = (int32_t*)dmalloc((size_t)ord_cap_ * 4);
-  d_ord_n_ = (int32_t*)dmalloc(8);  // [0] ord_n, [1] ordered-append blocks done
-  d_nan_list_ = (int32_t*)dmalloc((size_t)S * 4);
+  d_ord_list_ = (int32_t*)res_.dmalloc((size_t)ord_cap_ * 4);
+  d_ord_n_ = (int32_t*)res_.dmalloc(8);  // [0] ord_n, [1] ordered-append blocks done
+  d_nan_list_ = (int32_t*)res_.dmalloc((size_t)S * 4);
   d_nan_n_ = d_big_n_ + 1;
-  d_js_scratch_ = (int32_t*)dmalloc((size_t)JS_BLOCKS * kJsCap * 4);
+  d_js_scratch_ = (int32_t*)res_.dmalloc((size_t)JS_BLOCKS * kJsCap * 4);
   // z-score
   for (int l = 0; l < cfg_.n_lags; ++l) {
     LagState& L = lag_[l];
-    L.ring = dmalloc((size_t)NSTAT * cfg_.lags[l] * S * cfg_.ring_bytes);
-    L.len = (int32_t*)dmalloc((size_t)S * 4);
-    L.sum = (double*)dmalloc((size_t)NSTAT * S * 8);
-    L.comp = (double*)dmalloc((size_t)NSTAT * S * 8);
-    L.sumsq = (double*)dmalloc((size_t)NSTAT * S * 8);
-    L.sqcomp = (double*)dmalloc((size_t)NSTAT * S * 8);
-    L.cnt = (int32_t*)dmalloc((size_t)NSTAT * S * 4);
-    L.thr = (double*)dmalloc((size_t)S * 8);
-    L.infl = (double*)dmalloc((size_t)S * 8);
-    L.out = (ZOut*)dmalloc((size_t)S * sizeof(ZOut));
-    L.counter = (int32_t*)dmalloc((size_t)S * 4);
+    L.ring = res_.dmalloc((size_t)NSTAT * cfg_.lags[l] * S * cfg_.ring_bytes);
+    L.len = (int32_t*)res_.dmalloc((size_t)S * 4);
+    L.sum = (double*)res_.dmalloc((size_t)NSTAT * S * 8);
+    L.comp = (double*)res_.dmalloc((size_t)NSTAT * S * 8);
+    L.sumsq = (double*)res_.dmalloc((size_t)NSTAT * S * 8);
+    L.sqcomp = (double*)res_.dmalloc((size_t)NSTAT * S * 8);
+    L.cnt = (int32_t*)res_.dmalloc((size_t)NSTAT * S * 4);
+    L.thr = (double*)res_.dmalloc((size_t)S * 8);
+    L.infl = (double*)res_.dmalloc((size_t)S * 8);
+    L.out = (ZOut*)res_.dmalloc((size_t)S * sizeof(ZOut));
+    L.counter = (int32_t*)res_.dmalloc((size_t)S * 4);
   }
   // rolling-mode resync scratch: one contiguous range of ceil(S / K) series per rollover
   if (cfg_.resync_k > 0 && !cfg_.exact_mean) {
     rs_range_ = (S + cfg_.resync_k - 1) / cfg_.resync_k;
-    rs_part_ = (double*)dmalloc((size_t)NSTAT * RS_PARTS * rs_range_ * 4 * 8);
-    rs_cnt_ = (int32_t*)dmalloc((size_t)NSTAT * RS_PARTS * rs_range_ * 4);
+    rs_part_ = (double*)res_.dmalloc((size_t)NSTAT * RS_PARTS * rs_range_ * 4 * 8);
+    rs_cnt_ = (int32_t*)res_.dmalloc((size_t)NSTAT * RS_PARTS * rs_range_ * 4);
   }
   {
     const double* sp[MAX_LAGS] = {};
     const double* cp[MAX_LAGS] = {};
     const int32_t* np[MAX_LAGS] = {};
     for (int l = 0; l < cfg_.n_lags; ++l) { sp[l] = lag_[l].sum; cp[l] = lag_[l].comp; np[l] = lag_[l].cnt; }
-    d_lag_sum_ptrs_ = dmalloc(sizeof(sp));
-    d_lag_comp_ptrs_ = dmalloc(sizeof(cp));
-    d_lag_cnt_ptrs_ = dmalloc(sizeof(np));
+    d_lag_sum_ptrs_ = res_.dmalloc(sizeof(sp));
+    d_lag_comp_ptrs_ = res_.dmalloc(sizeof(cp));
+    d_lag_cnt_ptrs_ = res_.dmalloc(sizeof(np));
     HIP_OK(hipMemcpy(d_lag_sum_ptrs_, sp, sizeof(sp), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_lag_comp_ptrs_, cp, sizeof(cp), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_lag_cnt_ptrs_, np, sizeof(np), hipMemcpyHostToDevice));
-    d_series_service_ = (int32_t*)dmalloc((size_t)S * 4);
+    d_series_service_ = (int32_t*)res_.dmalloc((size_t)S * 4);
   }
-  d_hard_max_ = (double*)dmalloc((size_t)S * 8);
-  d_suppressed_ = (uint8_t*)dmalloc(S);
-  d_cool_t_ = (double*)dmalloc((size_t)S * 8);
+  d_hard_max_ = (double*)res_.dmalloc((size_t)S * 8);
+  d_suppressed_ = (uint8_t*)res_.dmalloc(S);
+  d_cool_t_ = (double*)res_.dmalloc((size_t)S * 8);
   HIP_OK(hipMemsetAsync(d_cool_t_, 0xff, (size_t)S * 8, stream_));  // NaN: no cooldown
-  d_emit_key_ = (uint64_t*)dmalloc((size_t)S * 8);
+  d_emit_key_ = (uint64_t*)res_.dmalloc((size_t)S * 8);
   // K12 formatter
-  d_ser_names_ = (int32_t*)dmalloc((size_t)S * 16);
-  d_perm_ = (int32_t*)dmalloc((size_t)S * 4);
-  d_series_server_ = (int32_t*)dmalloc((size_t)S * 4);
+  d_ser_names_ = (int32_t*)res_.dmalloc((size_t)S * 16);
+  d_perm_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+  d_series_server_ = (int32_t*)res_.dmalloc((size_t)S * 4);
   // st lengths/offsets [S + 1], then fs per (series, LAG) line [S * MAX_LAGS + 1]
-  d_fmt_len_ = (uint32_t*)dmalloc(((size_t)(S + 1) + (size_t)S * MAX_LAGS + 1) * 4);
-  d_fmt_off_ = (uint32_t*)dmalloc(((size_t)(S + 1) + (size_t)S * MAX_LAGS + 1) * 4);
-  d_fmt_fallback_ = (int32_t*)dmalloc(4);
+  d_fmt_len_ = (uint32_t*)res_.dmalloc(((size_t)(S + 1) + (size_t)S * MAX_LAGS + 1) * 4);
+  d_fmt_off_ = (uint32_t*)res_.dmalloc(((size_t)(S + 1) + (size_t)S * MAX_LAGS + 1) * 4);
+  d_fmt_fallback_ = (int32_t*)res_.dmalloc(4);
   fmt_tmp_bytes_ = apm_format_tmp_bytes((int32_t)((size_t)S * MAX_LAGS + 1));
-  d_fmt_tmp_ = dmalloc(fmt_tmp_bytes_);
-  HIP_OK(hipHostMalloc((void**)&h_fmt_meta_, 64, hipHostMallocDefault));
-  HIP_OK(hipHostGetDevicePointer((void**)&hd_fmt_meta_, h_fmt_meta_, 0));
+  d_fmt_tmp_ = res_.dmalloc(fmt_tmp_bytes_);
+  res_.pin(h_fmt_meta_, 64);
   if (want(OUT_LH)) {  // K15
-    d_hist_len_ = (uint32_t*)dmalloc((size_t)(S + 1) * 4);
-    d_hist_off_ = (uint32_t*)dmalloc((size_t)(S + 1) * 4);
-    d_hist_big_ = (int32_t*)dmalloc((size_t)(S + 1) * 4);
+    d_hist_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_hist_off_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_hist_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
     hist_tmp_bytes_ = apm_hist_tmp_bytes(S);
-    d_hist_tmp_ = dmalloc(hist_tmp_bytes_);
-    HIP_OK(hipHostMalloc((void**)&h_hist_total_, 64, hipHostMallocDefault));
-    HIP_OK(hipHostGetDevicePointer((void**)&hd_hist_total_, h_hist_total_, 0));
-    for (int k = 0; k < 2; ++k) HIP_OK(hipEventCreateWithFlags(&ev_hist_[k], hipEventDisableTiming));
+    d_hist_tmp_ = res_.dmalloc(hist_tmp_bytes_);
+    res_.pin(h_hist_total_, 64);
+    for (int k = 0; k < 2; ++k) ev_hist_[k] = res_.new_event();
   }
   {
     const char* f = std::getenv("APM_TXCOPY_FORCE_FALLBACK");
     txcopy_force_fb_ = f && f[0] == '1';
   }
   // alerts
-  d_alerts_ = (AlertRec*)dmalloc((size_t)cfg_.max_alerts * sizeof(AlertRec));
+  d_alerts_ = (AlertRec*)res_.dmalloc((size_t)cfg_.max_alerts * sizeof(AlertRec));
   d_n_alerts_ = d_big_n_ + 2;
-  HIP_OK(hipHostMalloc((void**)&h_alerts_, (size_t)cfg_.max_alerts * sizeof(AlertRec), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&h_alert_win_, (size_t)cfg_.max_alerts * sizeof(WinStat), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&h_alert_z_, (size_t)cfg_.max_alerts * sizeof(ZOut), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&h_n_alerts_, 16, hipHostMallocDefault));
-  HIP_OK(hipHostGetDevicePointer((void**)&hd_alerts_, h_alerts_, 0));
-  HIP_OK(hipHostGetDevicePointer((void**)&hd_alert_win_, h_alert_win_, 0));
-  HIP_OK(hipHostGetDevicePointer((void**)&hd_alert_z_, h_alert_z_, 0));
-  HIP_OK(hipHostGetDevicePointer((void**)&hd_n_alerts_, h_n_alerts_, 0));
-  HIP_OK(hipEventCreateWithFlags(&ev_alerts_, hipEventDisableTiming));
-  HIP_OK(hipEventCreateWithFlags(&ev_release_, hipEventDisableTiming));
+  res_.pin(h_alerts_, (size_t)cfg_.max_alerts * sizeof(AlertRec));
+  res_.pin(h_alert_win_, (size_t)cfg_.max_alerts * sizeof(WinStat));
+  res_.pin(h_alert_z_, (size_t)cfg_.max_alerts * sizeof(ZOut));
+  res_.pin(h_n_alerts_, 16);
+  ev_alerts_ = res_.new_event();
+  ev_release_ = res_.new_event();
   // tx + release
-  d_tx_ = (TxRec*)dmalloc((size_t)cfg_.max_tx_per_batch * sizeof(TxRec));
-  HIP_OK(hipHostMalloc((void**)&h_tx_, (size_t)cfg_.max_tx_per_batch * sizeof(TxRec), hipHostMallocDefault));
-  d_gid_ = (int64_t*)dmalloc((size_t)cfg_.max_tx_per_batch * 8);
-  HIP_OK(hipHostMalloc((void**)&h_gid_, (size_t)cfg_.max_tx_per_batch * 8, hipHostMallocDefault));
-  d_tail_end_ = (int64_t*)dmalloc((size_t)cfg_.pool_cap * 8);
-  d_tail_gid_ = (int64_t*)dmalloc((size_t)cfg_.pool_cap * 8);
-  d_sort_end_ = (int64_t*)dmalloc((size_t)cfg_.pool_cap * 8);
-  d_sort_gid_ = (int64_t*)dmalloc((size_t)cfg_.pool_cap * 8);
+  d_tx_ = (TxRec*)res_.dmalloc((size_t)cfg_.max_tx_per_batch * sizeof(TxRec));
+  res_.pin(h_tx_, (size_t)cfg_.max_tx_per_batch * sizeof(TxRec));
+  d_gid_ = (int64_t*)res_.dmalloc((size_t)cfg_.max_tx_per_batch * 8);
+  res_.pin(h_gid_, (size_t)cfg_.max_tx_per_batch * 8);
+  d_tail_end_ = (int64_t*)res_.dmalloc((size_t)cfg_.pool_cap * 8);
+  d_tail_gid_ = (int64_t*)res_.dmalloc((size_t)cfg_.pool_cap * 8);
+  d_sort_end_ = (int64_t*)res_.dmalloc((size_t)cfg_.pool_cap * 8);
+  d_sort_gid_ = (int64_t*)res_.dmalloc((size_t)cfg_.pool_cap * 8);
   for (int i = 0; i < 2; ++i) {
-    d_pool_end_[i] = (int64_t*)dmalloc((size_t)cfg_.pool_cap * 8);
-    d_pool_gid_[i] = (int64_t*)dmalloc((size_t)cfg_.pool_cap * 8);
+    d_pool_end_[i] = (int64_t*)res_.dmalloc((size_t)cfg_.pool_cap * 8);
+    d_pool_gid_[i] = (int64_t*)res_.dmalloc((size_t)cfg_.pool_cap * 8);
   }
   release_tmp_bytes_ = apm_release_tmp_bytes(cfg_.pool_cap);
   if (dev()) release_tmp_bytes_ = std::max(release_tmp_bytes_, apm_dj_tmp_bytes((uint32_t)cfg_.pool_cap + 2, 1024));
-  d_release_tmp_ = dmalloc(release_tmp_bytes_);
+  d_release_tmp_ = res_.dmalloc(release_tmp_bytes_);
   for (int k = 0; k < 2; ++k) {
-    HIP_OK(hipHostMalloc((void**)&h_release_gid_[k], (size_t)cfg_.pool_cap * 8, hipHostMallocDefault));
-    HIP_OK(hipEventCreateWithFlags(&ev_rel_[k], hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_fmt_[k], hipEventDisableTiming));
+    res_.pin(h_release_gid_[k], (size_t)cfg_.pool_cap * 8);
+    ev_rel_[k] = res_.new_event();
+    ev_fmt_[k] = res_.new_event();
   }
   // threads
   const char* pin_env = std::getenv("APM_PIN_THREADS");
@@ -506,23 +464,16 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   });
 }
 
+// Quiesce in order (lanes, threads, streams, sink holds), then release every resource at once.
 Engine::~Engine() {
   if (roll_lane_) {  // a pending rollover half reads buffers freed below
     try { roll_lane_->wait_all(); } catch (...) {}
     roll_lane_.reset();
   }
   ahead_lane_.reset();  // drains a pending next-batch pre-pass before the join state goes
-  if (in_stage_stream_) {  // a staged input copy writes a buffer the device join frees
-    hipStreamSynchronize(in_stage_stream_);
-    hipEventDestroy(in_stage_ev_);
-    hipStreamDestroy(in_stage_stream_);
-  }
+  if (in_stage_stream_) hipStreamSynchronize(in_stage_stream_);  // a staged input copy writes a buffer the device join frees
   fb_lane_.reset();     // and a pending fb emission before its buffers
-  if (nm_ev_) { hipEventSynchronize(nm_ev_); hipEventDestroy(nm_ev_); }
-  if (h_nm_send_) hipHostFree(h_nm_send_);
-  if (h_spill_snap_) hipHostFree(h_spill_snap_);
-  for (auto& m : spill_mark_) if (m.ev) hipEventDestroy(m.ev);
-  if (h_nm_recv_) hipHostFree(h_nm_recv_);
+  if (nm_ev_) hipEventSynchronize(nm_ev_);
   checkpoint_shutdown();
   {
     std::lock_guard<std::mutex> g(st_mu_);
@@ -544,86 +495,28 @@ Engine::~Engine() {
     hipStreamSynchronize(coll_stream_);
     coll_.reset();
     if (fb_stream_) hipStreamSynchronize(fb_stream_);
-    for (int i = 0; i < 2; ++i) {
-      hipEventDestroy(fleet_ev_[i]); hipEventDestroy(pack_ev_[i]);
-      if (fb_src_ev_[i]) hipEventDestroy(fb_src_ev_[i]);
-      if (fb_ev_[i]) hipEventDestroy(fb_ev_[i]);
-    }
-    if (h_fb_total_) hipHostFree(h_fb_total_);
-    if (fb_stream_) hipStreamDestroy(fb_stream_);
-    if (node_ev_) hipEventDestroy(node_ev_);
-    if (clock_ev_) hipEventDestroy(clock_ev_);
-    for (hipEvent_t e : bucket_ev_)
-      if (e) hipEventDestroy(e);
-    if (h_node_send_) hipHostFree(h_node_send_);
-    if (h_node_recv_) hipHostFree(h_node_recv_);
-    hipStreamDestroy(coll_stream_);
   }
-  if (h_sync_) hipHostFree(h_sync_);
   hipStreamSynchronize(stream_);
   hipStreamSynchronize(parse_stream_);
-  for (void* p : allocations_) hipFree(p);
-  for (auto& ps : pslot_) {
-    hipHostFree(ps.h_bytes); hipHostFree(ps.h_chunk_begin); hipHostFree(ps.h_chunk_kind); hipHostFree(ps.h_chunk_file);
-    if (ps.h_events) hipHostFree(ps.h_events);
-    hipHostFree(ps.h_counts); hipHostFree(ps.h_watermark);
-  }
-  hipHostFree(h_alerts_);
-  hipHostFree(h_alert_win_);
-  hipHostFree(h_alert_z_);
-  if (h_series_service_) hipHostFree(h_series_service_);
-  hipHostFree(h_n_alerts_); hipEventDestroy(ev_alerts_); hipEventDestroy(ev_release_); hipHostFree(h_tx_); hipHostFree(h_gid_);
-  if (ev_tx_staged_) hipEventDestroy(ev_tx_staged_);
-  for (int k = 0; k < 2; ++k) {
-    hipHostFree(h_release_gid_[k]);
-    if (h_fs_off_[k]) hipHostFree(h_fs_off_[k]);
-    hipEventDestroy(ev_rel_[k]);
-    hipEventDestroy(ev_fmt_[k]);
-  }
-  for (int r = 0; r < FMT_RING; ++r) {
+  // A pinned text slot the sink still references after 60 s is deliberately not freed (the sink
+  // would read freed memory): the owner forgets it instead.  st/fs ring first, then the two fb
+  // staging buffers (their holds are 2 and 3: fleet.cpp), then the db ring.
+  auto wait_holds = [this](int idx, void* slot) {
     FmtHolds& hs = *fmt_holds_;
     std::unique_lock<std::mutex> lk(hs.mu);
-    if (!hs.cv.wait_for(lk, std::chrono::seconds(60), [&] { return hs.n[6 + r] == 0; })) continue;
-    if (h_fmt_ring_[r]) hipHostFree(h_fmt_ring_[r]);
-  }
-  if (h_roll_out_) hipHostFree(h_roll_out_);
-  if (h_hist_total_) hipHostFree(h_hist_total_);
-  for (int k = 0; k < 2; ++k) {
-    if (h_hist_text_[k]) hipHostFree(h_hist_text_[k]);
-    if (ev_hist_[k]) hipEventDestroy(ev_hist_[k]);
-  }
-  if (cool_ev_) { hipEventSynchronize(cool_ev_); hipEventDestroy(cool_ev_); }
-  if (h_cool_idx_) { hipHostFree(h_cool_idx_); hipHostFree(h_cool_val_); }
+    if (!hs.cv.wait_for(lk, std::chrono::seconds(60), [&] { return hs.n[idx] == 0; })) res_.forget(slot);
+  };
+  for (int r = 0; r < FMT_RING; ++r) wait_holds(6 + r, h_fmt_ring_[r].p);
+  for (int k = 0; k < 2; ++k) wait_holds(2 + k, h_fb_out_[k].p);
+  if (cool_ev_) hipEventSynchronize(cool_ev_);
   if (dj_) {
     hipStreamSynchronize(out_stream_);
-    hipHostFree(h_ring_min_); hipHostFree(h_rel_n_); hipHostFree(h_rel_total_); hipHostFree(h_unseen_flag_);
-    for (int r = 0; r < REL_RING; ++r) {
-      {  // zero-copy db rows still referenced by the sink (bounded wait, as for st/fs)
-        FmtHolds& hs = *fmt_holds_;
-        std::unique_lock<std::mutex> lk(hs.mu);
-        if (!hs.cv.wait_for(lk, std::chrono::seconds(60), [&] { return hs.n[6 + FMT_RING + r] == 0; })) continue;
-      }
-      if (h_rel_text_[r]) hipHostFree(h_rel_text_[r]);
-    }
-    for (int k = 0; k < 2; ++k)
-      if (h_rel_offs_[k]) hipHostFree(h_rel_offs_[k]);
-
+    for (int r = 0; r < REL_RING; ++r) wait_holds(6 + FMT_RING + r, h_rel_text_[r].p);  // zero-copy db rows
     dj_.reset();
   }
   hipStreamSynchronize(out_stream_);
-  hipStreamDestroy(out_stream_);
-  if (rel_stream_) { hipStreamSynchronize(rel_stream_); hipStreamDestroy(rel_stream_); }
-  hipHostFree(h_fmt_meta_);
-  for (int k = 0; k < kStage; ++k) {
-    if (h_stage_[k]) hipHostFree(h_stage_[k]);
-    if (stage_ev_[k]) hipEventDestroy(stage_ev_[k]);
-  }
-  hipEventDestroy(ev_a_); hipEventDestroy(ev_b_);
-  for (int k = 0; k < 2; ++k) {
-    if (tail_csr_ev_[k]) hipEventDestroy(tail_csr_ev_[k]);
-    if (h_tail_csr_[k]) hipHostFree(h_tail_csr_[k]);
-  }
-  hipStreamDestroy(stream_); hipStreamDestroy(parse_stream_);
+  if (rel_stream_) hipStreamSynchronize(rel_stream_);
+  res_.release_all();
 }
 
 int32_t Engine::add_server(const std::string& name) {
@@ -940,7 +833,8 @@ void Engine::stage_batch(const uint8_t* host_bytes, uint64_t n_bytes) {
   const double t0 = now_ms();
   if (!in_stage_stream_) {
     HIP_OK(hipStreamCreateWithFlags(&in_stage_stream_, hipStreamNonBlocking));
-    HIP_OK(hipEventCreateWithFlags(&in_stage_ev_, hipEventDisableTiming));
+    res_.adopt(in_stage_stream_);
+    in_stage_ev_ = res_.new_event();
   }
   // The staging buffer is free: it is either fresh, the buffer an unconsumed earlier stage wrote
   // (ordered behind that copy on this stream), or -- after a swap -- the parse slot buffer of the
@@ -1482,10 +1376,10 @@ void Engine::flush() {
     unsigned long long u[3] = {0, 0, 0};
     int32_t fb = 0;
     ExportArgs ex{};
-    if (dev()) ex.add(d_unmapped_, hd_fmt_meta_ + 8, 8);
-    ex.add(d_spill_drop_, hd_fmt_meta_ + 10, 8);
-    ex.add(d_spill_drop_ + 1, hd_fmt_meta_ + 12, 8);
-    ex.add(d_fmt_fallback_, hd_fmt_meta_ + 14, 4);
+    if (dev()) ex.add(d_unmapped_, h_fmt_meta_.d + 8, 8);
+    ex.add(d_spill_drop_, h_fmt_meta_.d + 10, 8);
+    ex.add(d_spill_drop_ + 1, h_fmt_meta_.d + 12, 8);
+    ex.add(d_fmt_fallback_, h_fmt_meta_.d + 14, 4);
     apm_export(&ex, stream_);
     HIP_OK(hipStreamSynchronize(stream_));
     if (dev()) std::memcpy(&u[0], h_fmt_meta_ + 8, 8);
@@ -1609,6 +1503,7 @@ uint64_t Engine::post_rel(std::function<void()> fn) {
   if (!rel_lane_) {
     rel_lane_.reset(new TaskLane());
     HIP_OK(hipStreamCreateWithFlags(&rel_stream_, hipStreamNonBlocking));
+    res_.adopt(rel_stream_);
   }
   return rel_lane_->post(std::move(fn));
 }
@@ -1684,21 +1579,21 @@ void Engine::grow_tx_capacity(uint32_t need, uint32_t keep) {
   HIP_OK(hipStreamSynchronize(stream_));  // no copy / kernel still reads the old buffers
   TxRec* h_tx = nullptr;
   int64_t* h_gid = nullptr;
-  HIP_OK(hipHostMalloc((void**)&h_tx, (size_t)cap * sizeof(TxRec), hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&h_gid, (size_t)cap * 8, hipHostMallocDefault));
+  res_.pin(h_tx, (size_t)cap * sizeof(TxRec));
+  res_.pin(h_gid, (size_t)cap * 8);
   std::memcpy(h_tx, h_tx_, (size_t)keep * sizeof(TxRec));
   std::memcpy(h_gid, h_gid_, (size_t)keep * 8);
-  hipHostFree(h_tx_);
-  hipHostFree(h_gid_);
+  res_.pfree(h_tx_);
+  res_.pfree(h_gid_);
   h_tx_ = h_tx;
   h_gid_ = h_gid;
-  dfree(d_tx_);
-  dfree(d_gid_);
-  d_tx_ = (TxRec*)dmalloc((size_t)cap * sizeof(TxRec));
-  d_gid_ = (int64_t*)dmalloc((size_t)cap * 8);
+  res_.dfree(d_tx_);
+  res_.dfree(d_gid_);
+  d_tx_ = (TxRec*)res_.dmalloc((size_t)cap * sizeof(TxRec));
+  d_gid_ = (int64_t*)res_.dmalloc((size_t)cap * 8);
   if (cap > std::max<int64_t>(ord_cap_, 0)) {
-    dfree(d_ord_list_);
-    d_ord_list_ = (int32_t*)dmalloc((size_t)cap * 4);
+    res_.dfree(d_ord_list_);
+    d_ord_list_ = (int32_t*)res_.dmalloc((size_t)cap * 4);
     ord_cap_ = cap;
   }
   cfg_.max_tx_per_batch = (int32_t)cap;
@@ -1714,7 +1609,7 @@ StatsState Engine::stats_state() const {
   st.ord_n = d_ord_n_;
   st.ord_done = (uint32_t*)(d_ord_n_ + 1);
   st.keep = (int32_t)(cfg_.window + cfg_.buffer);
-  st.spill_snap = hd_spill_snap_;
+  st.spill_snap = h_spill_snap_.d;
   st.nslot = nslot_;
   return st;
 }
@@ -1782,18 +1677,17 @@ int32_t ring_slots_for(int window, int buffer) { return std::max<int32_t>(NSLOT_
 void Engine::alloc_ring(int32_t nslot) {
   const int32_t S = cfg_.max_series;
   nslot_ = nslot;
-  d_counts_cells_ = (int32_t*)dmalloc((size_t)nslot * S * 4);
-  d_cells_ = (int32_t*)dmalloc((size_t)nslot * S * cfg_.cell_cap * 4);
-  d_spill_n_ = (int32_t*)dmalloc((size_t)nslot * 4);
-  d_spill_series_ = (int32_t*)dmalloc((size_t)nslot * cfg_.spill_cap * 4);
-  d_spill_val_ = (int32_t*)dmalloc((size_t)nslot * cfg_.spill_cap * 4);
-  d_spill_series_alt_ = (int32_t*)dmalloc((size_t)nslot * cfg_.spill_cap * 4);
-  d_spill_val_alt_ = (int32_t*)dmalloc((size_t)nslot * cfg_.spill_cap * 4);
+  d_counts_cells_ = (int32_t*)res_.dmalloc((size_t)nslot * S * 4);
+  d_cells_ = (int32_t*)res_.dmalloc((size_t)nslot * S * cfg_.cell_cap * 4);
+  d_spill_n_ = (int32_t*)res_.dmalloc((size_t)nslot * 4);
+  d_spill_series_ = (int32_t*)res_.dmalloc((size_t)nslot * cfg_.spill_cap * 4);
+  d_spill_val_ = (int32_t*)res_.dmalloc((size_t)nslot * cfg_.spill_cap * 4);
+  d_spill_series_alt_ = (int32_t*)res_.dmalloc((size_t)nslot * cfg_.spill_cap * 4);
+  d_spill_val_alt_ = (int32_t*)res_.dmalloc((size_t)nslot * cfg_.spill_cap * 4);
   spill_tmp_bytes_ = apm_spill_sort_tmp_bytes(cfg_.spill_cap, S, nslot);
-  d_spill_tmp_ = dmalloc(spill_tmp_bytes_);
-  d_win_slots_ = (int32_t*)dmalloc((size_t)nslot * 4);
-  HIP_OK(hipHostMalloc((void**)&h_spill_snap_, (size_t)nslot * 4, hipHostMallocDefault));
-  HIP_OK(hipHostGetDevicePointer((void**)&hd_spill_snap_, h_spill_snap_, 0));
+  d_spill_tmp_ = res_.dmalloc(spill_tmp_bytes_);
+  d_win_slots_ = (int32_t*)res_.dmalloc((size_t)nslot * 4);
+  res_.pin(h_spill_snap_, (size_t)nslot * 4);
   std::memset(h_spill_snap_, 0, (size_t)nslot * 4);
   slot_bucket_.assign((size_t)nslot, NO_BUCKET);
   spill_clear_at_.assign((size_t)nslot, 0);
@@ -1813,10 +1707,10 @@ void Engine::grow_ring(int32_t nslot) {
   int32_t* o_sv = d_spill_val_;
   const std::vector<int64_t> o_bucket = slot_bucket_;
   const std::vector<uint64_t> o_clear = spill_clear_at_;
-  std::vector<int32_t> o_snap(h_spill_snap_, h_spill_snap_ + nslot_);
-  for (void* p : {(void*)d_spill_series_alt_, (void*)d_spill_val_alt_, d_spill_tmp_, (void*)d_win_slots_}) dfree(p);
-  HIP_OK(hipHostFree(h_spill_snap_));
-  if (d_ck_slots_) { dfree(d_ck_slots_); d_ck_slots_ = nullptr; }  // (sized by the ring: re-made on demand)
+  std::vector<int32_t> o_snap(h_spill_snap_.h, h_spill_snap_.h + nslot_);
+  for (void* p : {(void*)d_spill_series_alt_, (void*)d_spill_val_alt_, d_spill_tmp_, (void*)d_win_slots_}) res_.dfree(p);
+  res_.pfree(h_spill_snap_);
+  if (d_ck_slots_) { res_.dfree(d_ck_slots_); d_ck_slots_ = nullptr; }  // (sized by the ring: re-made on demand)
   const int32_t o_n = nslot_;
   alloc_ring(nslot);
   for (int32_t s = 0; s < o_n; ++s) {
@@ -1837,7 +1731,7 @@ void Engine::grow_ring(int32_t nslot) {
     h_spill_snap_[t] = o_snap[(size_t)s];
   }
   HIP_OK(hipStreamSynchronize(stream_));
-  for (void* p : {(void*)o_counts, (void*)o_cells, (void*)o_sn, (void*)o_ss, (void*)o_sv}) dfree(p);
+  for (void* p : {(void*)o_counts, (void*)o_cells, (void*)o_sn, (void*)o_ss, (void*)o_sv}) res_.dfree(p);
   spill_resync();  // fill levels at the new slots
   ++ring_grows_;
 }
@@ -1852,23 +1746,23 @@ void Engine::resize_spill(int32_t cap) {
   HIP_OK(hipStreamSynchronize(stream_));
   const size_t old = (size_t)cfg_.spill_cap;
   const size_t w = std::min(old, (size_t)cap) * 4;  // (a shrink keeps every slot's fill: cap >= it)
-  int32_t* ser = (int32_t*)dmalloc((size_t)nslot_ * cap * 4);
-  int32_t* val = (int32_t*)dmalloc((size_t)nslot_ * cap * 4);
+  int32_t* ser = (int32_t*)res_.dmalloc((size_t)nslot_ * cap * 4);
+  int32_t* val = (int32_t*)res_.dmalloc((size_t)nslot_ * cap * 4);
   HIP_OK(hipMemcpy2DAsync(ser, (size_t)cap * 4, d_spill_series_, old * 4, w, nslot_, hipMemcpyDeviceToDevice, stream_));
   HIP_OK(hipMemcpy2DAsync(val, (size_t)cap * 4, d_spill_val_, old * 4, w, nslot_, hipMemcpyDeviceToDevice, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
-  dfree(d_spill_series_);
-  dfree(d_spill_val_);
-  dfree(d_spill_series_alt_);
-  dfree(d_spill_val_alt_);
-  dfree(d_spill_tmp_);
+  res_.dfree(d_spill_series_);
+  res_.dfree(d_spill_val_);
+  res_.dfree(d_spill_series_alt_);
+  res_.dfree(d_spill_val_alt_);
+  res_.dfree(d_spill_tmp_);
   d_spill_series_ = ser;
   d_spill_val_ = val;
-  d_spill_series_alt_ = (int32_t*)dmalloc((size_t)nslot_ * cap * 4);
-  d_spill_val_alt_ = (int32_t*)dmalloc((size_t)nslot_ * cap * 4);
+  d_spill_series_alt_ = (int32_t*)res_.dmalloc((size_t)nslot_ * cap * 4);
+  d_spill_val_alt_ = (int32_t*)res_.dmalloc((size_t)nslot_ * cap * 4);
   cfg_.spill_cap = cap;
   spill_tmp_bytes_ = apm_spill_sort_tmp_bytes(cfg_.spill_cap, cfg_.max_series, nslot_);
-  d_spill_tmp_ = dmalloc(spill_tmp_bytes_);
+  d_spill_tmp_ = res_.dmalloc(spill_tmp_bytes_);
   metrics_.spill_capacity = cap;
 }
 
@@ -1890,17 +1784,17 @@ std::pair<size_t, size_t> Engine::trim_device_memory() {
   // checkpoint packing scratch and the incremental checkpoint's staging (re-made by the next one;
   // a staging allocation that then fails falls back to the synchronous writer)
   for (void** q : {(void**)&d_ck_lens_, (void**)&d_ck_offs_, (void**)&d_ck_packed_, &d_ck_ptmp_}) {
-    dfree(*q);
+    res_.dfree(*q);
     *q = nullptr;
   }
   ck_pack_n_ = 0;
   ck_ptmp_bytes_ = 0;
   for (int k = 0; k < 2; ++k) {
-    dfree(d_ck_text_[k]);
+    res_.dfree(d_ck_text_[k]);
     d_ck_text_[k] = nullptr;
     ck_text_cap_[k] = 0;
   }
-  dfree(d_ck_gids_);
+  res_.dfree(d_ck_gids_);
   d_ck_gids_ = nullptr;
   ck_gids_cap_ = 0;
   // the snapshot staging is kept at what the last snapshot needed (re-allocating it at the next
@@ -1909,10 +1803,8 @@ std::pair<size_t, size_t> Engine::trim_device_memory() {
   if (ck_stage_bytes_ > 2 * ck_last_need_) free_ck_stage();
   if (d_ck_defer_ && ck_defer_cap_ > 2 * std::max<size_t>(ck_defer_want_, (size_t)1 << 30)) {
     // the deferred small-section staging (the writer is idle: checkpoint_wait)
-    HIP_OK(hipFree(d_ck_defer_));
+    res_.dfree(d_ck_defer_);
     d_ck_defer_ = nullptr;
-    std::lock_guard<std::mutex> g(alloc_mu_);
-    device_bytes_ -= ck_defer_cap_;
     ck_defer_cap_ = 0;
   }
   HIP_OK(hipStreamSynchronize(stream_));
@@ -2027,7 +1919,7 @@ void Engine::stats_for_batch(std::vector<TxOut>& txs, double batch_t0) {
   if (n == 0) return;
   HIP_OK(hipMemcpyAsync(d_tx_, h_tx_, (size_t)n * sizeof(TxRec), hipMemcpyHostToDevice, stream_));
   HIP_OK(hipMemcpyAsync(d_gid_, h_gid_, (size_t)n * 8, hipMemcpyHostToDevice, stream_));
-  if (!ev_tx_staged_) HIP_OK(hipEventCreateWithFlags(&ev_tx_staged_, hipEventDisableTiming));
+  if (!ev_tx_staged_) ev_tx_staged_ = res_.new_event();
   HIP_OK(hipEventRecord(ev_tx_staged_, stream_));
   {
     StatsState st = stats_state();
@@ -2150,9 +2042,7 @@ void Engine::stats_for_batch_dev(DevJoinBatch& b, double batch_t0) {
 // does.  Bulk transfers (batch bytes, st/fs text) stay on the DMA engines.
 void Engine::h2d(void* d, const void* h, size_t n, hipStream_t s) {
   if (n == 0) return;
-  void* hv = nullptr;
-  HIP_OK(hipHostGetDevicePointer(&hv, const_cast<void*>(h), 0));
-  apm_copy(d, hv, n, s);
+  apm_copy(d, HipRes::device_alias(h), n, s);
 }
 
 void Engine::lane_d2h(void* h, const void* d, size_t n, hipStream_t s) {
@@ -2164,9 +2054,7 @@ void Engine::lane_sync() { HIP_OK(hipStreamSynchronize(out_stream_)); }
 
 void Engine::d2h(void* h, const void* d, size_t n, hipStream_t s) {
   if (n == 0) return;
-  void* hv = nullptr;
-  HIP_OK(hipHostGetDevicePointer(&hv, h, 0));
-  apm_copy(hv, d, n, s);
+  apm_copy(HipRes::device_alias(h), d, n, s);
 }
 
 // Pinned staging for the stats thread's small H2D uploads (raw -> series pairs, unseen series
@@ -2175,15 +2063,13 @@ void Engine::d2h(void* h, const void* d, size_t n, hipStream_t s) {
 char* Engine::stage(size_t bytes) {
   const int k = stage_k_;
   if (stage_ev_[k]) HIP_OK(hipEventSynchronize(stage_ev_[k]));
-  else HIP_OK(hipEventCreateWithFlags(&stage_ev_[k], hipEventDisableTiming));
-  if (bytes > h_stage_cap_[k]) {
+  else stage_ev_[k] = res_.new_event();
+  if (bytes > h_stage_[k].cap) {
     // slots rotate over uploads of very different sizes (80k-series permutation vs a JMX row):
     // grow each to the largest request seen so far, so the ring stops reallocating (a pinned
     // free + alloc costs ~1 ms) after one pass instead of after every slot met every size
     stage_max_ = std::max(stage_max_, bytes);
-    if (h_stage_[k]) HIP_OK(hipHostFree(h_stage_[k]));
-    h_stage_cap_[k] = std::max<size_t>(stage_max_ * 2, 1 << 20);
-    HIP_OK(hipHostMalloc((void**)&h_stage_[k], h_stage_cap_[k], hipHostMallocDefault));
+    res_.reserve(h_stage_[k], bytes, std::max<size_t>(stage_max_ * 2, 1 << 20));
   }
   return h_stage_[k];
 }
@@ -2194,7 +2080,7 @@ void Engine::stage_done() {
 }
 
 int32_t* Engine::pinned_pairs(size_t n_ints) {
-  if (n_ints * 4 > pairs_bytes_) d_pairs_ = (int32_t*)regrow(d_pairs_, pairs_bytes_, n_ints * 8 + 65536);
+  if (n_ints * 4 > pairs_bytes_) d_pairs_ = (int32_t*)res_.regrow(d_pairs_, pairs_bytes_, n_ints * 8 + 65536, stream_);
   return (int32_t*)stage(n_ints * 4);
 }
 
@@ -2379,7 +2265,7 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
     const ZOut* zl[MAX_LAGS] = {};
     for (int l = 0; l < cfg_.n_lags; ++l) zl[l] = lag_[l].out;
     apm_alert_gather(d_alerts_, d_n_alerts_, cfg_.max_alerts, d_win_, zl, cfg_.n_lags, want(OUT_AL) ? 1 : 0,
-                     hd_alerts_, hd_alert_win_, hd_alert_z_, hd_n_alerts_, stream_);
+                     h_alerts_.d, h_alert_win_.d, h_alert_z_.d, h_n_alerts_.d, stream_);
     HIP_OK(hipEventRecord(ev_alerts_, stream_));
   }
   if (dev()) {
@@ -2470,7 +2356,7 @@ void Engine::release_device(int64_t edge_ts) {
   tail_n_ = 0;
   apm_dj_count_le(d_pool_end_[pool_cur_], pool_n_, edge_ts, d_rel_n_, stream_);
   ExportArgs ex{};
-  ex.add(d_rel_n_, hd_rel_n_, 8);
+  ex.add(d_rel_n_, h_rel_n_.d, 8);
   if (want(OUT_DB) && pool_n_ > 0) {
     rel_copy_ = db_copy_;
     const int rc = rel_copy_
@@ -2480,8 +2366,8 @@ void Engine::release_device(int64_t edge_ts) {
                        : apm_dj_gather_plan(d_pool_gid_[pool_cur_], pool_n_, d_rel_n_, d_rel_lens_, d_rel_offs_,
                                             d_release_tmp_, release_tmp_bytes_, stream_);
     if (rc != 0) throw std::runtime_error("release tmp too small");
-    ex.add(d_rel_offs_ + pool_n_, hd_rel_total_, 4);
-    if (rel_copy_) ex.add(d_rel_fb_, hd_rel_total_ + 1, 4, true, 0);  // read and reset
+    ex.add(d_rel_offs_ + pool_n_, h_rel_total_.d, 4);
+    if (rel_copy_) ex.add(d_rel_fb_, h_rel_total_.d + 1, 4, true, 0);  // read and reset
   }
   apm_export(&ex, stream_);
 }
@@ -2515,7 +2401,7 @@ void Engine::release_device_finish() {
     const double tw = now_ms();
     rel_wait(rel_task_[k]);  // the buffer's previous reader is done
     trace_event("rel.wait_lane", tw, now_ms(), 1);
-    if (total + 64 > rel_text_cap_[k]) d_rel_text_[k] = (char*)regrow(d_rel_text_[k], rel_text_cap_[k], total + 64);
+    if (total + 64 > rel_text_cap_[k]) d_rel_text_[k] = (char*)res_.regrow(d_rel_text_[k], rel_text_cap_[k], total + 64, stream_);
     if (copy)
       apm_dj_txcopy_write(d_pool_gid_[pool_cur_], released, dj_->ring(), dj_->ring_cap(), d_rel_offs_, d_rel_text_[k],
                           stream_);
@@ -2526,11 +2412,7 @@ void Engine::release_device_finish() {
     // release: copied here, in stream order)
     const bool rows = byte_sink_[OUT_DB] != nullptr && !host_enc;
     if (rows) {
-      if ((size_t)released + 1 > h_rel_offs_cap_[k]) {
-        if (h_rel_offs_[k]) HIP_OK(hipHostFree(h_rel_offs_[k]));
-        h_rel_offs_cap_[k] = ((size_t)released + 1) * 2;
-        HIP_OK(hipHostMalloc((void**)&h_rel_offs_[k], h_rel_offs_cap_[k] * 4, hipHostMallocDefault));
-      }
+      res_.reserve(h_rel_offs_[k], (size_t)released + 1, ((size_t)released + 1) * 2);
       d2h(h_rel_offs_[k], d_rel_offs_, ((size_t)released + 1) * 4, stream_);
     }
     HIP_OK(hipEventRecord(ev_rel_[k], stream_));
@@ -2543,12 +2425,8 @@ void Engine::release_device_finish() {
       wait_fmt_holds(6 + FMT_RING + rk);  // the sink still writes from this slot (zero-copy COPY rows)
       trace_event("lane db wait gather", tw0, tw1, 4);
       trace_event("lane db wait sink", tw1, now_ms(), 4);
-      char*& h = h_rel_text_[rk];
-      if (total > h_rel_text_cap_[rk]) {
-        if (h) HIP_OK(hipHostFree(h));
-        h_rel_text_cap_[rk] = total * 2 + (4 << 20);  // (a pinned allocation costs ms: 2x headroom)
-        HIP_OK(hipHostMalloc((void**)&h, h_rel_text_cap_[rk], hipHostMallocDefault));
-      }
+      res_.reserve(h_rel_text_[rk], total, total * 2 + (4 << 20));  // (a pinned allocation costs ms: 2x headroom)
+      char* const h = h_rel_text_[rk];
       const double tl0 = now_ms();
       lane_d2h(h, d_rel_text_[k], total, rel_stream_);
       HIP_OK(hipStreamSynchronize(rel_stream_));
@@ -2578,7 +2456,7 @@ void Engine::release_device_finish() {
   // d_ring_min_ is UINT64_MAX here: the export below resets it after reading
   apm_dj_min_pos(d_pool_gid_[pool_cur_] + pool_off_, pool_n_, d_ring_min_, stream_);
   ExportArgs ex{};
-  ex.add(d_ring_min_, hd_ring_min_, 8, /*reset=*/true, ~0ull);
+  ex.add(d_ring_min_, h_ring_min_.d, 8, /*reset=*/true, ~0ull);
   apm_export(&ex, stream_);
   ring_low_pending_ = roll_ring_base_;
 }
@@ -2590,12 +2468,12 @@ void Engine::flush_alerts(int64_t edge_ts) {
   if (na <= 0) return;
   const bool need_rows = want(OUT_AL);
   // one sequential copy out of the GPU-written pinned buffers before the sort's random reads
-  std::vector<AlertRec> alerts(h_alerts_, h_alerts_ + na);
+  std::vector<AlertRec> alerts(h_alerts_.h, h_alerts_.h + na);
   std::vector<WinStat> awin;
   std::vector<ZOut> az;
   if (need_rows) {
-    awin.assign(h_alert_win_, h_alert_win_ + na);
-    az.assign(h_alert_z_, h_alert_z_ + na);
+    awin.assign(h_alert_win_.h, h_alert_win_.h + na);
+    az.assign(h_alert_z_.h, h_alert_z_.h + na);
   }
   // candidate i's rows are win_of(i) / z_of(i) in device order; decide in emission order
   std::vector<int32_t> ord((size_t)na);
@@ -2689,20 +2567,12 @@ void Engine::cool_mark(const std::vector<std::pair<uint64_t, double>>& wins, hip
     }
   }
   if (upd.empty()) return;
-  if (!cool_ev_) HIP_OK(hipEventCreateWithFlags(&cool_ev_, hipEventDisableTiming));
+  if (!cool_ev_) cool_ev_ = res_.new_event();
   else HIP_OK(hipEventSynchronize(cool_ev_));  // the previous scatter read the staging
-  if (upd.size() > cool_cap_) {
-    if (h_cool_idx_) { HIP_OK(hipHostFree(h_cool_idx_)); HIP_OK(hipHostFree(h_cool_val_)); }
-    cool_cap_ = std::max<size_t>(upd.size() * 2, 4096);
-    HIP_OK(hipHostMalloc((void**)&h_cool_idx_, cool_cap_ * 4, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&h_cool_val_, cool_cap_ * 8, hipHostMallocDefault));
-  }
+  res_.reserve(h_cool_idx_, upd.size(), std::max<size_t>(upd.size() * 2, 4096), true);
+  res_.reserve(h_cool_val_, upd.size(), std::max<size_t>(upd.size() * 2, 4096), true);
   for (size_t i = 0; i < upd.size(); ++i) { h_cool_idx_[i] = upd[i].first; h_cool_val_[i] = upd[i].second; }
-  int32_t* di = nullptr;
-  double* dv = nullptr;
-  HIP_OK(hipHostGetDevicePointer((void**)&di, h_cool_idx_, 0));
-  HIP_OK(hipHostGetDevicePointer((void**)&dv, h_cool_val_, 0));
-  apm_scatter_f64(d_cool_t_, di, dv, (int32_t)upd.size(), st);
+  apm_scatter_f64(d_cool_t_, h_cool_idx_.d, h_cool_val_.d, (int32_t)upd.size(), st);
   HIP_OK(hipEventRecord(cool_ev_, st));
 }
 
@@ -2738,50 +2608,12 @@ int32_t Engine::intern_name(const std::string& name) {
   return off;
 }
 
-// Frees a dmalloc'd buffer and forgets it (the destructor frees what is still listed).
-void Engine::dfree(void* p) {
-  if (!p) return;
-  HIP_OK(hipFree(p));
-  std::lock_guard<std::mutex> g(alloc_mu_);
-  allocations_.erase(std::remove(allocations_.begin(), allocations_.end(), p), allocations_.end());
-  auto it = alloc_bytes_.find(p);
-  if (it != alloc_bytes_.end()) {
-    device_bytes_ -= it->second;
-    alloc_bytes_.erase(it);
-  }
-}
-
-void* Engine::regrow(void* old, size_t& cap, size_t need) {
-  if (need <= cap && old) return old;
-  // 2x headroom: a regrow syncs the stream and hipFree waits for the device (a few ms of one
-  // batch), so the per-batch buffers must stop growing during the warm-up
-  size_t nc = std::max<size_t>(2 * need, 4 << 20);
-  // The old buffer is retired, not freed: kernels still in flight on any stream may read it, and
-  // hipFree would wait for the whole device (the collective stream included).  Retired buffers
-  // stay listed in allocations_ (and counted) until the engine goes away; with 2x growth they
-  // add up to less than the live buffer.
-  (void)old;
-  cap = nc;
-  void* p = nullptr;
-  const size_t bytes = (nc + 255) & ~(size_t)255;
-  HIP_OK(hipMalloc(&p, bytes));
-  // zeroed in order on the stats stream; the sync orders it for the other streams' later work
-  // without waiting for them (dmalloc's device-wide sync is for construction time)
-  HIP_OK(hipMemsetAsync(p, 0, bytes, stream_));
-  HIP_OK(hipStreamSynchronize(stream_));
-  std::lock_guard<std::mutex> g(alloc_mu_);
-  allocations_.push_back(p);
-  alloc_bytes_[p] = bytes;
-  device_bytes_ += bytes;
-  return p;
-}
-
 void Engine::sync_format_tables() {
   // uploads go through the pinned stager: nothing here waits for the stats stream
   if (names_uploaded_ < h_names_.size()) {
     if (h_names_.size() > names_cap_) {
       // grow: re-upload everything into the bigger buffer
-      d_names_ = (char*)regrow(d_names_, names_cap_, h_names_.size());
+      d_names_ = (char*)res_.regrow(d_names_, names_cap_, h_names_.size(), stream_);
       names_uploaded_ = 0;
     }
     const size_t nb = h_names_.size() - names_uploaded_;
@@ -2966,7 +2798,7 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   trace_event("fmt.wait_lane", tf1, now_ms(), 1);
   const size_t st_cap = fa.want_st ? (size_t)n * (176 + max_name_len_) : 0;
   const size_t fs_cap = fa.want_fs ? (size_t)n * cfg_.n_lags * (fs_copy_ ? 720 + 2 * max_name_len_ : 560 + max_name_len_) : 0;
-  if (st_cap + fs_cap + 64 > fmt_out_cap_[k]) d_fmt_out_[k] = (char*)regrow(d_fmt_out_[k], fmt_out_cap_[k], st_cap + fs_cap + 64);
+  if (st_cap + fs_cap + 64 > fmt_out_cap_[k]) d_fmt_out_[k] = (char*)res_.regrow(d_fmt_out_[k], fmt_out_cap_[k], st_cap + fs_cap + 64, stream_);
   fa.st_out = d_fmt_out_[k];
   fa.fs_out = d_fmt_out_[k] + st_cap;
   const double tpl = now_ms();
@@ -2978,19 +2810,15 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   trace_event("fmt.write", tpw, now_ms(), 1);
   {
     ExportArgs ex{};
-    ex.add(fa.st_off + n, hd_fmt_meta_ + 4 * k + 0, 4);
-    ex.add(fa.fs_off + (size_t)n * cfg_.n_lags, hd_fmt_meta_ + 4 * k + 1, 4);
+    ex.add(fa.st_off + n, h_fmt_meta_.d + 4 * k + 0, 4);
+    ex.add(fa.fs_off + (size_t)n * cfg_.n_lags, h_fmt_meta_.d + 4 * k + 1, 4);
     apm_export(&ex, stream_);
   }
   fs_rows_[k] = 0;
   if (fa.want_fs && byte_sink_[OUT_FS]) {
     // the row offsets for the sink's flush cuts (slot k's lane is done with the previous ones)
     const size_t rows = (size_t)n * cfg_.n_lags;
-    if (rows + 1 > h_fs_off_cap_[k]) {
-      if (h_fs_off_[k]) HIP_OK(hipHostFree(h_fs_off_[k]));
-      h_fs_off_cap_[k] = (rows + 1) * 5 / 4;
-      HIP_OK(hipHostMalloc((void**)&h_fs_off_[k], h_fs_off_cap_[k] * 4, hipHostMallocDefault));
-    }
+    res_.reserve(h_fs_off_[k], rows + 1, (rows + 1) * 5 / 4);
     d2h(h_fs_off_[k], fa.fs_off, (rows + 1) * 4, stream_);
     fs_rows_[k] = rows;
   }
@@ -3009,11 +2837,7 @@ void Engine::format_rollover_text(int64_t edge_ts) {
     wait_fmt_holds(6 + hk);  // the sink still writes from this ring slot (zero-copy COPY rows)
     trace_event("lane st/fs wait format", tw0, tw1, 4);
     trace_event("lane st/fs wait sink", tw1, now_ms(), 4);
-    if (st_total + fs_total > h_fmt_ring_cap_[hk]) {
-      if (h_fmt_ring_[hk]) HIP_OK(hipHostFree(h_fmt_ring_[hk]));
-      h_fmt_ring_cap_[hk] = (st_total + fs_total) * 5 / 4 + (4 << 20);
-      HIP_OK(hipHostMalloc((void**)&h_fmt_ring_[hk], h_fmt_ring_cap_[hk], hipHostMallocDefault));
-    }
+    res_.reserve(h_fmt_ring_[hk], st_total + fs_total, (st_total + fs_total) * 5 / 4 + (4 << 20));
     char* h = h_fmt_ring_[hk];
     const double tl0 = now_ms();
     if (st_total) lane_d2h(h, dst, st_total);
@@ -3064,13 +2888,13 @@ void Engine::hist_bucket(int64_t b, int slot) {
   out_wait(hist_task_[k]);  // slot k's previous D2H + emission is done
   // the output bound needs no length pass: every row is at most apm_hist_row_bound bytes
   const size_t cap = (size_t)n * apm_hist_row_bound(max_name_len_) + 64;
-  if (cap > hist_out_cap_[k]) d_hist_out_[k] = (char*)regrow(d_hist_out_[k], hist_out_cap_[k], cap);
+  if (cap > hist_out_cap_[k]) d_hist_out_[k] = (char*)res_.regrow(d_hist_out_[k], hist_out_cap_[k], cap, stream_);
   ha.out = d_hist_out_[k];
   if (apm_hist_plan(&ha, d_hist_tmp_, hist_tmp_bytes_, stream_) != 0) throw std::runtime_error("histogram scan failed");
   apm_hist_write(&ha, stream_);
   {
     ExportArgs ex{};
-    ex.add(ha.off + n, hd_hist_total_ + k, 4);
+    ex.add(ha.off + n, h_hist_total_.d + k, 4);
     apm_export(&ex, stream_);
   }
   HIP_OK(hipEventRecord(ev_hist_[k], stream_));
@@ -3079,11 +2903,7 @@ void Engine::hist_bucket(int64_t b, int slot) {
     HIP_OK(hipEventSynchronize(ev_hist_[k]));
     const size_t total = h_hist_total_[k];
     if (!total) return;
-    if (total > h_hist_text_cap_[k]) {
-      if (h_hist_text_[k]) HIP_OK(hipHostFree(h_hist_text_[k]));
-      h_hist_text_cap_[k] = total * 2 + (1 << 20);
-      HIP_OK(hipHostMalloc((void**)&h_hist_text_[k], h_hist_text_cap_[k], hipHostMallocDefault));
-    }
+    res_.reserve(h_hist_text_[k], total, total * 2 + (1 << 20));
     lane_d2h(h_hist_text_[k], dst, total);
     lane_sync();
     emit_bytes(OUT_LH, h_hist_text_[k], total);
@@ -3126,11 +2946,11 @@ void Engine::server_rollup(int64_t edge_ts) {
   if (nsv == 0) return;
   if ((size_t)nsv > roll_cap_) {  // grow (rare: new servers)
     size_t cap = std::max<size_t>(64, (size_t)nsv * 2), c1 = 0, c2 = 0, c3 = 0;
-    d_ctx_ = (double*)regrow(d_ctx_, c1 = roll_cap_ * CTX_FIELDS * 8, cap * CTX_FIELDS * 8);
-    d_roll_acc_ = (unsigned long long*)regrow(d_roll_acc_, c2 = roll_cap_ * ROLLUP_ACC * 8, cap * ROLLUP_ACC * 8);
-    d_roll_out_ = (double*)regrow(d_roll_out_, c3 = roll_cap_ * ROLLUP_OUT * 8, cap * ROLLUP_OUT * 8);
-    if (h_roll_out_) HIP_OK(hipHostFree(h_roll_out_));
-    HIP_OK(hipHostMalloc((void**)&h_roll_out_, cap * ROLLUP_OUT * 8, hipHostMallocDefault));
+    d_ctx_ = (double*)res_.regrow(d_ctx_, c1 = roll_cap_ * CTX_FIELDS * 8, cap * CTX_FIELDS * 8, stream_);
+    d_roll_acc_ = (unsigned long long*)res_.regrow(d_roll_acc_, c2 = roll_cap_ * ROLLUP_ACC * 8, cap * ROLLUP_ACC * 8, stream_);
+    d_roll_out_ = (double*)res_.regrow(d_roll_out_, c3 = roll_cap_ * ROLLUP_OUT * 8, cap * ROLLUP_OUT * 8, stream_);
+    res_.pfree(h_roll_out_);
+    res_.pin(h_roll_out_, cap * ROLLUP_OUT * 8);
     roll_cap_ = cap;
     ctx_dirty_ = true;
   }
@@ -3333,11 +3153,7 @@ void Engine::pack_moments_locked(double* d_dst, int32_t cap, hipStream_t stream,
     // Pinned host mirror of the table: the series list is append-only, so each upload reads a
     // region no earlier (possibly still in-flight) copy reads -- no stream sync on the stats thread.
     const int32_t lo = series_service_uploaded_;
-    if (!h_series_service_) {
-      void* p = nullptr;
-      HIP_OK(hipHostMalloc(&p, (size_t)cfg_.max_series * 4, hipHostMallocDefault));
-      h_series_service_ = (int32_t*)p;
-    }
+    if (!h_series_service_) res_.pin(h_series_service_, (size_t)cfg_.max_series * 4);
     if (lo == 0) HIP_OK(hipStreamSynchronize(stream_));  // table reset (load_state / new slots): rewrite from 0
     for (int32_t s = lo; s < n_series_; ++s) h_series_service_[s] = svc_key(s);
     HIP_OK(hipMemcpyAsync(d_series_service_ + lo, h_series_service_ + lo, (size_t)(n_series_ - lo) * 4,
@@ -3373,8 +3189,8 @@ void Engine::pack_moments_locked(double* d_dst, int32_t cap, hipStream_t stream,
       HIP_OK(hipEventRecord(ev_a_, stream));
       if (coll_) coll_wait(nullptr, ev_a_, "fleet CSR rebuild");
       else HIP_OK(hipEventSynchronize(ev_a_));
-      d_svc_off_ = (int32_t*)regrow(d_svc_off_, svc_off_cap_, h_svc_off_.size() * 4);
-      d_svc_ids_ = (int32_t*)regrow(d_svc_ids_, svc_ids_cap_, h_svc_ids_.size() * 4);
+      d_svc_off_ = (int32_t*)res_.regrow(d_svc_off_, svc_off_cap_, h_svc_off_.size() * 4, stream_);
+      d_svc_ids_ = (int32_t*)res_.regrow(d_svc_ids_, svc_ids_cap_, h_svc_ids_.size() * 4, stream_);
       HIP_OK(hipMemcpyAsync(d_svc_off_, h_svc_off_.data(), h_svc_off_.size() * 4, hipMemcpyHostToDevice, stream));
       HIP_OK(hipMemcpyAsync(d_svc_ids_, h_svc_ids_.data(), h_svc_ids_.size() * 4, hipMemcpyHostToDevice, stream));
       svc_csr_n_ = n_series_;
@@ -3415,15 +3231,11 @@ void Engine::pack_moments_locked(double* d_dst, int32_t cap, hipStream_t stream,
           tail_csr_m_ = (int32_t)m;
           const int k = tail_k_;
           tail_k_ ^= 1;
-          if (!tail_csr_ev_[k]) HIP_OK(hipEventCreateWithFlags(&tail_csr_ev_[k], hipEventDisableTiming));
+          if (!tail_csr_ev_[k]) tail_csr_ev_[k] = res_.new_event();
           else HIP_OK(hipEventSynchronize(tail_csr_ev_[k]));
-          if (nb > tail_csr_cap_[k]) {
-            if (h_tail_csr_[k]) HIP_OK(hipHostFree(h_tail_csr_[k]));
-            tail_csr_cap_[k] = nb * 2 + 4096;
-            HIP_OK(hipHostMalloc((void**)&h_tail_csr_[k], tail_csr_cap_[k], hipHostMallocDefault));
-          }
-          if (nb > d_tail_csr_cap_) d_tail_csr_ = (int32_t*)regrow(d_tail_csr_, d_tail_csr_cap_, nb * 2 + 4096);
-          int32_t* h = h_tail_csr_[k];
+          res_.reserve(h_tail_csr_[k], nb, nb * 2 + 4096);
+          if (nb > d_tail_csr_cap_) d_tail_csr_ = (int32_t*)res_.regrow(d_tail_csr_, d_tail_csr_cap_, nb * 2 + 4096, stream_);
+          int32_t* h = (int32_t*)h_tail_csr_[k].p;
           int32_t* hmap = h;
           int32_t* hoff = h + m;
           int32_t* hids = h + 2 * m + 1;
@@ -3508,35 +3320,37 @@ void Engine::fleet_setup(int32_t cap, bool lockstep) {
   HIP_OK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
   const char* pe = std::getenv("APM_COLL_PRIO");  // diagnostic: 0 = default-priority collective stream
   HIP_OK(hipStreamCreateWithPriority(&coll_stream_, hipStreamNonBlocking, pe && pe[0] == '0' ? prio_lo : prio_hi));
+  res_.adopt(coll_stream_);
   fleet_nranks_ = nranks;
   lockstep_ = lockstep;
   if (lockstep_) {
-    d_sync_ = (double*)dmalloc(64);
-    HIP_OK(hipHostMalloc((void**)&h_sync_, 256, hipHostMallocDefault));  // layout: engine.h
+    d_sync_ = (double*)res_.dmalloc(64);
+    res_.pin(h_sync_, 256);  // layout: engine.h
     std::memset(h_sync_, 0, 256);
-    HIP_OK(hipEventCreateWithFlags(&clock_ev_, hipEventDisableTiming));
-    for (hipEvent_t& e : bucket_ev_) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    clock_ev_ = res_.new_event();
+    for (hipEvent_t& e : bucket_ev_) e = res_.new_event();
     clock_pending_ = false;
   }
   fleet_cap_ = cap;
   fleet_elems_ = (size_t)cap * MAX_LAGS * NSTAT * 3;  // (capacity: a reload may change the LAG count)
   for (int i = 0; i < 2; ++i) {
-    fleet_buf_[i] = (double*)dmalloc(fleet_elems_ * 8);  // zeroed (and synchronised) by dmalloc
-    HIP_OK(hipEventCreateWithFlags(&fleet_ev_[i], hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&pack_ev_[i], hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&fb_src_ev_[i], hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&fb_ev_[i], hipEventDisableTiming));
+    fleet_buf_[i] = (double*)res_.dmalloc(fleet_elems_ * 8);  // zeroed (and synchronised) by dmalloc
+    fleet_ev_[i] = res_.new_event();
+    pack_ev_[i] = res_.new_event();
+    fb_src_ev_[i] = res_.new_event();
+    fb_ev_[i] = res_.new_event();
   }
   // fb rows: lowest priority (off every critical path; the output lane drains them)
   HIP_OK(hipStreamCreateWithPriority(&fb_stream_, hipStreamNonBlocking, prio_lo));
-  HIP_OK(hipHostMalloc((void**)&h_fb_total_, 16, hipHostMallocDefault));
+  res_.adopt(fb_stream_);
+  res_.pin(h_fb_total_, 16);
   fleet_rounds_ = fleet_posted_ = fleet_packed_ = 0;
   if (!lockstep_ && nranks > 1)
     throw std::runtime_error("fleet baseline across ranks needs lock-step rounds (node-wide service registry)");
-  d_reg_send_ = (uint8_t*)dmalloc(kRegBlock);
-  d_reg_recv_ = (uint8_t*)dmalloc(kRegBlock * (size_t)nranks);
-  HIP_OK(hipHostMalloc((void**)&h_reg_send_, kRegBlock, hipHostMallocDefault));
-  HIP_OK(hipHostMalloc((void**)&h_reg_recv_, kRegBlock * (size_t)nranks, hipHostMallocDefault));
+  d_reg_send_ = (uint8_t*)res_.dmalloc(kRegBlock);
+  d_reg_recv_ = (uint8_t*)res_.dmalloc(kRegBlock * (size_t)nranks);
+  res_.pin(h_reg_send_, kRegBlock);
+  res_.pin(h_reg_recv_, kRegBlock * (size_t)nranks);
   fleet_slot_.clear();
   reg_queued_.clear();
   reg_scan_series_ = 0;
@@ -3546,11 +3360,11 @@ void Engine::fleet_setup(int32_t cap, bool lockstep) {
   node_cool_ms_ = cfg_.cooldown_ms;
   if (node_mode_) {
     const size_t per = sizeof(NodeHdr) + (size_t)node_cap_ * sizeof(NodeCand);
-    d_node_send_ = (uint8_t*)dmalloc(per);
-    d_node_recv_ = (uint8_t*)dmalloc(per * (size_t)nranks);
-    HIP_OK(hipHostMalloc((void**)&h_node_send_, per, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&h_node_recv_, per * (size_t)nranks, hipHostMallocDefault));
-    HIP_OK(hipEventCreateWithFlags(&node_ev_, hipEventDisableTiming));
+    d_node_send_ = (uint8_t*)res_.dmalloc(per);
+    d_node_recv_ = (uint8_t*)res_.dmalloc(per * (size_t)nranks);
+    res_.pin(h_node_send_, per);
+    res_.pin(h_node_recv_, per * (size_t)nranks);
+    node_ev_ = res_.new_event();
   }
 }
 
@@ -3720,10 +3534,10 @@ void Engine::node_metrics_round() {
   // the next copy into it is queued
   std::lock_guard<std::mutex> g(nm_mu_);
   if (!d_nm_) {
-    d_nm_ = (double*)dmalloc(kNodeMetrics * 8);
-    HIP_OK(hipHostMalloc((void**)&h_nm_send_, kNodeMetrics * 8, hipHostMallocDefault));
-    HIP_OK(hipHostMalloc((void**)&h_nm_recv_, kNodeMetrics * 8, hipHostMallocDefault));
-    HIP_OK(hipEventCreateWithFlags(&nm_ev_, hipEventDisableTiming));
+    d_nm_ = (double*)res_.dmalloc(kNodeMetrics * 8);
+    res_.pin(h_nm_send_, kNodeMetrics * 8);
+    res_.pin(h_nm_recv_, kNodeMetrics * 8);
+    nm_ev_ = res_.new_event();
   } else if (nm_pending_) {
     coll_wait(nullptr, nm_ev_, "node metrics");  // the previous interval's: long done
     node_metrics_.assign(h_nm_recv_, h_nm_recv_ + kNodeMetrics);

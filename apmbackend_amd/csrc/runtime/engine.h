@@ -31,6 +31,7 @@
 #include "../kernels/kernel_api.h"
 #include "collective.h"
 #include "devjoin.h"
+#include "hipres.h"
 #include "join.h"
 
 namespace apm {
@@ -441,7 +442,7 @@ class Engine {
   hipStream_t stream() const { return stream_; }
   hipStream_t comm_stream() const { return stream_; }  // (the stats stream: callers flush() first)
   // HBM held: the engine's own buffers plus the device join's (which grow and shrink)
-  size_t device_bytes() const { return device_bytes_ + (dj_ ? dj_->device_bytes() : 0); }
+  size_t device_bytes() const { return res_.device_bytes() + (dj_ ? dj_->device_bytes() : 0); }
   // requestGC (util_methods.js:398-417 runGC, sent by apm_manager.js:475-512 on a memory
   // threshold): between batches, hand grow-only device memory back -- the join's key table and
   // need arena shrink to their live entries (>= their configured size), spill lists above 2x
@@ -506,7 +507,6 @@ class Engine {
   uint64_t roll_task_ = 0;
   bool roll_posted_ = false;
   std::mutex series_mu_;
-  std::mutex alloc_mu_;            // allocations_ / device_bytes_
   std::mutex roll_mu_;
   std::condition_variable roll_cv_;
   int64_t roll_done_round_ = -1;   // newest round whose alert candidates are queued (node mode)
@@ -516,8 +516,6 @@ class Engine {
   void format_rollover_text_host(int64_t edge_ts);  // fallback (|value| >= 1e13)
   void sync_format_tables();
   int32_t intern_name(const std::string& name);
-  void* regrow(void* old, size_t& cap, size_t need);
-  void dfree(void* p);
   void emit_bytes(int kind, const char* p, size_t n);
   // staging buffer k (st/fs 0, 1; fb 2, 3) is referenced by the sink until its holds are released
   void emit_bytes_held(int kind, const char* p, size_t n, int k, const uint32_t* row_off = nullptr,
@@ -558,8 +556,6 @@ class Engine {
   void out_wait_idle();
   void release_gather(int k, int64_t released);
   bool want(int k) const { return (cfg_.outputs >> k) & 1u; }
-  void* dmalloc(size_t bytes);
-  void* dmalloc_try(size_t bytes);
   void require_fresh(const char* what);
   void trace_event(const char* name, double t0, double t1, int tid);
   bool trace_on_ = false;
@@ -567,6 +563,9 @@ class Engine {
   std::vector<TraceEvent> trace_;
 
   EngineConfig cfg_;
+  // every device block, pinned block, event and stream of the engine (hipres.h): ~Engine
+  // quiesces, then releases them all at once
+  HipRes res_;
   hipStream_t stream_ = nullptr, parse_stream_ = nullptr;
   // fleet exchange + lock-step clocks: ONE communicator, driven only by the ingest thread on
   // coll_stream_, so every rank issues the same collectives in the same order (engine.cpp)
@@ -675,8 +674,7 @@ class Engine {
   hipEvent_t fb_src_ev_[2] = {nullptr, nullptr};   // moments slot all-reduced (coll stream)
   char* d_fb_out_[2] = {nullptr, nullptr};
   size_t fb_out_cap_[2] = {0, 0};
-  char* h_fb_out_[2] = {nullptr, nullptr};
-  size_t h_fb_cap_[2] = {0, 0};
+  PinnedBuf<char> h_fb_out_[2];
   uint32_t* h_fb_total_ = nullptr;
   hipEvent_t fb_ev_[2] = {nullptr, nullptr};
   uint64_t fb_task_[2] = {0, 0};
@@ -723,9 +721,6 @@ class Engine {
   std::string out_error_;
   double t_out_ms_ = 0;  // lane busy time (folded into metrics_ by flush)
   uint64_t formatted_bytes_lane_ = 0;  // st/fs bytes emitted by the lane (folded by flush)
-  size_t device_bytes_ = 0;
-  std::vector<void*> allocations_;
-  std::unordered_map<void*, size_t> alloc_bytes_;
 
   // files / servers / dictionaries
   std::vector<std::string> servers_;
@@ -785,32 +780,26 @@ class Engine {
   const DevJoinBatch* cur_dj_ = nullptr;       // stats thread: batch being processed
   uint64_t ring_low_pending_ = UINT64_MAX;     // ring base of the batch at the last min_pos launch
   unsigned long long* d_ring_min_ = nullptr;
-  unsigned long long* h_ring_min_ = nullptr;
-  unsigned long long* hd_ring_min_ = nullptr;  // device view (apm_export)
+  Mapped<unsigned long long> h_ring_min_;  // .d: device view (apm_export)
   int64_t* d_rel_n_ = nullptr;
-  int64_t* h_rel_n_ = nullptr;
-  int64_t* hd_rel_n_ = nullptr;
+  Mapped<int64_t> h_rel_n_;
   uint32_t* d_rel_lens_ = nullptr;
   uint32_t* d_rel_offs_ = nullptr;
   uint32_t* d_rel_fb_ = nullptr;  // released lines outside the GPU COPY encoder's domain (txcopy.hip)
-  uint32_t* h_rel_total_ = nullptr;            // [2]
-  uint32_t* hd_rel_total_ = nullptr;
+  Mapped<uint32_t> h_rel_total_;               // [2]
   char* d_rel_text_[2] = {nullptr, nullptr};
   size_t rel_text_cap_[2] = {0, 0};
   // pinned released-line text, a ring (the sink's spool writers hold a slot until written; with
   // two the release lane waited 1.7 ms per batch for them, profiles/r5_s)
-  char* h_rel_text_[REL_RING] = {};
-  size_t h_rel_text_cap_[REL_RING] = {};
+  PinnedBuf<char> h_rel_text_[REL_RING];
   int rel_ring_k_ = 0;  // stats thread
-  uint32_t* h_rel_offs_[2] = {nullptr, nullptr};  // pinned: the released rows' offsets (sink flush cuts)
-  size_t h_rel_offs_cap_[2] = {0, 0};
+  PinnedBuf<uint32_t> h_rel_offs_[2];  // pinned: the released rows' offsets (sink flush cuts)
   hipStream_t out_stream_ = nullptr;
   std::vector<int32_t> h_raw_series_;          // stats thread mirror of the raw -> series table
   // pinned staging of the stats thread's H2D uploads: kStage buffers used in rotation, each
   // reused only after its previous copy completed (an event), so no upload waits for the stream
   static constexpr int kStage = 32;  // > the uploads of a few batches (a batch with new series makes ~10)
-  char* h_stage_[kStage] = {};
-  size_t h_stage_cap_[kStage] = {};
+  PinnedBuf<char> h_stage_[kStage];
   size_t stage_max_ = 0;
   hipEvent_t stage_ev_[kStage] = {};
   int stage_k_ = 0;
@@ -882,8 +871,7 @@ class Engine {
   int32_t* d_spill_val_alt_ = nullptr;
   void* d_spill_tmp_ = nullptr;
   size_t spill_tmp_bytes_ = 0;
-  int32_t* h_spill_snap_ = nullptr;   // pinned [nslot_], written by K7 after every append
-  int32_t* hd_spill_snap_ = nullptr;  // its device alias
+  Mapped<int32_t> h_spill_snap_;      // pinned [nslot_], written by K7 after every append (through .d)
   // Spill sizing (no sample is ever dropped): spill_n[slot] <= spill_bound(slot) = the exact fill
   // of the newest completed append snapshot + every sample appended after it (any may spill), or
   // every sample appended since the slot was cleared.  spill_reserve() grows the lists before an
@@ -1042,8 +1030,7 @@ class Engine {
   int32_t* d_svc_ids_ = nullptr;
   size_t svc_off_cap_ = 0, svc_ids_cap_ = 0;
   int32_t svc_csr_n_ = -1, svc_csr_cap_ = -1;
-  int32_t* h_tail_csr_[2] = {nullptr, nullptr};  // per-batch CSR of the series added since the snapshot (pinned, alternating)
-  size_t tail_csr_cap_[2] = {0, 0};
+  PinnedBuf<char> h_tail_csr_[2];  // per-batch CSR (int32) of the series added since the snapshot (pinned, alternating)
   hipEvent_t tail_csr_ev_[2] = {nullptr, nullptr};
   int tail_k_ = 0;
   int32_t* d_tail_csr_ = nullptr;
@@ -1062,14 +1049,10 @@ class Engine {
   // alerts
   AlertRec* d_alerts_ = nullptr;
   int32_t* d_n_alerts_ = nullptr;
-  AlertRec* h_alerts_ = nullptr;
-  WinStat* h_alert_win_ = nullptr;  // pinned; candidate rows written by apm_alert_gather
-  ZOut* h_alert_z_ = nullptr;       // pinned
-  int32_t* h_n_alerts_ = nullptr;
-  AlertRec* hd_alerts_ = nullptr;  // device views of the four pinned buffers above
-  WinStat* hd_alert_win_ = nullptr;
-  ZOut* hd_alert_z_ = nullptr;
-  int32_t* hd_n_alerts_ = nullptr;
+  Mapped<AlertRec> h_alerts_;     // pinned, each with its device view (.d)
+  Mapped<WinStat> h_alert_win_;   // candidate rows written by apm_alert_gather
+  Mapped<ZOut> h_alert_z_;
+  Mapped<int32_t> h_n_alerts_;
   hipEvent_t ev_alerts_ = nullptr;  // the rollover's candidates are in host memory
   hipEvent_t ev_release_ = nullptr; // the rollover's device release (K9 part 1) exported its counts
   std::unordered_map<std::string, double> last_alert_;  // cooldown key -> alertTimestamp
@@ -1078,9 +1061,8 @@ class Engine {
   double* d_cool_t_ = nullptr;
   std::unordered_map<uint64_t, std::vector<int32_t>> cool_series_;
   double roll_now_ = 0;                    // `now` of the rollover in flight (K11 and the decision)
-  int32_t* h_cool_idx_ = nullptr;          // pinned staging of cooldown updates
-  double* h_cool_val_ = nullptr;
-  size_t cool_cap_ = 0;
+  PinnedBuf<int32_t> h_cool_idx_;          // pinned staging of cooldown updates
+  PinnedBuf<double> h_cool_val_;
   hipEvent_t cool_ev_ = nullptr;
   uint64_t cool_key_of(int32_t s) const;   // (series_mu_ held, or the series_ owner)
   void cool_mark(const std::vector<std::pair<uint64_t, double>>& wins, hipStream_t st);
@@ -1182,8 +1164,7 @@ class Engine {
   // buffer: the sink's spool writers hold a slot until written (zero-copy COPY rows), and with
   // the two device slots the lane waited for the writes of the batch before last (0.42 ms per
   // batch, profiles/r5_q/service_trace_summary.txt).
-  char* h_fmt_ring_[FMT_RING] = {};
-  size_t h_fmt_ring_cap_[FMT_RING] = {};
+  PinnedBuf<char> h_fmt_ring_[FMT_RING];
   int fmt_ring_k_ = 0;  // stats thread
   // K12's LDS stage: bytes of an average 64-line block of the longer stream in the last batch
   std::atomic<uint32_t> fmt_block_bytes_{0};
@@ -1192,13 +1173,11 @@ class Engine {
     if (a) fmt_block_bytes_.store((uint32_t)std::min<size_t>(a * 64, 1u << 20), std::memory_order_relaxed);
   }
   int fmt_k_ = 0;
-  uint32_t* h_fmt_meta_ = nullptr;               // pinned: per slot k, [4k] st total, [4k+1] fs total
+  Mapped<uint32_t> h_fmt_meta_;                  // pinned: per slot k, [4k] st total, [4k+1] fs total
   // pinned: per slot k, the fs row offsets of the last format (K12's scan), so a COPY sink cuts
   // its flushes without scanning the text
-  uint32_t* h_fs_off_[2] = {nullptr, nullptr};
-  size_t h_fs_off_cap_[2] = {0, 0};
+  PinnedBuf<uint32_t> h_fs_off_[2];
   size_t fs_rows_[2] = {0, 0};
-  uint32_t* hd_fmt_meta_ = nullptr;
 
   // K15 lh rows (hist.hip), allocated when the stream is on: every bucket is reported once, at the
   // rollover that first has it in the K8 window.  Two device / pinned slots, as for st / fs.
@@ -1208,9 +1187,8 @@ class Engine {
   size_t hist_tmp_bytes_ = 0;
   char* d_hist_out_[2] = {nullptr, nullptr};
   size_t hist_out_cap_[2] = {0, 0};
-  char* h_hist_text_[2] = {nullptr, nullptr};  // pinned (output lane)
-  size_t h_hist_text_cap_[2] = {0, 0};
-  uint32_t *h_hist_total_ = nullptr, *hd_hist_total_ = nullptr;  // pinned [2]: bytes of slot k's rows
+  PinnedBuf<char> h_hist_text_[2];  // pinned (output lane)
+  Mapped<uint32_t> h_hist_total_;   // pinned [2]: bytes of slot k's rows
   hipEvent_t ev_hist_[2] = {nullptr, nullptr};
   uint64_t hist_task_[2] = {0, 0};
   int hist_k_ = 0;

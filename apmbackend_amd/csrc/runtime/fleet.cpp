@@ -165,7 +165,7 @@ bool Engine::fleet_emit_fb(int slot) {
   if (fb_chars_up_ < h_fb_chars_.size()) {
     if (h_fb_chars_.size() > fb_chars_cap_) {
       HIP_OK(hipStreamSynchronize(fb_stream_));  // (regrow frees the buffer the stream may read)
-      d_fb_chars_ = (char*)regrow(d_fb_chars_, fb_chars_cap_, h_fb_chars_.size() * 2 + 4096);
+      d_fb_chars_ = (char*)res_.regrow(d_fb_chars_, fb_chars_cap_, h_fb_chars_.size() * 2 + 4096, stream_);
       fb_chars_up_ = 0;
     }
     HIP_OK(hipMemcpyAsync(d_fb_chars_ + fb_chars_up_, h_fb_chars_.data() + fb_chars_up_,
@@ -176,7 +176,7 @@ bool Engine::fleet_emit_fb(int slot) {
   if (fb_slots_up_ < n_all) {
     if ((size_t)n_all * 8 > fb_names_cap_) {
       HIP_OK(hipStreamSynchronize(fb_stream_));
-      d_fb_names_ = (int32_t*)regrow(d_fb_names_, fb_names_cap_, (size_t)n_all * 16 + 4096);
+      d_fb_names_ = (int32_t*)res_.regrow(d_fb_names_, fb_names_cap_, (size_t)n_all * 16 + 4096, stream_);
       fb_slots_up_ = 0;
     }
     HIP_OK(hipMemcpyAsync(d_fb_names_ + 2 * fb_slots_up_, h_fb_names_.data() + 2 * fb_slots_up_,
@@ -191,14 +191,14 @@ bool Engine::fleet_emit_fb(int slot) {
   const uint32_t blocks = apm_fleet_format_blocks(rows);
   if (blocks > fb_status_n_) {
     HIP_OK(hipStreamSynchronize(fb_stream_));
-    if (d_fb_status_) dfree(d_fb_status_);
+    if (d_fb_status_) res_.dfree(d_fb_status_);
     fb_status_n_ = std::max<uint32_t>(blocks * 2, apm_fleet_format_blocks(2 * fleet_cap_ * MAX_LAGS));
-    d_fb_status_ = (unsigned long long*)dmalloc((size_t)fb_status_n_ * 8 + 64);
+    d_fb_status_ = (unsigned long long*)res_.dmalloc((size_t)fb_status_n_ * 8 + 64);
   }
   size_t longest = 0;
   for (size_t i = 1; i < h_fb_names_.size(); i += 2) longest = std::max<size_t>(longest, (size_t)h_fb_names_[i]);
   const size_t cap_bytes = (size_t)rows * (260 + 2 * longest) + 64;
-  if (cap_bytes > fb_out_cap_[k]) d_fb_out_[k] = (char*)regrow(d_fb_out_[k], fb_out_cap_[k], cap_bytes);
+  if (cap_bytes > fb_out_cap_[k]) d_fb_out_[k] = (char*)res_.regrow(d_fb_out_[k], fb_out_cap_[k], cap_bytes, stream_);
   // the exchange's all-reduce (coll stream) before the rows read the merged moments
   HIP_OK(hipStreamWaitEvent(fb_stream_, fb_src_ev_[slot], 0));
   FleetFormatArgs fa{};
@@ -227,11 +227,7 @@ bool Engine::fleet_emit_fb(int slot) {
     HIP_OK(hipEventSynchronize(fb_ev_[k]));
     const size_t total = h_fb_total_[k];
     wait_fmt_holds(2 + k);  // the sink still writes from this buffer (zero-copy COPY rows)
-    if (total > h_fb_cap_[k]) {
-      if (h_fb_out_[k]) HIP_OK(hipHostFree(h_fb_out_[k]));
-      h_fb_cap_[k] = total * 3 / 2 + (1 << 16);
-      HIP_OK(hipHostMalloc((void**)&h_fb_out_[k], h_fb_cap_[k], hipHostMallocDefault));
-    }
+    res_.reserve(h_fb_out_[k], total, total * 3 / 2 + (1 << 16));
     if (total) {
       HIP_OK(hipMemcpy(h_fb_out_[k], dst, total, hipMemcpyDeviceToHost));
       uint64_t rows = 0;  // (memchr: vectorised; a byte loop over 18 MB cost ~3 ms of this lane)

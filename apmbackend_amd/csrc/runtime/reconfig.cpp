@@ -114,16 +114,16 @@ void Engine::apply_reconfig(const ReconfigSpec& r) {
       }
       // a new LAG: empty history (len 0; the ring head is the shared rollover index mod LAG)
       LagState& L = nl[i];
-      L.ring = dmalloc((size_t)NSTAT * r.lags[i] * S * cfg_.ring_bytes);
-      L.len = (int32_t*)dmalloc((size_t)S * 4);
-      L.sum = (double*)dmalloc((size_t)NSTAT * S * 8);
-      L.comp = (double*)dmalloc((size_t)NSTAT * S * 8);
-      L.sumsq = (double*)dmalloc((size_t)NSTAT * S * 8);
-      L.sqcomp = (double*)dmalloc((size_t)NSTAT * S * 8);
-      L.cnt = (int32_t*)dmalloc((size_t)NSTAT * S * 4);
-      L.thr = (double*)dmalloc((size_t)S * 8);
-      L.infl = (double*)dmalloc((size_t)S * 8);
-      L.out = (ZOut*)dmalloc((size_t)S * sizeof(ZOut));
+      L.ring = res_.dmalloc((size_t)NSTAT * r.lags[i] * S * cfg_.ring_bytes);
+      L.len = (int32_t*)res_.dmalloc((size_t)S * 4);
+      L.sum = (double*)res_.dmalloc((size_t)NSTAT * S * 8);
+      L.comp = (double*)res_.dmalloc((size_t)NSTAT * S * 8);
+      L.sumsq = (double*)res_.dmalloc((size_t)NSTAT * S * 8);
+      L.sqcomp = (double*)res_.dmalloc((size_t)NSTAT * S * 8);
+      L.cnt = (int32_t*)res_.dmalloc((size_t)NSTAT * S * 4);
+      L.thr = (double*)res_.dmalloc((size_t)S * 8);
+      L.infl = (double*)res_.dmalloc((size_t)S * 8);
+      L.out = (ZOut*)res_.dmalloc((size_t)S * sizeof(ZOut));
       // the alerts stage's leaky counters are keyed by LAG value and never deleted: a LAG that
       // comes back resumes the counters it had when it was removed
       auto st = counter_stash_.find(r.lags[i]);
@@ -131,7 +131,7 @@ void Engine::apply_reconfig(const ReconfigSpec& r) {
         L.counter = st->second;
         counter_stash_.erase(st);
       } else {
-        L.counter = (int32_t*)dmalloc((size_t)S * 4);
+        L.counter = (int32_t*)res_.dmalloc((size_t)S * 4);
       }
     }
     for (int o = 0; o < cfg_.n_lags; ++o) {
@@ -139,8 +139,8 @@ void Engine::apply_reconfig(const ReconfigSpec& r) {
       LagState& L = lag_[o];
       for (void* p : {L.ring, (void*)L.len, (void*)L.sum, (void*)L.comp, (void*)L.sumsq, (void*)L.sqcomp,
                       (void*)L.cnt, (void*)L.thr, (void*)L.infl, (void*)L.out})
-        dfree(p);
-      if (counter_stash_.count(cfg_.lags[o])) dfree(counter_stash_[cfg_.lags[o]]);
+        res_.dfree(p);
+      if (counter_stash_.count(cfg_.lags[o])) res_.dfree(counter_stash_[cfg_.lags[o]]);
       counter_stash_[cfg_.lags[o]] = L.counter;
     }
     for (int l = 0; l < MAX_LAGS; ++l) lag_[l] = l < r.n_lags ? nl[l] : LagState{};
