@@ -35,6 +35,16 @@ void register_dbsink(py::module_& m);
 
 namespace {
 
+// device memory of a test hook: freed on every way out, a throwing HIP_OK included
+struct DevMem {
+  void* p = nullptr;
+  explicit DevMem(size_t bytes) { HIP_OK(hipMalloc(&p, std::max<size_t>(bytes, 8))); }
+  ~DevMem() { if (p) (void)hipFree(p); }
+  DevMem(const DevMem&) = delete;
+  DevMem& operator=(const DevMem&) = delete;
+  template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
 template <class T>
 T get(const py::dict& d, const char* k, T dflt) {
   if (d.contains(k)) return d[k].cast<T>();
@@ -677,23 +687,86 @@ PYBIND11_MODULE(_apm_native, m) {
     }
     return true;
   });
-  m.def("gpu_to_fixed", [](const std::vector<double>& xs, int f) {
-    // K12 number printer on the device (test hook): nf(x, f) per value
+  m.def("gpu_to_fixed", [](const std::vector<double>& xs, int f, const std::string& mode) {
+    // K12 number printer on the device (test hook), per value: "nf" nf(x, f), "json" / "copy"
+    // js_fixed(x, f) as a JSON number / a COPY field
+    const int md = mode == "nf" ? 0 : mode == "json" ? 1 : mode == "copy" ? 2 : -1;
+    if (md < 0) throw std::invalid_argument("gpu_to_fixed: mode is nf, json or copy");
+    if (f != 1 && f != 2) throw std::invalid_argument("gpu_to_fixed: f is 1 or 2");
     const int n = (int)xs.size();
-    double* dx = nullptr;
-    char* dout = nullptr;
     std::vector<char> h((size_t)n * 32);
-    HIP_OK(hipMalloc(&dx, std::max(1, n) * 8));
-    HIP_OK(hipMalloc(&dout, std::max<size_t>(32, h.size())));
-    HIP_OK(hipMemcpy(dx, xs.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    apm_format_fixed_batch(dx, n, f, dout, 0);
-    HIP_OK(hipMemcpy(h.data(), dout, h.size(), hipMemcpyDeviceToHost));
-    HIP_OK(hipFree(dx));
-    HIP_OK(hipFree(dout));
+    DevMem dx((size_t)n * 8), dout(h.size());
+    HIP_OK(hipMemcpy(dx.p, xs.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    apm_format_fixed_batch(dx.as<double>(), n, f, md, dout.as<char>(), 0);
+    HIP_OK(hipMemcpy(h.data(), dout.p, h.size(), hipMemcpyDeviceToHost));
     std::vector<std::string> r;
     for (int i = 0; i < n; ++i) r.emplace_back(h.data() + (size_t)i * 32);
     return r;
-  });
+  }, py::arg("xs"), py::arg("f"), py::arg("mode") = "nf");
+  m.def("gpu_fleet_rows", [](const std::vector<double>& moments, const std::vector<std::string>& names,
+                             const std::vector<int32_t>& lag_values, int32_t slot_lo, int32_t n_slots, bool copy,
+                             int64_t edge_ts) {
+    // the fb row formatter alone (test hook): moments [slot][lag][stat]{n, sum, sum of squares} of
+    // every slot in `names`, rows of slots [slot_lo, slot_lo + n_slots)
+    const int n_lags = (int)lag_values.size();
+    if (n_lags < 1 || n_lags > MAX_LAGS) throw std::invalid_argument("gpu_fleet_rows: 1..MAX_LAGS lag values");
+    if (slot_lo < 0 || n_slots < 0 || (size_t)slot_lo + (size_t)n_slots > names.size())
+      throw std::invalid_argument("gpu_fleet_rows: slots outside names");
+    if (moments.size() != names.size() * (size_t)n_lags * NSTAT * 3)
+      throw std::invalid_argument("gpu_fleet_rows: moments hold names x lags x 3 x 3 doubles");
+    std::vector<int32_t> nm;
+    std::string chars;
+    size_t longest = 0;
+    for (const std::string& s : names) {
+      nm.push_back((int32_t)chars.size());
+      nm.push_back((int32_t)s.size());
+      chars += s;
+      longest = std::max(longest, s.size());
+    }
+    const int32_t rows = n_slots * n_lags;
+    const uint32_t blocks = apm_fleet_format_blocks(rows);
+    const size_t cap = apm_fleet_out_bound(rows, longest);
+    // `cap` holds any row the grammar allows (apm_fleet_out_bound), so the kernels cannot write
+    // past it; the check of `total` below only guards the copy back
+    DevMem m_mom(moments.size() * 8), m_nm(nm.size() * 4), m_out(cap);
+    DevMem m_chars(chars.size() + 64);                // (16-byte over-reading name loads)
+    DevMem m_status((size_t)blocks * 8 + 64);         // [blocks] wave totals, then {total, fallback}
+    double* d_mom = m_mom.as<double>();
+    int32_t* d_nm = m_nm.as<int32_t>();
+    char *d_chars = m_chars.as<char>(), *d_out = m_out.as<char>();
+    unsigned long long* d_status = m_status.as<unsigned long long>();
+    HIP_OK(hipMemset(d_chars, 0, chars.size() + 64));
+    HIP_OK(hipMemset(d_status, 0, (size_t)blocks * 8 + 64));
+    HIP_OK(hipMemcpy(d_mom, moments.data(), moments.size() * 8, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_nm, nm.data(), nm.size() * 4, hipMemcpyHostToDevice));
+    if (!chars.empty()) HIP_OK(hipMemcpy(d_chars, chars.data(), chars.size(), hipMemcpyHostToDevice));
+    FleetFormatArgs fa{};
+    fa.moments = d_mom;
+    fa.names = reinterpret_cast<const int2*>(d_nm);
+    fa.chars = d_chars;
+    fa.slot_lo = slot_lo;
+    fa.n_slots = n_slots;
+    fa.n_lags = n_lags;
+    std::vector<int> order(n_lags);
+    for (int l = 0; l < n_lags; ++l) order[l] = l;
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return lag_values[a] < lag_values[b]; });
+    for (int l = 0; l < n_lags; ++l) { fa.lag_order[l] = order[l]; fa.lag_value[l] = lag_values[l]; }
+    fa.edge_ts = edge_ts;
+    fa.copy = copy ? 1 : 0;
+    fa.ts_len = Engine::pg_timestamp(edge_ts, fa.ts);
+    fa.status = d_status;
+    fa.total = reinterpret_cast<uint32_t*>(d_status + blocks);
+    fa.out = d_out;
+    fa.fallback = reinterpret_cast<int32_t*>(d_status + blocks) + 1;
+    apm_fleet_format(&fa, 0);
+    uint32_t total = 0;
+    HIP_OK(hipMemcpy(&total, fa.total, 4, hipMemcpyDeviceToHost));
+    if (total > cap) throw std::runtime_error("gpu_fleet_rows: rows longer than the output bound");
+    std::string out(total, '\0');
+    if (total) HIP_OK(hipMemcpy(&out[0], d_out, total, hipMemcpyDeviceToHost));
+    return py::bytes(out);
+  }, py::arg("moments"), py::arg("names"), py::arg("lag_values"), py::arg("slot_lo"), py::arg("n_slots"),
+     py::arg("copy"), py::arg("edge_ts"));
   m.def("js_to_fixed", [](double x, int f) { return js::to_fixed(x, f); });
   m.def("js_num_str", [](double x) { return js::num_str(x); });
   m.def("js_parse_int", [](const std::string& s) { return js::parse_int(s); });

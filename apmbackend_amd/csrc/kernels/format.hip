@@ -298,12 +298,14 @@ __global__ __launch_bounds__(FMT_WAVE_LINES) void k_fleet_rows(FleetFormatArgs a
   if (lds) wave_copy_out(stage, a.out, g0, g1);
 }
 
-__global__ void k_fixed_batch(const double* x, int n, int f, char* out) {
+// mode 0: nf(x, f); 1: js_fixed as a JSON number; 2: js_fixed as a COPY field
+__global__ void k_fixed_batch(const double* x, int n, int f, int mode, char* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   bool fb = false;
   OutT<true> o(out + (size_t)i * 32);
-  o.fixed(x[i], f, fb);
+  if (mode == 0) o.fixed(x[i], f, fb);
+  else o.js_fixed(x[i], f, mode == 1, fb);
   o.c('\0');
   o.finish();
   if (fb) {
@@ -343,13 +345,24 @@ int apm_format_plan(FormatArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stre
   return fmt_scan_lens(sc, a->fs_len, a->fs_off, (size_t)a->n * a->n_lags + 1, stream);
 }
 
-// Test hook: nf(x[i], f) into 32-byte NUL-terminated slots.
-void apm_format_fixed_batch(const double* d_x, int n, int f, char* d_out, hipStream_t stream) {
-  if (n > 0) hipLaunchKernelGGL(k_fixed_batch, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, f, d_out);
+// Test hook: nf(x[i], f) (mode 0) or js_fixed(x[i], f, json = mode == 1) (modes 1, 2) into 32-byte
+// NUL-terminated slots; "<fallback>" where the printer raised its inexact flag.
+void apm_format_fixed_batch(const double* d_x, int n, int f, int mode, char* d_out, hipStream_t stream) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_fixed_batch, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, f, mode, d_out);
 }
 
 uint32_t apm_fleet_format_blocks(int32_t n_rows) {
   return (uint32_t)((std::max<int32_t>(n_rows, 1) + FLEET_RPW - 1) / FLEET_RPW);
+}
+
+// Bytes `rows` fb rows can take for names of at most `longest` bytes.  Wire: fb| 3, edge_ts 20, lag
+// 10, n 20, six numbers of at most 25 characters (-, 21 digits, .0 / 17 digits and an exponent),
+// 10 separators and the newline: 214 + name.  COPY: timestamp 31, lag 10, n 20, 4 tabs, 78 bytes
+// of JSON keys, braces and newline 3, six numbers of at most 24: 290 + the name with every byte
+// escaped.
+size_t apm_fleet_out_bound(int32_t rows, size_t longest) {
+  return (size_t)std::max<int32_t>(rows, 0) * (296 + 2 * longest) + 64;
 }
 
 // two launches; afterwards *a->total holds the bytes written (device)

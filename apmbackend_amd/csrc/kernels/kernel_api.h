@@ -265,7 +265,7 @@ void apm_zscore_warm(apm::ZArgs* a, int dtype_bytes, int fill, uint64_t seed, co
                      hipStream_t stream);
 void apm_server_rollup(apm::RollupArgs* a, hipStream_t stream);
 size_t apm_format_tmp_bytes(int32_t n_max);
-void apm_format_fixed_batch(const double* d_x, int n, int f, char* d_out, hipStream_t stream);
+void apm_format_fixed_batch(const double* d_x, int n, int f, int mode, char* d_out, hipStream_t stream);
 int apm_format_plan(apm::FormatArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_format_write(apm::FormatArgs* a, hipStream_t stream);
 void apm_alert_eval(apm::AlertArgs* a, hipStream_t stream);
@@ -273,6 +273,8 @@ void apm_alert_eval(apm::AlertArgs* a, hipStream_t stream);
 void apm_scatter_f64(double* dst, const int32_t* idx, const double* val, int32_t n, hipStream_t stream);
 // blocks of the one-pass fb formatter for `n_rows` rows (the status array's length)
 uint32_t apm_fleet_format_blocks(int32_t n_rows);
+// capacity of FleetFormatArgs::out for `rows` rows and names of at most `longest` bytes
+size_t apm_fleet_out_bound(int32_t rows, size_t longest);
 void apm_fleet_format(apm::FleetFormatArgs* a, hipStream_t stream);
 // after K11: the candidate count (clamped to max_n), the candidates and -- rows != 0 -- their window
 // stats and candidate-LAG z-score rows, written into host-mapped pinned buffers (device pointers

@@ -197,7 +197,7 @@ bool Engine::fleet_emit_fb(int slot) {
   }
   size_t longest = 0;
   for (size_t i = 1; i < h_fb_names_.size(); i += 2) longest = std::max<size_t>(longest, (size_t)h_fb_names_[i]);
-  const size_t cap_bytes = (size_t)rows * (260 + 2 * longest) + 64;
+  const size_t cap_bytes = apm_fleet_out_bound(rows, longest);
   if (cap_bytes > fb_out_cap_[k]) d_fb_out_[k] = (char*)res_.regrow(d_fb_out_[k], fb_out_cap_[k], cap_bytes, stream_);
   // the exchange's all-reduce (coll stream) before the rows read the merged moments
   HIP_OK(hipStreamWaitEvent(fb_stream_, fb_src_ev_[slot], 0));

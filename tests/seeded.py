@@ -572,3 +572,236 @@ def zscore_reference():
                      for L in Z_LAGS} for k in order + [TRIGGER]}
         _Z_REF["ref"] = (list(sd.st), list(sd.fs), final)
     return _Z_REF["ref"]
+
+
+# ------------------------------------------------------------------------------- K12 case table
+# Whole st / fs lines from a seeded engine (tests/test_format_seeded_gpu.py).  The point is line
+# layout, so no printed value depends on how an expression is evaluated: window samples are
+# int32 (exact sums, exact halves), every LAG 2 history is [v, v] (0 + v + v and / 2 are exact),
+# THRESHOLD is 0 (lb = ub = mean - 0 * sd = mean) and INFLUENCE is 0 or 1 (the stored value is x
+# or the last entry, exactly).  The other LAGs hold constant half-multiples or stay short.
+
+FMT_WAVE_LINES = 64                              # format.hip: lines per block of the write pass
+FMT_STAGES = (8192, 12288, 16384, 24576)         # format.hip: k_format_write's LDS stages
+FMT_LAGS = {1: (2,), 2: (2, 5), 3: (2, 5, 9)}
+FMT_WIDE = -math.nextafter(1e21, 0.0)            # toFixed(1) prints '-', 21 digits, '.0': 24 characters
+FMT_WIDE_JSON = -math.nextafter(2.0 ** 127, 0.0)  # String(x) prints 23 characters, the widest exact one
+
+
+def fmt_stage(hint):
+    """apm_format_write: the stage for the hint note_fmt_block left (0: none yet)."""
+    want = hint or 12288
+    return 8192 if want <= 7168 else 12288 if want <= 12800 else 16384 if want <= 16896 else 24576
+
+
+def fmt_hint(st_bytes, st_lines, fs_bytes, fs_lines):
+    """Engine::note_fmt_block: 64 average lines of the longer stream (None: the hint stays)."""
+    a = max(st_bytes // st_lines if st_lines else 0, fs_bytes // fs_lines if fs_lines else 0)
+    return min(a * 64, 1 << 20) if a else None
+
+
+def fmt_history_pool():
+    """The boundary values of the number-printer table a history can hold: finite, outside every
+    flag domain, v + v finite; -0.0 left out (0 + -0 + -0 is +0: the mean would not be v)."""
+    import format_cases as F
+    out = []
+    for x in F.number_table()[:4000]:
+        if x != x or abs(x) >= 2.0 ** 126 or (x == 0 and math.copysign(1, x) < 0):
+            continue
+        if any(F.may_flag(x, 1, m) for m in F.MODES):
+            continue
+        out.append(x)
+    return out
+
+
+WINDOWS = [
+    [INT32_MAX, INT32_MAX, INT32_MAX],            # avg 2147483647.0: nn = 21474836470 (64-bit split_fixed)
+    [-INT32_MAX, -INT32_MAX],                     # the most negative sample a window holds
+    [INT32_MAX, INT32_MAX - 1],                   # 2147483646.5
+    [ELAPSED_NAN, 7, 3],                          # NaN window: avg undefined
+    [],                                           # active, nothing to count: all undefined
+    [5], [1, 2, 4], [429496729, 429496730], [-1, 0, 1], [99, 100, 101, 1000000],
+    [INT32_MAX, -INT32_MAX, 1], [12, 13],
+]
+
+
+class FormatCase:
+    """One engine: n series (the trigger last), n_lags LAGs, two rollovers."""
+
+    def __init__(self, label, n, n_lags, svc_len, inactive=(), copy=False, wide=(), specials=False):
+        assert n >= 1
+        self.label, self.n, self.n_lags, self.copy = label, n, n_lags, copy
+        self.lags = FMT_LAGS[n_lags]
+        pool = fmt_history_pool()
+        C0 = seeded_cfg(lags=tuple((L, 0.0, 0.0) for L in self.lags))
+        labels = window_labels(C0)
+        mid = labels[len(labels) // 2]  # inside the window of both rollovers
+        self.order, self.buckets, self.histories, self.overrides, self.hist_v = [], {}, {}, {}, {}
+        seen = set()
+        for i in range(n - 1):
+            L = svc_len(i)
+            tag = f"{i:03d}"
+            svc = (tag + "abcdefghijklmnopqrstuvwxyz" * (L // 26 + 1))[:max(L, 3)]
+            if L < 3 and "Q7"[:L] not in seen:  # an empty, a one- and a two-character name, once each
+                svc = "Q7"[:L]
+            if specials and i % 9 == 4 and L >= 12:  # all four COPY escapes; the st rows hold them raw
+                svc = svc[:3] + "\n\\" + svc[5:7] + "\t" + svc[8:10] + "\r" + svc[11:]
+            assert svc not in seen
+            seen.add(svc)
+            k = (SERVER, svc)
+            self.order.append(k)
+            if i in inactive:
+                continue
+            self.buckets[k] = {mid: list(WINDOWS[i % len(WINDOWS)])}
+            if i in wide:
+                # every number as wide as this line can print it: the most negative window, a
+                # negative mean (24 characters, lb / ub undefined), positive ones (mean = lb = ub)
+                self.buckets[k] = {mid: [-INT32_MAX, -INT32_MAX]}
+                w = -(FMT_WIDE_JSON if copy else FMT_WIDE)
+                v3 = (-w, w, w)
+            else:
+                v3 = tuple(pool[(i * 3 + j * 131) * 7 % len(pool)] for j in range(3))
+            self.hist_v[k] = v3
+            h = {2: tuple([v, v] for v in v3)}
+            for L_ in self.lags[1:]:  # constant half-multiples at full length, or one entry short
+                c = 0.5 * ((i * 11 + L_) % 255)
+                h[L_] = tuple([c] * (L_ if i % 3 else L_ - 2) for _ in range(3))
+            self.histories[k] = h
+            if i % 2:
+                self.overrides[svc] = {str(L_): {"INFLUENCE": 1.0} for L_ in self.lags}
+        self.order.append(TRIGGER)
+
+    def cfg(self):
+        return seeded_cfg(lags=tuple((L, 0.0, 0.0) for L in self.lags), overrides=self.overrides, max_series=256)
+
+    def reference(self):
+        """[(st rows, fs wire rows)] of the two rollovers from the oracle."""
+        if not hasattr(self, "_ref"):
+            sd = Seeded(self.cfg(), self.order, self.buckets, self.histories, device=False)
+            ref = []
+            for _ in range(2):
+                a, b = len(sd.st), len(sd.fs)
+                sd.step()
+                ref.append((sd.st[a:], sd.fs[b:]))
+            self._ref = ref
+        return self._ref
+
+    def expected_rows(self, r):
+        """(st rows, fs rows) of rollover r as bytes, each with its line feed: the fs wire rows, or
+        what the Python COPY encoder (sinks.copy_encode_lines) makes of them.  (A name may hold a
+        line feed itself, so rows are kept as a list and never recovered by splitting.)"""
+        from apmbackend_amd.runtime import sinks
+        st, fs = self.reference()[r]
+        st_rows = [(l + "\n").encode() for l in st]
+        if self.copy:
+            rows = sinks.copy_encode_lines(fs)["fs"]
+            assert len(rows) == len(fs)
+            return st_rows, [x.encode() for x in rows]
+        return st_rows, [(l + "\n").encode() for l in fs]
+
+    def expected(self, r):
+        """(st bytes, fs bytes) of rollover r."""
+        st, fs = self.expected_rows(r)
+        return b"".join(st), b"".join(fs)
+
+    def active(self, r):
+        """Emission positions with lines at rollover r (the trigger from the second one on)."""
+        return [i for i, k in enumerate(self.order) if k in self.buckets or (k == TRIGGER and r > 0)]
+
+    def line_lens(self, r):
+        """(st, fs) line bytes per emission position / (position, LAG), 0 for an inactive series."""
+        st_rows, fs_rows = self.expected_rows(r)
+        act = set(self.active(r))
+        st_it, fs_it = iter(st_rows), iter(fs_rows)
+        st, fs = [], []
+        for i in range(self.n):
+            st.append(len(next(st_it)) if i in act else 0)
+            fs += [len(next(fs_it)) if i in act else 0 for _ in range(self.n_lags)]
+        assert next(st_it, None) is None and next(fs_it, None) is None
+        return st, fs
+
+    def stage(self, r):
+        """The LDS stage rollover r uses: 12 KB without a hint, then from the bytes before it."""
+        hint = 0
+        for q in range(r):
+            st, fs = self.line_lens(q)
+            hint = fmt_hint(sum(st), len(st), sum(fs), len(fs)) or hint
+        return fmt_stage(hint)
+
+    def flag_count(self):
+        """What metrics()["format_fallbacks"] must read after the two rollovers.  k_format_len adds
+        one per lane that printed any value inside a flag domain of the number printer
+        (format_cases.may_flag), and lane j prints st line j and fs line j: the st lines here
+        hold no such value, so that is the number of fs lines holding one.  Read off the wire
+        rows: toFixed's digits are its integer n.  COPY rows flag n >= 10^15 below 2^53; nothing
+        here reaches 2^127, the only flag of wire rows."""
+        k = 0
+        for _st, fs in self.reference():
+            for line in fs:
+                f = line.split("|")
+                hit = False
+                for tok in [f[5]] + [t for g in f[6:9] for t in g.split(":")[:4]]:
+                    if tok == "undefined" or "e" in tok:  # (from 1e21 toFixed prints String(x): exact)
+                        continue
+                    assert abs(float(tok)) < 2.0 ** 127
+                    n = int(tok.replace("-", "").replace(".", ""))
+                    hit = hit or (self.copy and abs(float(tok)) < 2.0 ** 53 and n >= 10 ** 15)
+                k += hit
+        return int(k)
+
+    def max_name_len(self):
+        return max(len(a.encode()) + len(b.encode()) for a, b in self.order)
+
+    def name_offsets(self):
+        """Engine::intern_name: names appended to one table in first-use order, each once."""
+        off, at = {}, 0
+        for k in self.order:
+            for nm in k:
+                if nm not in off:
+                    off[nm] = at
+                    at += len(nm.encode())
+        return off
+
+
+def block_ranges(lens, base=0):
+    """(g0, g1) of every 64-line block of a stream whose line bytes are `lens`."""
+    off = [base]
+    for x in lens:
+        off.append(off[-1] + x)
+    return [(off[j], off[min(j + FMT_WAVE_LINES, len(lens))]) for j in range(0, len(lens), FMT_WAVE_LINES)]
+
+
+def block_is_direct(g0, g1, stage):
+    """k_format_write's test, on offsets inside the stream as the kernel takes them.  The stream
+    itself need not start on a dword: fs_out lies st_cap bytes into the buffer, so with
+    st_cap % 4 != 0 the stage's copy-out stores dwords that are unaligned in memory.  The
+    n65_cap0..3 cases exist to show that the bytes come out right for each such start."""
+    return g1 - (g0 & ~3) > stage
+
+
+_FMT_CASES = []
+
+
+def format_cases():
+    if _FMT_CASES:
+        return _FMT_CASES
+    C = _FMT_CASES
+    cyc = lambda *a: (lambda i: a[i % len(a)])
+    # series counts around the 64-line block, LAG counts that move the fs blocks' edges
+    C.append(FormatCase("n1", 1, 1, cyc(6)))
+    C.append(FormatCase("n63", 63, 2, cyc(1, 0, 6, 7, 8, 9, 13, 22), inactive={0, 30}, wide={5}))
+    C.append(FormatCase("n64", 64, 3, cyc(5, 6, 7, 8, 11), inactive={62}))
+    # st_cap % 4 = (176 + longest name) % 4 with n = 65: the longest service name sets it
+    for r in range(4):
+        C.append(FormatCase(f"n65_cap{r}", 65, 1 + r % 3, lambda i, r=r: 40 + r if i == 9 else 3 + i % 17,
+                            inactive={0} if r == 1 else (), copy=r == 2, specials=r == 2, wide={3}))
+    # inactive: the first series, one between active ones, the whole second block (its byte range
+    # is empty), and the trigger (the last series, inactive at the first rollover)
+    C.append(FormatCase("n129_holes", 129, 1, cyc(4, 9, 14, 3, 21), inactive={0, 17} | set(range(64, 128))))
+    # stage sizes by the average block of the first rollover; a block of long names over its stage
+    C.append(FormatCase("n129_direct", 129, 2, lambda i: 1000 + i if 70 <= i < 80 else 3 + i % 5))
+    C.append(FormatCase("n65_names50", 65, 2, lambda i: 70 + i % 33))
+    C.append(FormatCase("n65_names200", 65, 3, lambda i: 200 + i % 29, wide={7}))
+    C.append(FormatCase("n129_copy", 129, 2, cyc(12, 13, 15, 18, 30, 44), inactive={64}, copy=True, specials=True,
+                        wide={11}))
+    return C
