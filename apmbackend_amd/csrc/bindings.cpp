@@ -120,6 +120,16 @@ EngineConfig config_from(const py::dict& d) {
   c.coll_init_timeout_ms = get<double>(d, "coll_init_timeout_ms", c.coll_init_timeout_ms);
   c.node_cooldown = get<int>(d, "node_cooldown", c.node_cooldown);
   c.outputs = get<uint32_t>(d, "outputs", c.outputs);
+  if (d.contains("win_pcts")) {
+    auto v = d["win_pcts"].cast<std::vector<int64_t>>();
+    if (v.size() > 8) throw std::invalid_argument("win_pcts: at most 8 percentiles");
+    c.n_win_pcts = (int32_t)v.size();
+    for (size_t i = 0; i < v.size(); ++i) {
+      if (v[i] < 1 || v[i] > 100000 || (i && v[i] <= v[i - 1]))
+        throw std::invalid_argument("win_pcts: strictly ascending integers in 1 .. 100000 (percentile * 1000)");
+      c.win_pcts[i] = (int32_t)v[i];
+    }
+  }
   c.async_stats = get<int>(d, "async_stats", c.async_stats);
   c.device_join = get<int>(d, "device_join", c.device_join);
   c.join_table_bits = get<int>(d, "join_table_bits", c.join_table_bits);
@@ -551,6 +561,20 @@ PYBIND11_MODULE(_apm_native, m) {
       .def("pack_service_moments", [](Engine& e, uintptr_t dst, int32_t cap, bool atomic_path) {
         e.pack_service_moments((double*)dst, cap, e.comm_stream(), atomic_path);
       }, py::arg("dst"), py::arg("cap"), py::arg("atomic_path") = false)
+      .def("winpcts", [](Engine& e) {
+        // per series (m, nan, [sum2 per configured percentile]) of the last rollover's K16 value pass
+        std::vector<int32_t> m, nan;
+        std::vector<long long> sum2;
+        e.download_winpcts(m, nan, sum2);
+        const size_t nq = m.empty() ? 0 : sum2.size() / m.size();
+        py::list out;
+        for (size_t i = 0; i < m.size(); ++i) {
+          py::list v;
+          for (size_t j = 0; j < nq; ++j) v.append(py::int_(sum2[i * nq + j]));
+          out.append(py::make_tuple(m[i], nan[i], v));
+        }
+        return out;
+      })
       .def("winstats", [](Engine& e) {
         std::vector<WinStat> w;
         e.download_winstats(w);
@@ -593,15 +617,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[6];
-    int64_t counts[6] = {0, 0, 0, 0, 0, 0};
+    std::string out[7];
+    int64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[6] = {"tx", "fs", "al", "jx", "fb", "lh"};
-    for (int k = 0; k < 6; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[7] = {"tx", "fs", "al", "jx", "fb", "lh", "wp"};
+    for (int k = 0; k < 7; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -782,6 +806,10 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("hist_bin", [](int32_t v) { return hist_bin(v); });
   m.def("hist_lower", [](int b) { return hist_lower(b); });
   m.def("hist_group_max", []() { return apm_hist_group_max(); });
+  // wp percentiles (winpct.hip): the sample count and window length up to which the value pass
+  // keeps a series in its 32-lane group (tests bracket them)
+  m.def("winpct_group_max", []() { return apm_winpct_group_max(); });
+  m.def("winpct_group_win", []() { return apm_winpct_group_win(); });
 
   register_tailer(m);
   register_synth(m);

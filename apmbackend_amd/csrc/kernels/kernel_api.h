@@ -185,6 +185,37 @@ struct HistArgs {
   int32_t* big_n;
   char* out;                    // at least apm_hist_row_bound(max name bytes) * n bytes
 };
+// K16 wp rows: exact window percentiles (winpct.hip, docs/PERCENTILES.md).  The value pass reads
+// the window K8 just read (the same WindowArgs) and writes, per series, the non-NaN sample count m,
+// the NaN count and for each configured percentile the sum of the one or two ranks the integer
+// rank rule reads (one rank: twice the sample).  The text pass prints, per emission position whose
+// series has m >= 1:   wp|<edge ts>|server|service|<m>|<nan>|<p>:<v>,<p>:<v>,...
+constexpr int WP_MAX_Q = 8;
+struct WinPctArgs {
+  WindowArgs w;                 // K8's arguments of this rollover (spill lists sorted; w.out = K8's result)
+  int32_t nq;                   // 1 .. WP_MAX_Q
+  int32_t q[WP_MAX_Q];          // percentile * 1000, strictly ascending, 1 .. 100000
+  long long* sum2;              // [S][nq]
+  int32_t *m, *nan;             // [S]
+  int32_t* big_list;            // [S] series deferred to the block pass
+  int32_t* big_n;
+};
+struct WinPctTextArgs {
+  const long long* sum2;        // [S][nq]
+  const int32_t *m, *nan;       // [S]
+  const int32_t* perm;          // [n] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;
+  int32_t n_series;
+  int32_t nq;
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  char ptxt[WP_MAX_Q][8];       // "<p>:" per percentile (at most "99.999:")
+  int32_t plen[WP_MAX_Q];
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_winpct_row_bound(max name bytes, nq) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -292,6 +323,19 @@ size_t apm_hist_row_bound(size_t name_bytes);
 // count pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_hist_plan(apm::HistArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_hist_write(apm::HistArgs* a, hipStream_t stream);
+// winpct.hip
+// the value pass' two paths (tests bracket them): a series stays in its 32-lane group while the
+// window has at most apm_winpct_group_win() buckets and at most apm_winpct_group_max() samples;
+// every other series is selected by a whole block
+int32_t apm_winpct_group_max();
+int32_t apm_winpct_group_win();
+size_t apm_winpct_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes and nq percentiles
+size_t apm_winpct_row_bound(size_t name_bytes, int32_t nq);
+void apm_winpct_values(apm::WinPctArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_winpct_plan(apm::WinPctTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_winpct_write(apm::WinPctTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

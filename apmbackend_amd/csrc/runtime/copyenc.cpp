@@ -198,8 +198,48 @@ void fs_row_json(std::string& out, const Fields& a) {
 
 }  // namespace
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[6]*/) {
+// wp pairs (utils/records.py _pct_from_text / _half_from_text hold the same rules): integers only.
+bool all_digits(std::string_view s, size_t max_len) {
+  if (s.empty() || s.size() > max_len) return false;
+  for (char ch : s) if (ch < '0' || ch > '9') return false;
+  return true;
+}
+// "99.9" -> q = 99900 (1..100000, at most three decimals); -1: malformed
+int64_t pct_from_text(std::string_view s) {
+  const size_t d = s.find('.');
+  const std::string_view ip = s.substr(0, d);
+  if (!all_digits(ip, 3)) return -1;
+  int64_t q = 0;
+  for (char ch : ip) q = q * 10 + (ch - '0');
+  q *= 1000;
+  if (d != std::string_view::npos) {
+    const std::string_view fr = s.substr(d + 1);
+    if (!all_digits(fr, 3)) return -1;
+    int64_t f = 0;
+    for (char ch : fr) f = f * 10 + (ch - '0');
+    for (size_t k = fr.size(); k < 3; ++k) f *= 10;
+    q += f;
+  }
+  return q >= 1 && q <= 100000 ? q : -1;
+}
+// "-340.5" -> sum2 = -681 (twice the value: an integer, or an integer and ".5"); false: malformed
+bool half_from_text(std::string_view s, int64_t& sum2) {
+  const bool neg = !s.empty() && s[0] == '-';
+  if (neg) s.remove_prefix(1);
+  const size_t d = s.find('.');
+  const std::string_view ip = s.substr(0, d);
+  if (!all_digits(ip, 10)) return false;
+  if (d != std::string_view::npos && s.substr(d + 1) != "5") return false;
+  int64_t v = 0;
+  for (char ch : ip) v = v * 10 + (ch - '0');
+  v = 2 * v + (d != std::string_view::npos ? 1 : 0);
+  sum2 = neg ? -v : v;
+  return true;
+}
+void append_i64(std::string& o, int64_t v) { o += std::to_string(v); }
+
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[7]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -294,6 +334,45 @@ int encode_line(std::string_view line, std::string* out /*[6]*/) {
     copy_escape(o, js);
     o += '\n';
     return 5;
+  }
+  if (t == "wp") {  // window percentiles: timestamp, server, service, count, nan, pcts json
+    std::string& o = out[6];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    c_num(o, a.has(4) ? js::parse_int(a.f[4]) : js::nan()); o += '\t';
+    c_num(o, a.has(5) ? js::parse_int(a.f[5]) : js::nan()); o += '\t';
+    std::string js = "{";
+    std::string_view rest = a.has(6) ? a.f[6] : std::string_view();
+    while (!rest.empty()) {
+      const size_t e = rest.find(',');
+      const std::string_view pr = rest.substr(0, e);
+      rest = e == std::string_view::npos ? std::string_view() : rest.substr(e + 1);
+      const size_t c = pr.find(':');
+      const int64_t q = pct_from_text(pr.substr(0, c));
+      int64_t sum2 = 0;
+      if (q < 0 || c == std::string_view::npos || !half_from_text(pr.substr(c + 1), sum2)) continue;  // (dropped)
+      if (js.size() > 1) js += ',';
+      // the canonical texts again: q / 1000 without trailing zeros, sum2 / 2 as an integer or x.5
+      js += '"';
+      append_i64(js, q / 1000);
+      if (q % 1000) {
+        char fr[4] = {(char)('0' + q % 1000 / 100), (char)('0' + q % 100 / 10), (char)('0' + q % 10), 0};
+        int n = 3;
+        while (fr[n - 1] == '0') --n;
+        js += '.';
+        js.append(fr, (size_t)n);
+      }
+      js += "\":";
+      const int64_t m = sum2 < 0 ? -sum2 : sum2;
+      if (sum2 < 0) js += '-';
+      append_i64(js, m / 2);
+      if (m & 1) js += ".5";
+    }
+    js += '}';
+    copy_escape(o, js);
+    o += '\n';
+    return 6;
   }
   if (t == "jx") {
     std::string& o = out[3];

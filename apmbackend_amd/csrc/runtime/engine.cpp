@@ -212,6 +212,13 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   check_window(cfg_.window, cfg_.buffer, cfg_.interval_len);
   if (cfg_.n_lags < 1 || cfg_.n_lags > MAX_LAGS)
     throw std::runtime_error("engine: 1.." + std::to_string(MAX_LAGS) + " LAG settings");
+  if (want(OUT_WP)) {  // K16: the stream needs its list (before anything is allocated or started)
+    const int nq = cfg_.n_win_pcts;
+    bool ok = nq >= 1 && nq <= WP_MAX_Q;
+    for (int j = 0; ok && j < nq; ++j)
+      ok = cfg_.win_pcts[j] >= 1 && cfg_.win_pcts[j] <= 100000 && (j == 0 || cfg_.win_pcts[j] > cfg_.win_pcts[j - 1]);
+    if (!ok) throw std::invalid_argument("wp stream: win_pcts must hold 1 to 8 strictly ascending percentiles");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -386,6 +393,19 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
   fmt_tmp_bytes_ = apm_format_tmp_bytes((int32_t)((size_t)S * MAX_LAGS + 1));
   d_fmt_tmp_ = res_.dmalloc(fmt_tmp_bytes_);
   res_.pin(h_fmt_meta_, 64);
+  if (want(OUT_WP)) {  // K16
+    const int nq = cfg_.n_win_pcts;  // (checked at the top of the constructor)
+    d_wp_sum2_ = (long long*)res_.dmalloc((size_t)S * nq * 8);
+    d_wp_m_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    d_wp_nan_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    d_wp_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_wp_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_wp_off_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    wp_tmp_bytes_ = apm_winpct_tmp_bytes(S);
+    d_wp_tmp_ = res_.dmalloc(wp_tmp_bytes_);
+    res_.pin(h_wp_total_, 64);
+    for (int k = 0; k < 2; ++k) ev_wp_[k] = res_.new_event();
+  }
   if (want(OUT_LH)) {  // K15
     d_hist_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
     d_hist_off_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
@@ -2278,6 +2298,10 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   const double tr2 = now_ms();
   trace_event("ro.K8-K11 launch", tsp, tr2, 1);
   if (want(OUT_ST) || want(OUT_FS)) format_rollover_text(edge_ts);
+  // K16: behind the alert chain and the st / fs text, so neither waits for it.  Nothing queued
+  // since K8 writes window cells, counts or spill lists (K10 / K11 / the gather read d_win_, the
+  // release merges the tx pool, K12 formats), and the next append follows on this stream.
+  if (want(OUT_WP)) winpct_rollover(wa, edge_ts);
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2432,8 +2456,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[6];
-        int64_t counts[6] = {0, 0, 0, 0, 0, 0};
+        std::string enc[7];
+        int64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -2910,6 +2934,88 @@ void Engine::hist_bucket(int64_t b, int slot) {
   });
 }
 
+// ---- K16: wp rows.  One row per st row whose window holds a non-NaN sample, in st order, with
+// the st rows' timestamp: value pass over K8's window, then count / scan / write of the text.
+void Engine::winpct_rollover(const WindowArgs& wa, int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();
+  const int nq = cfg_.n_win_pcts;
+  WinPctArgs pa{};
+  pa.w = wa;
+  pa.nq = nq;
+  for (int j = 0; j < nq; ++j) pa.q[j] = cfg_.win_pcts[j];
+  pa.sum2 = d_wp_sum2_;
+  pa.m = d_wp_m_;
+  pa.nan = d_wp_nan_;
+  pa.big_list = d_wp_big_;
+  pa.big_n = d_wp_big_ + cfg_.max_series;
+  apm_winpct_values(&pa, stream_);
+  WinPctTextArgs ta{};
+  ta.sum2 = d_wp_sum2_;
+  ta.m = d_wp_m_;
+  ta.nan = d_wp_nan_;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n;
+  ta.n_series = n;
+  ta.nq = nq;
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  for (int j = 0; j < nq; ++j) {
+    // the canonical text of q / 1000: trailing zeros and a trailing point dropped
+    const int q = cfg_.win_pcts[j];
+    char fr[8];
+    int len = std::snprintf(ta.ptxt[j], sizeof ta.ptxt[j], "%d", q / 1000);
+    if (q % 1000) {
+      int k = std::snprintf(fr, sizeof fr, "%03d", q % 1000);
+      while (fr[k - 1] == '0') --k;
+      ta.ptxt[j][len++] = '.';
+      for (int i = 0; i < k; ++i) ta.ptxt[j][len++] = fr[i];
+    }
+    ta.ptxt[j][len++] = ':';
+    ta.plen[j] = len;
+  }
+  ta.len = d_wp_len_;
+  ta.off = d_wp_off_;
+  const int k = wp_k_;
+  wp_k_ ^= 1;
+  out_wait(wp_task_[k]);  // slot k's previous D2H + emission is done
+  // the output bound needs no length pass: every row is at most apm_winpct_row_bound bytes
+  const size_t cap = (size_t)n * apm_winpct_row_bound(max_name_len_, nq) + 64;
+  if (cap > wp_out_cap_[k]) d_wp_out_[k] = (char*)res_.regrow(d_wp_out_[k], wp_out_cap_[k], cap, stream_);
+  ta.out = d_wp_out_[k];
+  if (apm_winpct_plan(&ta, d_wp_tmp_, wp_tmp_bytes_, stream_) != 0) throw std::runtime_error("percentile scan failed");
+  apm_winpct_write(&ta, stream_);
+  {
+    ExportArgs ex{};
+    ex.add(ta.off + n, h_wp_total_.d + k, 4);
+    apm_export(&ex, stream_);
+  }
+  HIP_OK(hipEventRecord(ev_wp_[k], stream_));
+  const char* dst = d_wp_out_[k];
+  wp_task_[k] = post_out([this, k, dst]() {
+    HIP_OK(hipEventSynchronize(ev_wp_[k]));
+    const size_t total = h_wp_total_[k];
+    if (!total) return;
+    res_.reserve(h_wp_text_[k], total, total * 2 + (1 << 20));
+    lane_d2h(h_wp_text_[k], dst, total);
+    lane_sync();
+    emit_bytes(OUT_WP, h_wp_text_[k], total);
+  });
+}
+
+void Engine::download_winpcts(std::vector<int32_t>& m, std::vector<int32_t>& nan, std::vector<long long>& sum2) {
+  m.clear(); nan.clear(); sum2.clear();
+  if (!want(OUT_WP) || n_series_ == 0) return;
+  const size_t n = (size_t)n_series_, nq = (size_t)cfg_.n_win_pcts;
+  m.resize(n); nan.resize(n); sum2.resize(n * nq);
+  HIP_OK(hipMemcpyAsync(m.data(), d_wp_m_, n * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(nan.data(), d_wp_nan_, n * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(sum2.data(), d_wp_sum2_, n * nq * 8, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3050,7 +3156,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp"};
   return n[k];
 }
 

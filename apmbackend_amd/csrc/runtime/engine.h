@@ -114,6 +114,10 @@ struct EngineConfig {
   bool pin_threads = false;  // pin host lanes to GPU-local physical cores (APM_PIN_THREADS overrides)
   // outputs: bit k of `outputs` materialises stream k (OutKind) in the reference wire format
   uint32_t outputs = 0;
+  // wp stream (K16): the percentiles as q = p * 1000, strictly ascending, 1 .. 100000; read at
+  // construction (OUT_WP in `outputs` without a valid list is an error)
+  int32_t n_win_pcts = 0;
+  int32_t win_pcts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int async_stats = 1;      // overlap batch i's stats with batch i+1's parse + join
   // RCCL watchdog: a collective not complete after this long (a dead or wedged peer) aborts the
   // communicator and throws, so the supervisor restarts the rank group from its checkpoint
@@ -139,12 +143,12 @@ struct EngineConfig {
 //   FS            z -> alerts/db  fs lines (one per series per LAG)
 //   AL            alerts -> db    al lines
 //   SX            new: per-JVM rollup fused with JMX / VM gauges (K14), one line per server
-enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, N_OUT };
+enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, N_OUT };
 // Streams whose pending text a checkpoint stores (checkpoint.cpp).  The version-9 layout holds
-// exactly these; lh rows are taken by their consumer before a checkpoint and are not persisted.
+// exactly these; lh and wp rows are taken by their consumer before a checkpoint and are not persisted.
 constexpr int N_OUT_CKPT = OUT_FB + 1;
-// streams written by the engine's output lane (released tx, st, fs, lh); the stats thread owns the rest
-constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH);
+// streams written by the engine's output lane (released tx, st, fs, lh, wp); the stats thread owns the rest
+constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP);
 const char* out_kind_name(int k);
 int out_kind_of(const std::string& name);
 
@@ -711,7 +715,7 @@ class Engine {
   std::mutex out_pool_mu_;
   bool st_has_job_ = false, st_busy_ = false, st_stop_ = false;
   std::string st_error_;
-  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh streams (kLaneKinds)
+  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp streams (kLaneKinds)
   std::thread out_thread_;
   std::mutex out_mu_;
   std::condition_variable out_cv_;
@@ -1195,9 +1199,31 @@ class Engine {
   void hist_rollover(int64_t L, int64_t prev);
   void hist_bucket(int64_t b, int slot);
 
+  // K16 wp rows (winpct.hip), allocated when the stream is on: exact percentiles of the window K8
+  // read, queued behind the rollover's alert chain and st / fs formatting.  No device state
+  // outlives a rollover; two device / pinned text slots, as for st / fs.
+  long long* d_wp_sum2_ = nullptr;                          // [S][nq]
+  int32_t *d_wp_m_ = nullptr, *d_wp_nan_ = nullptr;         // [S]
+  int32_t* d_wp_big_ = nullptr;                             // [S] block-pass list, [S] its length
+  uint32_t *d_wp_len_ = nullptr, *d_wp_off_ = nullptr;      // [S + 1]
+  void* d_wp_tmp_ = nullptr;
+  size_t wp_tmp_bytes_ = 0;
+  char* d_wp_out_[2] = {nullptr, nullptr};
+  size_t wp_out_cap_[2] = {0, 0};
+  PinnedBuf<char> h_wp_text_[2];  // pinned (output lane)
+  Mapped<uint32_t> h_wp_total_;   // pinned [2]: bytes of slot k's rows
+  hipEvent_t ev_wp_[2] = {nullptr, nullptr};
+  uint64_t wp_task_[2] = {0, 0};
+  int wp_k_ = 0;
+  void winpct_rollover(const WindowArgs& wa, int64_t edge_ts);
+ public:
+  // (tests) the value pass' result of the last rollover: per series m, nan and nq sums
+  void download_winpcts(std::vector<int32_t>& m, std::vector<int32_t>& nan, std::vector<long long>& sum2);
+ private:
+
   // text outputs
   std::string blob_[N_OUT];
-  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   std::shared_ptr<ByteSink> byte_sink_[N_OUT];
   bool fs_copy_ = false;
   bool db_copy_ = false;
@@ -1206,7 +1232,7 @@ class Engine {
   void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
-  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // K14 server rollup + exogenous context
   std::vector<double> h_ctx_;                    // [servers][CTX_FIELDS] (stats thread)
   bool ctx_dirty_ = false;

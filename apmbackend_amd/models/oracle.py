@@ -26,9 +26,9 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import as_bool, gpu_opt, zscore_lag_settings
-from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, StatEntry, TxEntry, entry_from_csv, hist_bin,
-                             hist_lower)
+from ..utils.config import as_bool, gpu_opt, window_percentiles, zscore_lag_settings
+from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, StatEntry, TxEntry, WindowPctEntry,
+                             entry_from_csv, hist_bin, hist_lower, pct_ranks)
 from ..utils.timeparse import TzOffset, convert_string_date_to_ms, default_tz
 
 NAN = float("nan")
@@ -667,8 +667,11 @@ class StatsOracle:
     """``StatParser`` + ``consumeMsg`` of stream_calc_stats.js."""
 
     def __init__(self, emit_stat: Callable[[str], None], emit_db: Callable[[str], None],
-                 interval_len=10, window=30, buffer=6, emit_hist: Optional[Callable[[str], None]] = None):
+                 interval_len=10, window=30, buffer=6, emit_hist: Optional[Callable[[str], None]] = None,
+                 emit_pct: Optional[Callable[[str], None]] = None, percentiles: Iterable[int] = ()):
         self.emit_hist = emit_hist  # lh rows (docs/HISTOGRAM.md); None = stream off
+        self.emit_pct = emit_pct    # wp rows (docs/PERCENTILES.md); None = stream off
+        self.percentiles = [int(q) for q in percentiles]  # q = p * 1000 (config.window_percentiles)
         self.emit_stat = emit_stat
         self.emit_db = emit_db
         self.interval_len = interval_len
@@ -737,6 +740,20 @@ class StatsOracle:
                                                  [(hist_lower(k), bins[k]) for k in sorted(bins)]).to_csv())
         return rows
 
+    def pct_row(self, edge_ts: int, server: str, service: str, win: List[List[int]]) -> Optional[str]:
+        """The wp row of one window (its buckets in key order): the percentiles of the samples
+        that are not NaN, sorted ascending, by the integer rank rule; None when there is none."""
+        flat = [v for arr in win for v in arr]
+        # the engine stores int32; anything else is its NaN sentinel (engine.cpp)
+        fin = sorted(int(v) for v in flat if v == v and -2147483647 <= v <= 2147483647)
+        if not fin:
+            return None
+        pcts = []
+        for q in self.percentiles:
+            lo, hi = pct_ranks(len(fin), q)
+            pcts.append((q, fin[lo] + fin[hi]))
+        return WindowPctEntry(edge_ts, server, service, len(fin), len(flat) - len(fin), pcts).to_csv()
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -771,6 +788,10 @@ class StatsOracle:
                 tpm = cnt / (self.window * self.interval_len / 60.0)
                 st = StatEntry.make(edge_ts, server, service, tpm, avg, p75, p95)
                 self.emit_stat(st.to_csv())
+                if self.emit_pct is not None and cnt != 0:
+                    row = self.pct_row(edge_ts, server, service, win)
+                    if row is not None:
+                        self.emit_pct(row)
 
 
 # ----------------------------------------------------------------------------- z-score oracle
@@ -998,6 +1019,7 @@ class PipelineOracle:
         self.al: List[str] = []
         self.tx_out: List[str] = []
         self.lh: List[str] = []
+        self.wp: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1005,7 +1027,9 @@ class PipelineOracle:
         sc = cfg["streamCalcStats"]
         self.st = StatsOracle(self._on_st, self.tx_db.append, int(sc["intervalLengthInSeconds"]),
                               int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
-                              emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None)
+                              emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None,
+                              emit_pct=self.wp.append if window_percentiles(cfg) else None,
+                              percentiles=window_percentiles(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

@@ -21,6 +21,7 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 from .. import _native
 from ..models.oracle import file_kind, server_of
 from ..ops.parse_ref import tz_table
+from ..utils.config import window_percentiles
 from ..utils.timeparse import TzOffset
 
 log = logging.getLogger("apm.pipeline")
@@ -29,7 +30,11 @@ KIND_CODE = {"SOAP": 0, "SERVER": 1, "APP": 2}
 
 # Output streams (engine.h OutKind); the bit index is the position in this tuple.
 OUT_KINDS = ("transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh")
-# keep_text=True materialises these; lh (K15 latency histograms) is opt-in through `outputs` only
+# Streams added after lh continue the enum here: OUT_KINDS keeps ending in "lh", which
+# tests/test_hist_engine_gpu.py pins.  ALL_OUT_KINDS is engine.h's OutKind in full.
+ALL_OUT_KINDS = OUT_KINDS + ("wp",)
+# keep_text=True materialises these; lh (K15 latency histograms) and wp (K16 window percentiles)
+# are opt-in through `outputs` only
 KEEP_TEXT_KINDS = tuple(k for k in OUT_KINDS if k != "lh")
 # What the reference persists (db_insert queue): released + audit tx, fs, al.  `transactions`
 # and `st` are internal hand-offs that only the AMQP bridge needs.
@@ -40,17 +45,21 @@ MAX_LAGS = 16  # apm_types.h MAX_LAGS: LAG capacity per engine (each LAG is an H
 def output_mask(kinds) -> int:
     m = 0
     for k in kinds:
-        m |= 1 << OUT_KINDS.index(k)
+        m |= 1 << ALL_OUT_KINDS.index(k)
     return m
 
 
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
                   **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
-    materialises every stream but the opt-in lh; `outputs` (iterable of OUT_KINDS) selects explicitly.
+    materialises every stream but the opt-in lh / wp; `outputs` (iterable of ALL_OUT_KINDS) selects explicitly.
     The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
-    existed, `outputs` was ignored under keep_text)."""
+    existed, `outputs` was ignored under keep_text).  "wp" takes its percentiles from
+    gpu.windowPercentiles (ValueError when the list is missing or malformed)."""
     g = cfg.get("gpu", {})
+    win_pcts = window_percentiles(cfg)
+    if "wp" in (outputs or ()) and not win_pcts:
+        raise ValueError('outputs names "wp" but gpu.windowPercentiles is empty')
     zc = cfg["streamCalcZScore"]
     ac = cfg["streamProcessAlerts"]
     sc = cfg["streamCalcStats"]
@@ -115,6 +124,9 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         "tx_ring_bytes": min(int(g.get("txTextRingMB", 4096)), max(256, (128 * int(g.get("batchBytes", 32 << 20))) >> 20)) << 20,
         "max_raw_services": max(int(g.get("maxRawServices", 1 << 18)), 2 * int(g.get("maxSeries", 1 << 17))),
         "outputs": output_mask(KEEP_TEXT_KINDS if keep_text else ()) | output_mask(outputs or ()),
+        # K16: the percentiles of the wp stream as q = p * 1000, read at construction (a reload that
+        # changes them is reported as needing a restart, like every other non-live setting)
+        "win_pcts": win_pcts,
     }
     # intervalLengthInSeconds only scales the TPM divisor: the bucket label is endTs without its
     # last 4 digits whatever the interval (stream_calc_stats.js:89-96, :186), as here

@@ -38,9 +38,9 @@ import time
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 from ..models.oracle import file_kind, server_of
-from ..models.pipeline import DB_OUTPUTS, KIND_CODE, OUT_KINDS, APMEngine
+from ..models.pipeline import ALL_OUT_KINDS, DB_OUTPUTS, KIND_CODE, APMEngine
 from ..parallel.dist import dist_env, shard_servers
-from ..utils.config import ConfigWatcher, as_bool, gpu_opt, read_apm_config
+from ..utils.config import ConfigWatcher, as_bool, gpu_opt, read_apm_config, window_percentiles
 from . import logger as apmlog
 from .notifier import AlertNotifier
 from .sinks import DBInserter
@@ -149,16 +149,18 @@ class IngestService:
             outs.add("sx")
         if as_bool(gpu_opt(self.cfg, "latencyHistogram")):  # K15 per-interval latency histograms
             outs.add("lh")
+        if window_percentiles(self.cfg):  # K16 exact window percentiles (ValueError on a malformed list)
+            outs.add("wp")
         if self.world > 1 and engine == "native" and as_bool(g.get("fleetBaseline", True)) \
                 and as_bool(g.get("fleetBaselineRows", True)):
             outs.add("fb")  # fleet-merged per-service baselines (rank 0 emits them)
         if self.mode == "amqp":
             outs |= {"transactions" if "transactions" in self.bridge else "", "st" if "stats" in self.bridge else ""}
             outs.discard("")
-        self.outputs = [k for k in OUT_KINDS if k in outs]
+        self.outputs = [k for k in ALL_OUT_KINDS if k in outs]
         self.outs_set = set(self.outputs)
         if self.mode == "amqp" and "z_score" in self.bridge:
-            self.outputs = [k for k in OUT_KINDS if k in set(self.outputs) | {"fs"}]
+            self.outputs = [k for k in ALL_OUT_KINDS if k in set(self.outputs) | {"fs"}]
         if engine == "native":
             self.eng = APMEngine(self.cfg, device=self.local_rank, outputs=self.outputs)
             self.native = self.eng.eng
@@ -271,6 +273,8 @@ class IngestService:
                 self.producers["fleet"] = self.qm.get_queue(g.get("fleetQueue", "fleet_baseline"), "p")
             if "lh" in self.outs_set:  # likewise (stream_insert_db.js does not know the type)
                 self.producers["hist"] = self.qm.get_queue(gpu_opt(self.cfg, "histQueue"), "p")
+            if "wp" in self.outs_set:
+                self.producers["pct"] = self.qm.get_queue(gpu_opt(self.cfg, "pctQueue"), "p")
             self.qm.on("pause", lambda: log.info("queue backpressure: pausing ingest"))
         elif self.mode != "none":
             raise ValueError(f"unknown gpu.outputMode {self.mode!r}")
@@ -824,13 +828,15 @@ class IngestService:
             counts[k] = blob.count(b"\n")
             if k == "al" and self.notifier:
                 self.notifier.add_lines(blob.decode("utf-8").split("\n"))
-            if self.inserter is not None and (k in DB_OUTPUTS or k in ("fb", "lh")):
+            if self.inserter is not None and (k in DB_OUTPUTS or k in ("fb", "lh", "wp")):
                 self.inserter.consume_bytes(blob)
             elif self.qm is not None:
                 if k == "fb":
                     prod = self.producers.get("fleet")
                 elif k == "lh":
                     prod = self.producers.get("hist")
+                elif k == "wp":
+                    prod = self.producers.get("pct")
                 elif k in DB_OUTPUTS:
                     prod = self.producers["db"]
                 elif k == "transactions":

@@ -56,10 +56,12 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
     "fb": ("dbFleetTable", ["timestamp", "service", "lag", "nseries", "stats"]),
     # per-interval latency histograms (lh records, gpu.latencyHistogram): not part of the reference schema
     "lh": ("dbHistTable", ["timestamp", "server", "service", "count", "nan", "bins"]),
+    # exact window percentiles (wp records, gpu.windowPercentiles): not part of the reference schema
+    "wp": ("dbPctTable", ["timestamp", "server", "service", "count", "nan", "pcts"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb", "lh")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp")
 # tables of the record types the reference does not know (its config has no key for them)
-DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist"}
+DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -143,7 +145,7 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = None
         elif c in _TS_COLS:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
-        elif c in ("stats", "entry", "bins"):
+        elif c in ("stats", "entry", "bins", "pcts"):
             out[c] = json.loads(v)
         elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan") or rtype == "jx" and c not in ("server",):
             f = float(v)
@@ -328,7 +330,7 @@ def make_writer(ins_cfg: Dict[str, Any]) -> Writer:
 def save_resume(path: str, buffers: Dict[str, Deque[Dict[str, Any]]]):
     """util_methods.saveToResumeFile with the Map replacer: {"dataType":"Map","value":[...]}
     (atomic: tmp + rename)."""
-    # the reference's four buffers always; the fleet and histogram buffers (our additions) only
+    # the reference's four buffers always; the fleet, histogram and percentile buffers (our additions) only
     # when they hold rows
     doc = {"dataType": "Map", "value": [[t, [_json_row(r) for r in rows]] for t, rows in buffers.items()
                                         if t not in DEFAULT_TABLES or rows]}

@@ -15,6 +15,7 @@ reported, never silently ignored.
 from __future__ import annotations
 
 import copy
+import decimal
 import hashlib
 import json
 import logging
@@ -86,11 +87,55 @@ GPU_DEFAULTS: Dict[str, Any] = {
 GPU_OPTIONAL: Dict[str, Any] = {
     "latencyHistogram": False,        # K15 "lh" stream: per-interval latency histograms (docs/HISTOGRAM.md)
     "histQueue": "latency_hist",      # amqp mode: the queue the lh records go to
+    "windowPercentiles": [],          # K16 "wp" stream: exact window percentiles, e.g. [50, 90, 99, 99.9] (docs/PERCENTILES.md)
+    "pctQueue": "window_pct",         # amqp mode: the queue the wp records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
     """An optional gpu key's value, GPU_OPTIONAL's default when the config does not name it."""
     return (cfg.get("gpu") or {}).get(key, GPU_OPTIONAL[key])
+
+
+MAX_WINDOW_PCTS = 8   # kernel_api.h WP_MAX_Q
+PCT_SCALE = 100000    # q = p * 1000: a percentile with three decimals as an integer, 100 % = 100000
+
+
+def parse_window_percentiles(v: Any) -> List[int]:
+    """gpu.windowPercentiles -> [q], q = p * 1000 (1 <= q <= 100000), strictly ascending, at most
+    eight.  Each entry goes through its decimal text (a float's shortest repr, which is the text
+    the config held), never through float arithmetic.  None / [] -> [] (stream off); anything
+    else that is not such a list raises ValueError."""
+    if v is None:
+        return []
+    if isinstance(v, (str, bytes)) or not isinstance(v, (list, tuple)):
+        raise ValueError(f"gpu.windowPercentiles: a list of percentiles, got {v!r}")
+    if len(v) > MAX_WINDOW_PCTS:
+        raise ValueError(f"gpu.windowPercentiles: at most {MAX_WINDOW_PCTS} percentiles, got {len(v)}")
+    out: List[int] = []
+    for p in v:
+        if isinstance(p, bool) or not isinstance(p, (int, float, str, decimal.Decimal)):
+            raise ValueError(f"gpu.windowPercentiles: {p!r} is not a number")
+        try:
+            d = decimal.Decimal(repr(p) if isinstance(p, float) else str(p).strip())
+        except decimal.InvalidOperation:
+            raise ValueError(f"gpu.windowPercentiles: {p!r} is not a number") from None
+        if not d.is_finite():
+            raise ValueError(f"gpu.windowPercentiles: {p!r} is not finite")
+        q = d * 1000
+        if q != q.to_integral_value():
+            raise ValueError(f"gpu.windowPercentiles: {p!r} has more than three decimals")
+        q = int(q)
+        if not 1 <= q <= PCT_SCALE:
+            raise ValueError(f"gpu.windowPercentiles: {p!r} is outside (0, 100]")
+        if out and q <= out[-1]:
+            raise ValueError(f"gpu.windowPercentiles: {p!r} does not ascend strictly")
+        out.append(q)
+    return out
+
+
+def window_percentiles(cfg: Dict[str, Any]) -> List[int]:
+    """The validated gpu.windowPercentiles of a config as integers q = p * 1000 ([]: off)."""
+    return parse_window_percentiles(gpu_opt(cfg, "windowPercentiles"))
 
 
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
@@ -124,6 +169,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
     merged = dict(GPU_DEFAULTS)
     merged.update({k: v for k, v in cfg["gpu"].items() if k in GPU_DEFAULTS or k in GPU_OPTIONAL})
     cfg["gpu"] = merged
+    if "windowPercentiles" in merged:
+        parse_window_percentiles(merged["windowPercentiles"])  # ValueError: a bad list stops the load
     return cfg
 
 

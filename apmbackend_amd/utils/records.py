@@ -315,6 +315,81 @@ class LatencyHistEntry:
                 "bins": {str(lo): c for lo, c in self.bins}}
 
 
+# ---- wp: exact window percentiles (docs/PERCENTILES.md).  Integers only: a percentile is
+# q = p * 1000 (1..100000), a value the sum of the one or two ranks read (one rank: twice it).
+PCT_SCALE = 100000
+
+
+def pct_text(q: int) -> str:
+    """Canonical text of percentile q / 1000: trailing zeros and a trailing point dropped."""
+    q = int(q)
+    s = f"{q // 1000}.{q % 1000:03d}".rstrip("0")
+    return s[:-1] if s.endswith(".") else s
+
+
+def pct_ranks(m: int, q: int) -> tuple:
+    """calcPercentile's (lo, hi) ranks among m >= 1 ascending samples for percentile q / 1000, in
+    integers: t = q * m; t a multiple of 100000 -> rank t / 100000 - 1; else i = ceil(t / 100000) - 1
+    and (i, i + 1), or (i, i) at the last sample.  m == 1 -> (0, 0)."""
+    if m == 1:
+        return (0, 0)
+    t = int(q) * int(m)
+    if t % PCT_SCALE == 0:
+        i = t // PCT_SCALE - 1
+        return (i, i)
+    i = t // PCT_SCALE  # ceil(t / 100000) - 1 of a non-multiple
+    return (i, i) if i == m - 1 else (i, i + 1)
+
+
+def half_text(sum2: int) -> str:
+    """sum2 / 2 in decimal: the integer half, '.5' when sum2 is odd, '-' when negative (-1 -> -0.5)."""
+    sum2 = int(sum2)
+    a = abs(sum2)
+    return ("-" if sum2 < 0 else "") + str(a // 2) + (".5" if a & 1 else "")
+
+
+def _pct_from_text(s: str) -> Optional[int]:
+    ip, sep, fr = s.partition(".")
+    if not (ip.isascii() and ip.isdigit() and len(ip) <= 3) or (sep and not (fr.isascii() and fr.isdigit() and len(fr) <= 3)):
+        return None
+    q = int(ip) * 1000 + (int(fr.ljust(3, "0")) if sep else 0)
+    return q if 1 <= q <= PCT_SCALE else None
+
+
+def _half_from_text(s: str) -> Optional[int]:
+    neg = s.startswith("-")
+    ip, sep, fr = (s[1:] if neg else s).partition(".")
+    if not (ip.isascii() and ip.isdigit() and len(ip) <= 10) or (sep and fr != "5"):
+        return None
+    v = 2 * int(ip) + (1 if sep else 0)
+    return -v if neg else v
+
+
+@dataclass
+class WindowPctEntry:
+    """``wp|ts|server|service|m|nan|p:v,p:v,...`` -- exact percentiles of the K8 window's ``m``
+    non-NaN samples (``nan`` counts the others), one row per st row with m >= 1 (no reference
+    counterpart).  ``pcts`` holds (q, sum2) integer pairs: q = p * 1000, sum2 = twice the value."""
+    timestamp: Num
+    server: str
+    service: str
+    count: Num
+    nan: Num
+    pcts: List[tuple]
+    type: str = "wp"
+
+    def to_csv(self) -> str:
+        pairs = ",".join(f"{pct_text(q)}:{half_text(v)}" for q, v in self.pcts)
+        return (f"wp|{js_str(self.timestamp)}|{self.server}|{self.service}|{js_str(self.count)}|"
+                f"{js_str(self.nan)}|{pairs}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        # (|sum2| < 2^33: the half is exact in a double)
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "count": _num_or_none(self.count), "nan": _num_or_none(self.nan),
+                "pcts": {pct_text(q): (v // 2 if v % 2 == 0 else v / 2) for q, v in self.pcts}}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -357,7 +432,16 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
             if lo == lo and c == c:  # (a malformed pair is dropped, as copyenc.cpp does)
                 bins.append((int(lo), int(c)))
         return LatencyHistEntry(parse_int(a[1]), a[2], a[3], parse_int(a[4]), parse_int(a[5]), bins)
+    if t == "wp":
+        a = _pad(arr, 7)
+        pcts = []
+        for pr in (a[6] or "").split(","):
+            p, _sep, v = pr.partition(":")
+            q, s2 = _pct_from_text(p), _half_from_text(v)
+            if q is not None and s2 is not None:  # (a malformed pair is dropped, as copyenc.cpp does)
+                pcts.append((q, s2))
+        return WindowPctEntry(parse_int(a[1]), a[2], a[3], parse_int(a[4]), parse_int(a[5]), pcts)
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp")
