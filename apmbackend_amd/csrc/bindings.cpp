@@ -130,6 +130,11 @@ EngineConfig config_from(const py::dict& d) {
       c.win_pcts[i] = (int32_t)v[i];
     }
   }
+  if (d.contains("slo_classes")) {  // (the constructor checks the tables when the sl stream is on)
+    c.slo_classes = d["slo_classes"].cast<std::vector<std::vector<int64_t>>>();
+    if (d.contains("slo_services")) c.slo_services = d["slo_services"].cast<std::map<std::string, int32_t>>();
+    c.slo_default = get<int32_t>(d, "slo_default", 0);
+  }
   c.async_stats = get<int>(d, "async_stats", c.async_stats);
   c.device_join = get<int>(d, "device_join", c.device_join);
   c.join_table_bits = get<int>(d, "join_table_bits", c.join_table_bits);
@@ -575,6 +580,19 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("slo_counts", [](Engine& e) {
+        // per series (m, nan, [c_j per threshold of its class]) of the last rollover's K17 value pass
+        std::vector<SloRec> rec;
+        std::vector<int32_t> nthr;
+        e.download_slo(rec, nthr);
+        py::list out;
+        for (size_t i = 0; i < rec.size(); ++i) {
+          py::list v;
+          for (int32_t j = 0; j < nthr[i]; ++j) v.append(py::int_(rec[i].c[j]));
+          out.append(py::make_tuple(rec[i].m, rec[i].nan, v));
+        }
+        return out;
+      })
       .def("winstats", [](Engine& e) {
         std::vector<WinStat> w;
         e.download_winstats(w);
@@ -617,15 +635,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[7];
-    int64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
+    std::string out[8];
+    int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[7] = {"tx", "fs", "al", "jx", "fb", "lh", "wp"};
-    for (int k = 0; k < 7; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[8] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl"};
+    for (int k = 0; k < 8; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -810,6 +828,10 @@ PYBIND11_MODULE(_apm_native, m) {
   // keeps a series in its 32-lane group (tests bracket them)
   m.def("winpct_group_max", []() { return apm_winpct_group_max(); });
   m.def("winpct_group_win", []() { return apm_winpct_group_win(); });
+  // sl threshold counts (slo.hip): the sample count up to which the value pass keeps a series in
+  // its 32-lane group, and the write pass' LDS stage (tests bracket them)
+  m.def("slo_group_max", []() { return apm_slo_group_max(); });
+  m.def("slo_stage_bytes", []() { return apm_slo_stage_bytes(); });
 
   register_tailer(m);
   register_synth(m);

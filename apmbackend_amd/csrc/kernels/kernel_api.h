@@ -216,6 +216,43 @@ struct WinPctTextArgs {
   uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
   char* out;                    // at least apm_winpct_row_bound(max name bytes, nq) * n bytes
 };
+// K17 sl rows: exact window threshold counts per service objective (slo.hip, docs/OBJECTIVES.md).
+// The value pass reads the window K8 just read and writes one record per series: the non-NaN sample
+// count m, the NaN count and, for the thresholds T_1 < ... < T_k of the series' class, the number
+// of non-NaN samples v <= T_j (cumulative).  Class 0 has no threshold (no row).  The text pass
+// prints, per emission position whose series has m >= 1 and k >= 1:
+//   sl|<edge ts>|server|service|<m>|<nan>|<T>:<c>,<T>:<c>,...
+constexpr int SL_MAX_T = 8;
+struct SloRec {
+  int32_t m, nan;
+  int32_t c[SL_MAX_T];
+};
+struct SloArgs {
+  WindowArgs w;                 // K8's arguments of this rollover (spill lists sorted; w.out = K8's result)
+  const int32_t* cls;           // [S] class per series (values outside [0, n_classes) count as 0)
+  const int32_t* nthr;          // [n_classes] thresholds per class, 0 .. SL_MAX_T (class 0: 0)
+  const int32_t* thr;           // [n_classes][SL_MAX_T] strictly ascending, 0 .. INT32_MAX
+  int32_t n_classes;
+  SloRec* rec;                  // [S]
+  int32_t* big_list;            // [S] series deferred to the block pass
+  int32_t* big_n;
+};
+struct SloTextArgs {
+  const SloRec* rec;            // [S]
+  const int32_t* cls;           // [S]
+  const int32_t* nthr;
+  const int32_t* thr;
+  int32_t n_classes;
+  const int32_t* perm;          // [n] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;
+  int32_t n_series;
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_slo_row_bound(max name bytes) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -336,6 +373,18 @@ void apm_winpct_values(apm::WinPctArgs* a, hipStream_t stream);
 // length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_winpct_plan(apm::WinPctTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_winpct_write(apm::WinPctTextArgs* a, hipStream_t stream);
+// slo.hip
+// the value pass' two paths (tests bracket the boundary): a series whose window K8 counted at most
+// apm_slo_group_max() samples stays in its 32-lane group, every other one is counted by a block
+int32_t apm_slo_group_max();
+int32_t apm_slo_stage_bytes();   // the write pass' LDS stage (a 64-row block over it stores directly)
+size_t apm_slo_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes
+size_t apm_slo_row_bound(size_t name_bytes);
+void apm_slo_values(apm::SloArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_slo_plan(apm::SloTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_slo_write(apm::SloTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

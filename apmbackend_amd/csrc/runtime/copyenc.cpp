@@ -238,8 +238,8 @@ bool half_from_text(std::string_view s, int64_t& sum2) {
 }
 void append_i64(std::string& o, int64_t v) { o += std::to_string(v); }
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[7]*/) {
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[8]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -373,6 +373,40 @@ int encode_line(std::string_view line, std::string* out /*[7]*/) {
     copy_escape(o, js);
     o += '\n';
     return 6;
+  }
+  if (t == "sl") {  // window threshold counts: timestamp, server, service, count, nan, le json
+    std::string& o = out[7];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    c_num(o, a.has(4) ? js::parse_int(a.f[4]) : js::nan()); o += '\t';
+    c_num(o, a.has(5) ? js::parse_int(a.f[5]) : js::nan()); o += '\t';
+    std::string js = "{";
+    std::string_view rest = a.has(6) ? a.f[6] : std::string_view();
+    int64_t last_t = -1;
+    while (!rest.empty()) {
+      const size_t e = rest.find(',');
+      const std::string_view pr = rest.substr(0, e);
+      rest = e == std::string_view::npos ? std::string_view() : rest.substr(e + 1);
+      const size_t c = pr.find(':');
+      // (utils/records.py slo_pairs_from_text holds the same rules) T and c: 1 to 10 digits,
+      // T <= INT32_MAX and above the last pair kept
+      if (c == std::string_view::npos || !all_digits(pr.substr(0, c), 10) || !all_digits(pr.substr(c + 1), 10)) continue;
+      int64_t tv = 0, cv = 0;
+      for (char ch : pr.substr(0, c)) tv = tv * 10 + (ch - '0');
+      for (char ch : pr.substr(c + 1)) cv = cv * 10 + (ch - '0');
+      if (tv > 2147483647 || tv <= last_t) continue;  // (dropped)
+      last_t = tv;
+      if (js.size() > 1) js += ',';
+      js += '"';
+      append_i64(js, tv);
+      js += "\":";
+      append_i64(js, cv);
+    }
+    js += '}';
+    copy_escape(o, js);
+    o += '\n';
+    return 7;
   }
   if (t == "jx") {
     std::string& o = out[3];

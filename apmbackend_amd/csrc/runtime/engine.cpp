@@ -219,6 +219,23 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       ok = cfg_.win_pcts[j] >= 1 && cfg_.win_pcts[j] <= 100000 && (j == 0 || cfg_.win_pcts[j] > cfg_.win_pcts[j - 1]);
     if (!ok) throw std::invalid_argument("wp stream: win_pcts must hold 1 to 8 strictly ascending percentiles");
   }
+  if (want(OUT_SL)) {  // K17: the stream needs its tables (likewise before anything is allocated)
+    const auto& cl = cfg_.slo_classes;
+    bool ok = !cl.empty() && cl[0].empty() && cl.size() <= (size_t)cfg_.max_series + 2;
+    bool any = false;
+    for (size_t c = 1; ok && c < cl.size(); ++c) {
+      ok = !cl[c].empty() && cl[c].size() <= (size_t)SL_MAX_T;
+      for (size_t j = 0; ok && j < cl[c].size(); ++j)
+        ok = cl[c][j] >= 0 && cl[c][j] <= INT32_MAX && (j == 0 || cl[c][j] > cl[c][j - 1]);
+      any = true;
+    }
+    const auto in_range = [&](int32_t c) { return c >= 0 && (size_t)c < cl.size(); };
+    ok = ok && any && in_range(cfg_.slo_default);
+    for (const auto& kv : cfg_.slo_services) ok = ok && in_range(kv.second);
+    if (!ok)
+      throw std::invalid_argument("sl stream: slo_classes must hold the empty class 0 and at least one class of 1 to 8 "
+                                  "strictly ascending thresholds in 0 .. 2147483647; every class index must name one");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -405,6 +422,30 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_wp_tmp_ = res_.dmalloc(wp_tmp_bytes_);
     res_.pin(h_wp_total_, 64);
     for (int k = 0; k < 2; ++k) ev_wp_[k] = res_.new_event();
+  }
+  if (want(OUT_SL)) {  // K17
+    const int32_t C = (int32_t)cfg_.slo_classes.size();  // (checked at the top of the constructor)
+    n_slo_classes_ = C;
+    d_slo_tab_ = (int32_t*)res_.dmalloc((size_t)C * (1 + SL_MAX_T) * 4);
+    {
+      std::vector<int32_t> tab((size_t)C * (1 + SL_MAX_T), 0);
+      for (int32_t c = 0; c < C; ++c) {
+        tab[(size_t)c] = (int32_t)cfg_.slo_classes[c].size();
+        for (size_t j = 0; j < cfg_.slo_classes[c].size(); ++j)
+          tab[(size_t)C + (size_t)c * SL_MAX_T + j] = (int32_t)cfg_.slo_classes[c][j];
+      }
+      HIP_OK(hipMemcpy(d_slo_tab_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    }
+    d_slo_cls_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    HIP_OK(hipMemset(d_slo_cls_, 0, (size_t)S * 4));  // class 0 until a series' class is uploaded
+    d_slo_rec_ = (SloRec*)res_.dmalloc((size_t)S * sizeof(SloRec));
+    d_slo_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_slo_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_slo_off_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    slo_tmp_bytes_ = apm_slo_tmp_bytes(S);
+    d_slo_tmp_ = res_.dmalloc(slo_tmp_bytes_);
+    res_.pin(h_slo_total_, 64);
+    for (int k = 0; k < 2; ++k) ev_slo_[k] = res_.new_event();
   }
   if (want(OUT_LH)) {  // K15
     d_hist_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
@@ -645,6 +686,7 @@ int32_t Engine::series_for(int32_t server, int32_t service) {
   h_thr_.resize((size_t)n_series_ * MAX_LAGS);
   h_infl_.resize((size_t)n_series_ * MAX_LAGS);
   h_hard_max_.push_back(cfg_.hard_max_ms);
+  if (want(OUT_SL)) h_slo_cls_.push_back(slo_class_of(s));  // (uploaded with the hard max)
   h_suppressed_.push_back(0);
   zscore_seen_.push_back(0);
   h_active_.push_back(0);
@@ -671,6 +713,12 @@ void Engine::apply_series_settings(int32_t s) {
   for (int l = 0; l < MAX_LAGS; ++l) { h_thr_[(size_t)s * MAX_LAGS + l] = thr[l]; h_infl_[(size_t)s * MAX_LAGS + l] = infl[l]; }
   h_hard_max_[s] = hm;
   h_suppressed_[s] = sup;
+}
+
+// K17: the class of a series is its service's (the names the z-score overrides use), else the default
+int32_t Engine::slo_class_of(int32_t s) const {
+  auto it = cfg_.slo_services.find(dict_.service_name(series_[s].service));
+  return it != cfg_.slo_services.end() ? it->second : cfg_.slo_default;
 }
 
 void Engine::refresh_series_settings() {
@@ -713,6 +761,28 @@ void Engine::upload_series_tables(int32_t lo) {
   h2d(d_emit_key_ + lo, ek, m * 8, stream_);
   h2d(d_suppressed_ + lo, sp, m, stream_);
   stage_done();
+  if (want(OUT_SL)) upload_slo_classes(lo);
+}
+
+// K17: the classes of series [lo, n) to the device, on the stats stream.  A full upload (lo == 0: a
+// reload, a restored or imported series table) resolves every class again -- it depends on the
+// service name and the construction-time tables only.
+void Engine::upload_slo_classes(int32_t lo) {
+  const int32_t n = n_series_;
+  lo = std::min(lo, slo_cls_uploaded_);  // (series no earlier upload carried go along)
+  if (lo == 0 || h_slo_cls_.size() != (size_t)n) {
+    h_slo_cls_.resize((size_t)n);
+    for (int32_t s = 0; s < n; ++s) h_slo_cls_[s] = slo_class_of(s);
+    lo = 0;
+  }
+  if (n > lo) {
+    const size_t mc = (size_t)(n - lo);
+    int32_t* cs = (int32_t*)stage(mc * 4);
+    std::memcpy(cs, h_slo_cls_.data() + lo, mc * 4);
+    h2d(d_slo_cls_ + lo, cs, mc * 4, stream_);
+    stage_done();
+  }
+  slo_cls_uploaded_ = n;
 }
 
 std::vector<uint64_t> Engine::cache_stats(bool drain) {
@@ -2302,6 +2372,7 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   // since K8 writes window cells, counts or spill lists (K10 / K11 / the gather read d_win_, the
   // release merges the tx pool, K12 formats), and the next append follows on this stream.
   if (want(OUT_WP)) winpct_rollover(wa, edge_ts);
+  if (want(OUT_SL)) slo_rollover(wa, edge_ts);  // K17: the same argument (it reads what K16 reads)
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2456,8 +2527,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[7];
-        int64_t counts[7] = {0, 0, 0, 0, 0, 0, 0};
+        std::string enc[8];
+        int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3016,6 +3087,85 @@ void Engine::download_winpcts(std::vector<int32_t>& m, std::vector<int32_t>& nan
   HIP_OK(hipStreamSynchronize(stream_));
 }
 
+// ---- K17: sl rows.  One row per st row whose window holds a non-NaN sample and whose service has
+// a threshold, in st order, with the st rows' timestamp: value pass over K8's window, then count /
+// scan / write of the text.
+void Engine::slo_rollover(const WindowArgs& wa, int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();
+  // series whose settings no upload_series_tables() carried yet (imported without a history, or
+  // still unseen by the z-score stage under Q4 emulation): their class before this rollover reads it
+  if (slo_cls_uploaded_ < n) upload_slo_classes(slo_cls_uploaded_);
+  const int32_t* nthr = d_slo_tab_;
+  const int32_t* thr = d_slo_tab_ + n_slo_classes_;
+  SloArgs va{};
+  va.w = wa;
+  va.cls = d_slo_cls_;
+  va.nthr = nthr;
+  va.thr = thr;
+  va.n_classes = n_slo_classes_;
+  va.rec = d_slo_rec_;
+  va.big_list = d_slo_big_;
+  va.big_n = d_slo_big_ + cfg_.max_series;
+  apm_slo_values(&va, stream_);
+  SloTextArgs ta{};
+  ta.rec = d_slo_rec_;
+  ta.cls = d_slo_cls_;
+  ta.nthr = nthr;
+  ta.thr = thr;
+  ta.n_classes = n_slo_classes_;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n;
+  ta.n_series = n;
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  ta.len = d_slo_len_;
+  ta.off = d_slo_off_;
+  const int k = slo_k_;
+  slo_k_ ^= 1;
+  out_wait(slo_task_[k]);  // slot k's previous D2H + emission is done
+  // the output bound needs no length pass: every row is at most apm_slo_row_bound bytes
+  const size_t cap = (size_t)n * apm_slo_row_bound(max_name_len_) + 64;
+  if (cap > slo_out_cap_[k]) d_slo_out_[k] = (char*)res_.regrow(d_slo_out_[k], slo_out_cap_[k], cap, stream_);
+  ta.out = d_slo_out_[k];
+  if (apm_slo_plan(&ta, d_slo_tmp_, slo_tmp_bytes_, stream_) != 0) throw std::runtime_error("objective scan failed");
+  apm_slo_write(&ta, stream_);
+  {
+    ExportArgs ex{};
+    ex.add(ta.off + n, h_slo_total_.d + k, 4);
+    apm_export(&ex, stream_);
+  }
+  HIP_OK(hipEventRecord(ev_slo_[k], stream_));
+  const char* dst = d_slo_out_[k];
+  slo_task_[k] = post_out([this, k, dst]() {
+    HIP_OK(hipEventSynchronize(ev_slo_[k]));
+    const size_t total = h_slo_total_[k];
+    if (!total) return;
+    res_.reserve(h_slo_text_[k], total, total * 2 + (1 << 20));
+    lane_d2h(h_slo_text_[k], dst, total);
+    lane_sync();
+    emit_bytes(OUT_SL, h_slo_text_[k], total);
+  });
+}
+
+void Engine::download_slo(std::vector<SloRec>& rec, std::vector<int32_t>& nthr) {
+  rec.clear(); nthr.clear();
+  if (!want(OUT_SL) || n_series_ == 0) return;
+  const size_t n = (size_t)n_series_;
+  rec.resize(n);
+  std::vector<int32_t> cls(n);
+  HIP_OK(hipMemcpyAsync(rec.data(), d_slo_rec_, n * sizeof(SloRec), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(cls.data(), d_slo_cls_, n * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  nthr.resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    const int32_t c = cls[i] > 0 && cls[i] < n_slo_classes_ ? cls[i] : 0;
+    nthr[i] = (int32_t)cfg_.slo_classes[(size_t)c].size();
+  }
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3156,7 +3306,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl"};
   return n[k];
 }
 

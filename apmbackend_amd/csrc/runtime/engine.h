@@ -118,6 +118,13 @@ struct EngineConfig {
   // construction (OUT_WP in `outputs` without a valid list is an error)
   int32_t n_win_pcts = 0;
   int32_t win_pcts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // sl stream (K17): the threshold table -- class 0 is "no row" (an empty list), every other class
+  // 1 to 8 strictly ascending thresholds in 0 .. INT32_MAX -- the class of each named service and
+  // the class of every other service; read at construction (OUT_SL in `outputs` without a class
+  // that has a threshold is an error)
+  std::vector<std::vector<int64_t>> slo_classes;
+  std::map<std::string, int32_t> slo_services;
+  int32_t slo_default = 0;
   int async_stats = 1;      // overlap batch i's stats with batch i+1's parse + join
   // RCCL watchdog: a collective not complete after this long (a dead or wedged peer) aborts the
   // communicator and throws, so the supervisor restarts the rank group from its checkpoint
@@ -143,12 +150,13 @@ struct EngineConfig {
 //   FS            z -> alerts/db  fs lines (one per series per LAG)
 //   AL            alerts -> db    al lines
 //   SX            new: per-JVM rollup fused with JMX / VM gauges (K14), one line per server
-enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, N_OUT };
+enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, N_OUT };
 // Streams whose pending text a checkpoint stores (checkpoint.cpp).  The version-9 layout holds
-// exactly these; lh and wp rows are taken by their consumer before a checkpoint and are not persisted.
+// exactly these; lh, wp and sl rows are taken by their consumer before a checkpoint and are not persisted.
 constexpr int N_OUT_CKPT = OUT_FB + 1;
-// streams written by the engine's output lane (released tx, st, fs, lh, wp); the stats thread owns the rest
-constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP);
+// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl); the stats thread owns the rest
+constexpr uint32_t kLaneKinds =
+    (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP) | (1u << OUT_SL);
 const char* out_kind_name(int k);
 int out_kind_of(const std::string& name);
 
@@ -715,7 +723,7 @@ class Engine {
   std::mutex out_pool_mu_;
   bool st_has_job_ = false, st_busy_ = false, st_stop_ = false;
   std::string st_error_;
-  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp streams (kLaneKinds)
+  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl streams (kLaneKinds)
   std::thread out_thread_;
   std::mutex out_mu_;
   std::condition_variable out_cv_;
@@ -1221,9 +1229,38 @@ class Engine {
   void download_winpcts(std::vector<int32_t>& m, std::vector<int32_t>& nan, std::vector<long long>& sum2);
  private:
 
+  // K17 sl rows (slo.hip), allocated when the stream is on: per service objective, how many of the
+  // window's samples lie at or below each threshold.  Queued next to K16 at the end of the
+  // rollover.  No device state outlives a rollover; the class table is constant, the class of a
+  // series is resolved where its hard max is (h_hard_max_) and uploaded with it.
+  int32_t* d_slo_tab_ = nullptr;                            // [C] thresholds per class, then [C][SL_MAX_T]
+  int32_t n_slo_classes_ = 0;
+  int32_t* d_slo_cls_ = nullptr;                            // [S]
+  std::vector<int32_t> h_slo_cls_;                          // its host mirror (stats thread)
+  SloRec* d_slo_rec_ = nullptr;                             // [S]
+  int32_t* d_slo_big_ = nullptr;                            // [S] block-pass list, [S] its length
+  uint32_t *d_slo_len_ = nullptr, *d_slo_off_ = nullptr;    // [S + 1]
+  void* d_slo_tmp_ = nullptr;
+  size_t slo_tmp_bytes_ = 0;
+  char* d_slo_out_[2] = {nullptr, nullptr};
+  size_t slo_out_cap_[2] = {0, 0};
+  PinnedBuf<char> h_slo_text_[2];  // pinned (output lane)
+  Mapped<uint32_t> h_slo_total_;   // pinned [2]: bytes of slot k's rows
+  hipEvent_t ev_slo_[2] = {nullptr, nullptr};
+  uint64_t slo_task_[2] = {0, 0};
+  int slo_k_ = 0;
+  int32_t slo_cls_uploaded_ = 0;                            // series whose class is on the device
+  int32_t slo_class_of(int32_t s) const;
+  void upload_slo_classes(int32_t lo);
+  void slo_rollover(const WindowArgs& wa, int64_t edge_ts);
+ public:
+  // (tests) the value pass' records of the last rollover, one per series
+  void download_slo(std::vector<SloRec>& rec, std::vector<int32_t>& nthr);
+ private:
+
   // text outputs
   std::string blob_[N_OUT];
-  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   std::shared_ptr<ByteSink> byte_sink_[N_OUT];
   bool fs_copy_ = false;
   bool db_copy_ = false;
@@ -1232,7 +1269,7 @@ class Engine {
   void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
-  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // K14 server rollup + exogenous context
   std::vector<double> h_ctx_;                    // [servers][CTX_FIELDS] (stats thread)
   bool ctx_dirty_ = false;

@@ -26,8 +26,8 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import as_bool, gpu_opt, window_percentiles, zscore_lag_settings
-from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, StatEntry, TxEntry, WindowPctEntry,
+from ..utils.config import as_bool, gpu_opt, latency_objectives, window_percentiles, zscore_lag_settings
+from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, StatEntry, TxEntry, WindowPctEntry, WindowSloEntry,
                              entry_from_csv, hist_bin, hist_lower, pct_ranks)
 from ..utils.timeparse import TzOffset, convert_string_date_to_ms, default_tz
 
@@ -668,7 +668,11 @@ class StatsOracle:
 
     def __init__(self, emit_stat: Callable[[str], None], emit_db: Callable[[str], None],
                  interval_len=10, window=30, buffer=6, emit_hist: Optional[Callable[[str], None]] = None,
-                 emit_pct: Optional[Callable[[str], None]] = None, percentiles: Iterable[int] = ()):
+                 emit_pct: Optional[Callable[[str], None]] = None, percentiles: Iterable[int] = (),
+                 emit_slo: Optional[Callable[[str], None]] = None, objectives: Optional[Dict[str, Any]] = None):
+        self.emit_slo = emit_slo    # sl rows (docs/OBJECTIVES.md); None = stream off
+        # config.parse_latency_objectives' result: {"default": [T, ...], "services": {name: [T, ...]}}
+        self.objectives = objectives or {"default": [], "services": {}}
         self.emit_hist = emit_hist  # lh rows (docs/HISTOGRAM.md); None = stream off
         self.emit_pct = emit_pct    # wp rows (docs/PERCENTILES.md); None = stream off
         self.percentiles = [int(q) for q in percentiles]  # q = p * 1000 (config.window_percentiles)
@@ -754,6 +758,18 @@ class StatsOracle:
             pcts.append((q, fin[lo] + fin[hi]))
         return WindowPctEntry(edge_ts, server, service, len(fin), len(flat) - len(fin), pcts).to_csv()
 
+    def slo_row(self, edge_ts: int, server: str, service: str, win: List[List[int]]) -> Optional[str]:
+        """The sl row of one window: for each threshold T of the service's objective, the number of
+        samples that are not NaN with v <= T; None without a threshold or without such a sample."""
+        thr = self.objectives["services"].get(service, self.objectives["default"])
+        flat = [v for arr in win for v in arr]
+        # the engine stores int32; anything else is its NaN sentinel (engine.cpp)
+        fin = [int(v) for v in flat if v == v and -2147483647 <= v <= 2147483647]
+        if not thr or not fin:
+            return None
+        le = [(t, sum(1 for v in fin if v <= t)) for t in thr]
+        return WindowSloEntry(edge_ts, server, service, len(fin), len(flat) - len(fin), le).to_csv()
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -792,6 +808,10 @@ class StatsOracle:
                     row = self.pct_row(edge_ts, server, service, win)
                     if row is not None:
                         self.emit_pct(row)
+                if self.emit_slo is not None and cnt != 0:
+                    row = self.slo_row(edge_ts, server, service, win)
+                    if row is not None:
+                        self.emit_slo(row)
 
 
 # ----------------------------------------------------------------------------- z-score oracle
@@ -1020,6 +1040,7 @@ class PipelineOracle:
         self.tx_out: List[str] = []
         self.lh: List[str] = []
         self.wp: List[str] = []
+        self.sl: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1029,7 +1050,9 @@ class PipelineOracle:
                               int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
                               emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None,
                               emit_pct=self.wp.append if window_percentiles(cfg) else None,
-                              percentiles=window_percentiles(cfg))
+                              percentiles=window_percentiles(cfg),
+                              emit_slo=self.sl.append if latency_objectives(cfg) else None,
+                              objectives=latency_objectives(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

@@ -21,7 +21,7 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 from .. import _native
 from ..models.oracle import file_kind, server_of
 from ..ops.parse_ref import tz_table
-from ..utils.config import window_percentiles
+from ..utils.config import latency_objectives, slo_tables, window_percentiles
 from ..utils.timeparse import TzOffset
 
 log = logging.getLogger("apm.pipeline")
@@ -31,10 +31,13 @@ KIND_CODE = {"SOAP": 0, "SERVER": 1, "APP": 2}
 # Output streams (engine.h OutKind); the bit index is the position in this tuple.
 OUT_KINDS = ("transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh")
 # Streams added after lh continue the enum here: OUT_KINDS keeps ending in "lh", which
-# tests/test_hist_engine_gpu.py pins.  ALL_OUT_KINDS is engine.h's OutKind in full.
+# tests/test_hist_engine_gpu.py pins.
 ALL_OUT_KINDS = OUT_KINDS + ("wp",)
-# keep_text=True materialises these; lh (K15 latency histograms) and wp (K16 window percentiles)
-# are opt-in through `outputs` only
+# ... and tests/test_winpct_engine_gpu.py pins ALL_OUT_KINDS; ENGINE_OUT_KINDS is engine.h's OutKind
+# in full and the tuple a stream's bit index comes from.
+ENGINE_OUT_KINDS = ALL_OUT_KINDS + ("sl",)
+# keep_text=True materialises these; lh (K15 latency histograms), wp (K16 window percentiles) and
+# sl (K17 threshold counts) are opt-in through `outputs` only
 KEEP_TEXT_KINDS = tuple(k for k in OUT_KINDS if k != "lh")
 # What the reference persists (db_insert queue): released + audit tx, fs, al.  `transactions`
 # and `st` are internal hand-offs that only the AMQP bridge needs.
@@ -45,21 +48,25 @@ MAX_LAGS = 16  # apm_types.h MAX_LAGS: LAG capacity per engine (each LAG is an H
 def output_mask(kinds) -> int:
     m = 0
     for k in kinds:
-        m |= 1 << ALL_OUT_KINDS.index(k)
+        m |= 1 << ENGINE_OUT_KINDS.index(k)
     return m
 
 
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
                   **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
-    materialises every stream but the opt-in lh / wp; `outputs` (iterable of ALL_OUT_KINDS) selects explicitly.
+    materialises every stream but the opt-in lh / wp / sl; `outputs` (iterable of ENGINE_OUT_KINDS) selects explicitly.
     The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
     existed, `outputs` was ignored under keep_text).  "wp" takes its percentiles from
-    gpu.windowPercentiles (ValueError when the list is missing or malformed)."""
+    gpu.windowPercentiles (ValueError when the list is missing or malformed), "sl" its thresholds
+    from gpu.latencyObjectives (likewise)."""
     g = cfg.get("gpu", {})
     win_pcts = window_percentiles(cfg)
     if "wp" in (outputs or ()) and not win_pcts:
         raise ValueError('outputs names "wp" but gpu.windowPercentiles is empty')
+    slo_classes, slo_services, slo_default = slo_tables(latency_objectives(cfg))
+    if "sl" in (outputs or ()) and not slo_classes:
+        raise ValueError('outputs names "sl" but gpu.latencyObjectives holds no threshold')
     zc = cfg["streamCalcZScore"]
     ac = cfg["streamProcessAlerts"]
     sc = cfg["streamCalcStats"]
@@ -127,6 +134,11 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         # K16: the percentiles of the wp stream as q = p * 1000, read at construction (a reload that
         # changes them is reported as needing a restart, like every other non-live setting)
         "win_pcts": win_pcts,
+        # K17: the sl stream's threshold table (class 0: no row) and each named service's class,
+        # likewise read at construction
+        "slo_classes": slo_classes,
+        "slo_services": slo_services,
+        "slo_default": slo_default,
     }
     # intervalLengthInSeconds only scales the TPM divisor: the bucket label is endTs without its
     # last 4 digits whatever the interval (stream_calc_stats.js:89-96, :186), as here
@@ -200,6 +212,13 @@ class APMEngine:
     LIVE_KEYS = ("lags", "lag_suppressed", "alert_window", "alert_threshold", "hard_min_ms", "hard_min_tpm",
                  "hard_max_ms", "both_only", "cooldown_ms", "interval_len", "window", "buffer")
 
+    @classmethod
+    def restart_required(cls, old: Dict[str, Any], new: Dict[str, Any]) -> List[str]:
+        """The engine settings that differ between two engine_config results and are not applied
+        live (win_pcts, the slo_* tables, ...)."""
+        return sorted(k for k in new if k not in cls.LIVE_KEYS and k not in ("outputs", "tz_table")
+                      and new[k] != old.get(k))
+
     def reload(self, cfg: Dict[str, Any], gen: Optional[int] = None) -> List[str]:
         """Config hot reload (the reference's watchAPMConfig callbacks): z-score defaults and
         per-service overrides re-applied to every series, LAGs added (empty history) or removed
@@ -207,8 +226,7 @@ class APMEngine:
         next batch boundary (the same boundary on every lock-step rank).  Returns the engine
         settings that changed but need a restart (they are not applied)."""
         new = engine_config(cfg, self.ecfg["device"], outputs=())
-        restart = sorted(k for k in new if k not in self.LIVE_KEYS and k not in ("outputs", "tz_table")
-                         and new[k] != self.ecfg.get(k))
+        restart = self.restart_required(self.ecfg, new)
         if restart:
             log.warning("config reload: %s changed but need a restart (not applied)", ", ".join(restart))
         if gen is None:

@@ -58,10 +58,12 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
     "lh": ("dbHistTable", ["timestamp", "server", "service", "count", "nan", "bins"]),
     # exact window percentiles (wp records, gpu.windowPercentiles): not part of the reference schema
     "wp": ("dbPctTable", ["timestamp", "server", "service", "count", "nan", "pcts"]),
+    # window threshold counts per latency objective (sl records, gpu.latencyObjectives): likewise
+    "sl": ("dbSloTable", ["timestamp", "server", "service", "count", "nan", "le"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl")
 # tables of the record types the reference does not know (its config has no key for them)
-DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct"}
+DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct", "sl": "apm_window_slo"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -145,7 +147,7 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = None
         elif c in _TS_COLS:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
-        elif c in ("stats", "entry", "bins", "pcts"):
+        elif c in ("stats", "entry", "bins", "pcts", "le"):
             out[c] = json.loads(v)
         elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan") or rtype == "jx" and c not in ("server",):
             f = float(v)
@@ -330,7 +332,7 @@ def make_writer(ins_cfg: Dict[str, Any]) -> Writer:
 def save_resume(path: str, buffers: Dict[str, Deque[Dict[str, Any]]]):
     """util_methods.saveToResumeFile with the Map replacer: {"dataType":"Map","value":[...]}
     (atomic: tmp + rename)."""
-    # the reference's four buffers always; the fleet, histogram and percentile buffers (our additions) only
+    # the reference's four buffers always; the fleet, histogram, percentile and objective buffers (our additions) only
     # when they hold rows
     doc = {"dataType": "Map", "value": [[t, [_json_row(r) for r in rows]] for t, rows in buffers.items()
                                         if t not in DEFAULT_TABLES or rows]}

@@ -23,7 +23,7 @@ import os
 import re
 import threading
 import time
-from typing import Any, Callable, Dict, Iterable, List, Optional
+from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 log = logging.getLogger("apm.config")
 
@@ -89,6 +89,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "histQueue": "latency_hist",      # amqp mode: the queue the lh records go to
     "windowPercentiles": [],          # K16 "wp" stream: exact window percentiles, e.g. [50, 90, 99, 99.9] (docs/PERCENTILES.md)
     "pctQueue": "window_pct",         # amqp mode: the queue the wp records go to
+    "latencyObjectives": None,        # K17 "sl" stream: per-service latency thresholds, {"default": [500, 2000], "services": {...}} (docs/OBJECTIVES.md)
+    "sloQueue": "window_slo",         # amqp mode: the queue the sl records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -138,6 +140,81 @@ def window_percentiles(cfg: Dict[str, Any]) -> List[int]:
     return parse_window_percentiles(gpu_opt(cfg, "windowPercentiles"))
 
 
+MAX_SLO_THRESHOLDS = 8   # kernel_api.h SL_MAX_T
+SLO_T_MAX = 2147483647   # samples are int32
+
+
+def _parse_threshold_list(where: str, v: Any) -> List[int]:
+    if not isinstance(v, (list, tuple)):
+        raise ValueError(f"gpu.latencyObjectives: {where} must be a list of integers, got {v!r}")
+    if len(v) > MAX_SLO_THRESHOLDS:
+        raise ValueError(f"gpu.latencyObjectives: {where} holds {len(v)} thresholds, at most {MAX_SLO_THRESHOLDS}")
+    out: List[int] = []
+    for t in v:
+        if isinstance(t, bool) or not isinstance(t, int):
+            raise ValueError(f"gpu.latencyObjectives: {where}: {t!r} is not an integer")
+        if not 0 <= t <= SLO_T_MAX:
+            raise ValueError(f"gpu.latencyObjectives: {where}: {t!r} is outside 0 .. {SLO_T_MAX}")
+        if out and t <= out[-1]:
+            raise ValueError(f"gpu.latencyObjectives: {where}: {t!r} does not ascend strictly")
+        out.append(t)
+    return out
+
+
+def parse_latency_objectives(v: Any) -> Optional[Dict[str, Any]]:
+    """gpu.latencyObjectives -> {"default": [T, ...], "services": {name: [T, ...]}} with every
+    list 0 to 8 strictly ascending integers in 0 .. 2147483647 (bool, float and str entries are
+    rejected: a threshold is compared with int32 samples, nothing is rounded).  None, or an object
+    without a non-empty list -> None (stream off); anything else raises ValueError."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.latencyObjectives: an object with 'default' and / or 'services', got {v!r}")
+    extra = set(v) - {"default", "services"}
+    if extra:
+        raise ValueError(f"gpu.latencyObjectives: unknown key(s) {sorted(extra)!r}")
+    default = _parse_threshold_list("default", v["default"]) if v.get("default") is not None else []
+    services = v.get("services")
+    if services is None:
+        services = {}
+    if not isinstance(services, dict):
+        raise ValueError(f"gpu.latencyObjectives: services must be an object, got {services!r}")
+    named: Dict[str, List[int]] = {}
+    for name, lst in services.items():
+        if not isinstance(name, str):
+            raise ValueError(f"gpu.latencyObjectives: service name {name!r} is not a string")
+        named[name] = _parse_threshold_list(f"services[{name!r}]", lst)
+    if not default and not any(named.values()):
+        return None
+    return {"default": default, "services": named}
+
+
+def latency_objectives(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """The validated gpu.latencyObjectives of a config (None: off)."""
+    return parse_latency_objectives(gpu_opt(cfg, "latencyObjectives"))
+
+
+def slo_tables(obj: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[str, int], int]:
+    """(classes, service -> class, default class) as the engine takes them: class 0 is "no row",
+    class 1 the default list when it is not empty, then one class per named service with a
+    non-empty list, in config order; a service named with [] maps to class 0."""
+    if not obj:
+        return [], {}, 0
+    classes: List[List[int]] = [[]]
+    default_class = 0
+    if obj["default"]:
+        classes.append(list(obj["default"]))
+        default_class = 1
+    services: Dict[str, int] = {}
+    for name, lst in obj["services"].items():
+        if lst:
+            classes.append(list(lst))
+            services[name] = len(classes) - 1
+        else:
+            services[name] = 0
+    return classes, services, default_class
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -171,6 +248,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
     cfg["gpu"] = merged
     if "windowPercentiles" in merged:
         parse_window_percentiles(merged["windowPercentiles"])  # ValueError: a bad list stops the load
+    if "latencyObjectives" in merged:
+        parse_latency_objectives(merged["latencyObjectives"])  # likewise
     return cfg
 
 

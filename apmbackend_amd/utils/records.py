@@ -390,6 +390,54 @@ class WindowPctEntry:
                 "pcts": {pct_text(q): (v // 2 if v % 2 == 0 else v / 2) for q, v in self.pcts}}
 
 
+# ---- sl: exact window threshold counts per service objective (docs/OBJECTIVES.md).  Integers only.
+SLO_T_MAX = 2147483647
+
+
+def _slo_int(s: str, max_len: int = 10) -> Optional[int]:
+    """A plain decimal of at most ``max_len`` digits (no sign, no spaces); None: malformed."""
+    if not (s.isascii() and s.isdigit() and len(s) <= max_len):
+        return None
+    return int(s)
+
+
+def slo_pairs_from_text(text: str) -> List[tuple]:
+    """``T:c,T:c,...`` -> [(T, c)]; a malformed pair is dropped (copyenc.cpp holds the same rules:
+    T and c of 1 to 10 digits, T <= 2147483647 and above the last pair kept)."""
+    out = []
+    for pr in (text or "").split(","):
+        t, sep, c = pr.partition(":")
+        tv, cv = _slo_int(t), _slo_int(c)
+        if sep and tv is not None and cv is not None and tv <= SLO_T_MAX and (not out or tv > out[-1][0]):
+            out.append((tv, cv))
+    return out
+
+
+@dataclass
+class WindowSloEntry:
+    """``sl|ts|server|service|m|nan|T:c,T:c,...`` -- for each threshold T of the service's latency
+    objective the number c of the K8 window's ``m`` non-NaN samples with elapsed <= T (cumulative;
+    ``nan`` counts the others), one row per st row with m >= 1 and at least one threshold (no
+    reference counterpart).  ``le`` holds (T, c) integer pairs in list order."""
+    timestamp: Num
+    server: str
+    service: str
+    count: Num
+    nan: Num
+    le: List[tuple]
+    type: str = "sl"
+
+    def to_csv(self) -> str:
+        pairs = ",".join(f"{int(t)}:{int(c)}" for t, c in self.le)
+        return (f"sl|{js_str(self.timestamp)}|{self.server}|{self.service}|{js_str(self.count)}|"
+                f"{js_str(self.nan)}|{pairs}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "count": _num_or_none(self.count), "nan": _num_or_none(self.nan),
+                "le": {str(int(t)): int(c) for t, c in self.le}}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -441,7 +489,11 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
             if q is not None and s2 is not None:  # (a malformed pair is dropped, as copyenc.cpp does)
                 pcts.append((q, s2))
         return WindowPctEntry(parse_int(a[1]), a[2], a[3], parse_int(a[4]), parse_int(a[5]), pcts)
+    if t == "sl":
+        a = _pad(arr, 7)
+        return WindowSloEntry(parse_int(a[1]), a[2], a[3], parse_int(a[4]), parse_int(a[5]),
+                              slo_pairs_from_text(a[6]))
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl")

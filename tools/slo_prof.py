@@ -1,0 +1,71 @@
+"""Driver for profiling the K17 sl kernels (slo.hip) next to K8, K16 and K12 on the headline shard.
+
+Feeds the shard tests/test_scale_gpu.py uses (8 JVMs x 10k services, 80k series): 33 ten-second
+batches of pre-history so the K8 window is full, then 20 more (one rollover each) with the sl
+stream on (default objective [500, 2000]) and, unless --no-wp, the wp stream with the list
+[50, 90, 99, 99.9], so that both text writers appear in one trace.  Run it under the kernel trace,
+in a run of its own, and compare k_slo_* with k_window_stats_h2, k_winpct_* and k_format_write
+from the same trace:
+
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/slo_prof.py
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from apmbackend_amd import _native  # noqa: E402
+from apmbackend_amd.models.pipeline import APMEngine  # noqa: E402
+from apmbackend_amd.utils.config import default_config  # noqa: E402
+
+START = 1578391200000
+STEP_MS = 10_000
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pre", type=int, default=33)
+    ap.add_argument("--rollovers", type=int, default=20)
+    ap.add_argument("--no-sl", action="store_true")
+    ap.add_argument("--no-wp", action="store_true")
+    ap.add_argument("--thresholds", default="500,2000")
+    ap.add_argument("--pcts", default="50,90,99,99.9")
+    a = ap.parse_args()
+    N = _native.load(build_if_missing=False)
+    gen = N.SynthGen({"servers": 8, "ejb_services": 6000, "provider_services": 4000, "tx_per_sec_per_server": 250.0,
+                      "seed": 3, "anomaly_services": 16, "anomaly_factor": 25.0,
+                      "anomaly_start_ms": START + 2 * STEP_MS})
+    C = default_config(replay=True)
+    C["gpu"].update({"timezone": "UTC", "maxSeries": 1 << 17, "batchBytes": 48 << 20, "maxLinesPerBatch": 1 << 20,
+                     "zscoreMeanMode": "rolling", "ringDtype": "float64", "bucketCellCapacity": 16})
+    outs = ("st", "fs", "al")
+    if not a.no_sl:
+        C["gpu"]["latencyObjectives"] = {"default": [int(t) for t in a.thresholds.split(",")]}
+        outs += ("sl",)
+    if not a.no_wp:
+        C["gpu"]["windowPercentiles"] = a.pcts.split(",")
+        outs += ("wp",)
+    eng = APMEngine(C, outputs=outs)
+    for path, kind, server in gen.files():
+        eng.add_file(path, {0: "SOAP", 1: "SERVER", 2: "APP"}[kind], server)
+    rows = {k: 0 for k in outs}
+    nbytes = {k: 0 for k in outs}
+    t0 = time.time()
+    for b in range(a.pre + a.rollovers):
+        data, chunks = gen.generate(START + (b + 1) * STEP_MS, 16)
+        eng.eng.process_batch(data, chunks, -1.0)
+        for k in outs:
+            blob = eng.take_bytes(k)
+            if b >= a.pre:
+                rows[k] += blob.count(b"\n")
+                nbytes[k] += len(blob)
+    m = eng.metrics()
+    per = max(a.rollovers, 1)
+    print(f"series {m['series']} rollovers {m['rollovers']} wall {time.time() - t0:.1f} s; last {a.rollovers} rollovers: "
+          + "; ".join(f"{k} rows {rows[k]} bytes {nbytes[k]} ({nbytes[k] // per} each)" for k in outs if k in ("st", "sl", "wp")))
+
+
+if __name__ == "__main__":
+    main()
