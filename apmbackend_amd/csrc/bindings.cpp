@@ -135,6 +135,11 @@ EngineConfig config_from(const py::dict& d) {
     if (d.contains("slo_services")) c.slo_services = d["slo_services"].cast<std::map<std::string, int32_t>>();
     c.slo_default = get<int32_t>(d, "slo_default", 0);
   }
+  if (d.contains("tk_k") && !d["tk_k"].is_none()) {  // (the constructor checks them when the tk stream is on)
+    c.tk_k = d["tk_k"].cast<int32_t>();
+    if (d.contains("tk_by")) c.tk_by = d["tk_by"].cast<std::vector<int32_t>>();
+    c.tk_min_tpm = get<double>(d, "tk_min_tpm", 0.0);
+  }
   c.async_stats = get<int>(d, "async_stats", c.async_stats);
   c.device_join = get<int>(d, "device_join", c.device_join);
   c.join_table_bits = get<int>(d, "join_table_bits", c.join_table_bits);
@@ -593,6 +598,22 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("leaderboard", [](Engine& e) {
+        // the last rollover's K18 records: (board, rank, series id, tpm, avg, p75, p95), raw doubles
+        std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> rows;
+        {
+          py::gil_scoped_release rel;
+          rows = e.leaderboard();
+        }
+        static const char* key_name[4] = {"tpm", "average", "per75", "per95"};
+        py::list out;
+        for (const auto& r : rows) {
+          const WinStat& w = std::get<3>(r);
+          out.append(py::make_tuple(key_name[std::get<0>(r) & 3], std::get<1>(r), std::get<2>(r),
+                                    w.tpm, w.avg, w.p75, w.p95));
+        }
+        return out;
+      })
       .def("winstats", [](Engine& e) {
         std::vector<WinStat> w;
         e.download_winstats(w);
@@ -635,15 +656,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[8];
-    int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::string out[9];
+    int64_t counts[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[8] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl"};
-    for (int k = 0; k < 8; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[9] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk"};
+    for (int k = 0; k < 9; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -832,6 +853,50 @@ PYBIND11_MODULE(_apm_native, m) {
   // its 32-lane group, and the write pass' LDS stage (tests bracket them)
   m.def("slo_group_max", []() { return apm_slo_group_max(); });
   m.def("slo_stage_bytes", []() { return apm_slo_stage_bytes(); });
+  // tk leaderboards (topk.hip): emission positions per block of the tile pass, and the survivors the
+  // final block reads per sweep (tests bracket both)
+  m.def("apm_topk_tile", []() { return apm_topk_tile(); });
+  m.def("apm_topk_final_span", []() { return apm_topk_final_span(); });
+  m.def("topk_select", [](const std::vector<std::tuple<double, double, double, double, int32_t>>& win_rows,
+                          const std::vector<int32_t>& perm, int32_t k, const std::vector<int32_t>& by, double min_tpm) {
+    // the two K18 kernels alone (test hook): win_rows are (tpm, avg, p75, p95, active) per series,
+    // perm the series in emission order; returns per board [(series, position)] in rank order
+    if (k < 1 || k > TK_MAX_K) throw std::invalid_argument("topk_select: k is 1 .. 128");
+    if (by.empty() || by.size() > (size_t)TK_MAX_BOARDS) throw std::invalid_argument("topk_select: 1 to 4 boards");
+    for (int32_t c : by)
+      if (c < TK_TPM || c > TK_P95) throw std::invalid_argument("topk_select: keys are 0 .. 3");
+    for (int32_t s : perm)
+      if (s < 0 || (size_t)s >= win_rows.size()) throw std::invalid_argument("topk_select: perm names no series");
+    const int32_t n = (int32_t)perm.size(), S = (int32_t)win_rows.size(), nb = (int32_t)by.size();
+    std::vector<WinStat> win((size_t)S);
+    for (int32_t s = 0; s < S; ++s) {
+      win[s].tpm = std::get<0>(win_rows[s]); win[s].avg = std::get<1>(win_rows[s]);
+      win[s].p75 = std::get<2>(win_rows[s]); win[s].p95 = std::get<3>(win_rows[s]);
+      win[s].n = 0; win[s].active = std::get<4>(win_rows[s]);
+    }
+    DevMem dwin((size_t)S * sizeof(WinStat)), dperm((size_t)n * 4), dsc(apm_topk_scratch_bytes(n, k, nb));
+    DevMem dout((size_t)nb * k * sizeof(TopKRec)), dn(64);
+    if (S) HIP_OK(hipMemcpy(dwin.p, win.data(), (size_t)S * sizeof(WinStat), hipMemcpyHostToDevice));
+    if (n) HIP_OK(hipMemcpy(dperm.p, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    TopKArgs a{};
+    a.win = dwin.as<WinStat>(); a.perm = dperm.as<int32_t>(); a.n = n; a.n_series = S; a.k = k; a.nb = nb;
+    for (int32_t b = 0; b < nb; ++b) a.by[b] = by[b];
+    a.min_tpm = min_tpm;
+    a.out = dout.as<TopKRec>(); a.out_n = dn.as<int32_t>();
+    apm_topk(&a, dsc.p, 0);
+    std::vector<TopKRec> rec((size_t)nb * k);
+    int32_t cnt[TK_MAX_BOARDS] = {0, 0, 0, 0};
+    HIP_OK(hipMemcpy(cnt, dn.p, (size_t)nb * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(rec.data(), dout.p, rec.size() * sizeof(TopKRec), hipMemcpyDeviceToHost));
+    py::list out;
+    for (int32_t b = 0; b < nb; ++b) {
+      py::list rows;
+      for (int32_t r = 0; r < std::min(std::max(cnt[b], 0), k); ++r)
+        rows.append(py::make_tuple(rec[(size_t)b * k + r].series, rec[(size_t)b * k + r].pos));
+      out.append(rows);
+    }
+    return out;
+  }, py::arg("win_rows"), py::arg("perm"), py::arg("k"), py::arg("by"), py::arg("min_tpm") = 0.0);
 
   register_tailer(m);
   register_synth(m);

@@ -253,6 +253,32 @@ struct SloTextArgs {
   uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
   char* out;                    // at least apm_slo_row_bound(max name bytes) * n bytes
 };
+// K18 tk rows: per-rollover top-K series leaderboards (topk.hip, docs/LEADERBOARD.md).  For each
+// board (key) the k candidates with the largest key value -- value descending as doubles, ties by
+// emission position ascending; a candidate is active, has a non-NaN key value and tpm >= min_tpm.
+constexpr int TK_MAX_BOARDS = 4;
+constexpr int TK_MAX_K = 128;
+enum TopKKey { TK_TPM = 0, TK_AVG, TK_P75, TK_P95 };
+struct TopKRec {
+  int32_t series, pos;          // series id and emission position
+  WinStat w;                    // the series' K8 result of this rollover
+};
+struct TopKArgs {
+  const WinStat* win;           // [n_series]
+  const int32_t* perm;          // [n] series in emission order (16-byte aligned)
+  int32_t n;
+  int32_t n_series;
+  int32_t k;                    // 1 .. TK_MAX_K
+  int32_t nb;                   // boards, 1 .. TK_MAX_BOARDS
+  int32_t by[TK_MAX_BOARDS];    // TopKKey per board
+  double min_tpm;
+  TopKRec* out;                 // [nb][k] rank order (host-mapped pinned memory or device memory)
+  int32_t* out_n;               // [nb] rows of each board
+  // set by apm_topk
+  int32_t tiles;
+  uint64_t* sc_key;             // [nb][tiles][k] tile survivors: order key (0: unused slot)
+  int32_t* sc_pos;              // [nb][tiles][k] their emission positions
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -385,6 +411,12 @@ void apm_slo_values(apm::SloArgs* a, hipStream_t stream);
 // length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_slo_plan(apm::SloTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_slo_write(apm::SloTextArgs* a, hipStream_t stream);
+// topk.hip
+int32_t apm_topk_tile();         // emission positions per block of the tile pass (tests bracket it)
+int32_t apm_topk_final_span();   // survivors the final block reads per sweep (it loops beyond)
+size_t apm_topk_scratch_bytes(int32_t n_max, int32_t k, int32_t nb);
+// both launches for all boards; `scratch` holds apm_topk_scratch_bytes(a->n, a->k, a->nb) bytes
+void apm_topk(apm::TopKArgs* a, void* scratch, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

@@ -834,6 +834,10 @@ std::string Engine::load_small_state(const std::string& path) {
     zscore_seen_ = rd.vec<int32_t>(); h_active_ = rd.vec<uint8_t>(); unseen_ = rd.vec<int32_t>();
     rd.raw(alias_thr_, sizeof(alias_thr_)); rd.raw(alias_infl_, sizeof(alias_infl_));
     series_.clear();
+    {
+      std::lock_guard<std::mutex> g(tk_mu_);  // (K18: the output lane's copy of the names)
+      tk_names_.clear();
+    }
     series_map_.clear();
     ser_tab_.clear();
     ser_raw_.clear();

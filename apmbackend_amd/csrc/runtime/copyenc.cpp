@@ -238,8 +238,8 @@ bool half_from_text(std::string_view s, int64_t& sum2) {
 }
 void append_i64(std::string& o, int64_t v) { o += std::to_string(v); }
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[8]*/) {
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[9]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -407,6 +407,28 @@ int encode_line(std::string_view line, std::string* out /*[8]*/) {
     copy_escape(o, js);
     o += '\n';
     return 7;
+  }
+  if (t == "tk") {  // leaderboard: timestamp, board, rank, server, service, tpm, average, per75, per95
+    // (utils/records.py entry_from_csv holds the same rules) a row with an unknown board, or a rank
+    // that is not 1 to 3 plain digits in 1 .. 128, is dropped
+    const std::string_view board = a.has(2) ? a.f[2] : std::string_view();
+    if (board != "tpm" && board != "average" && board != "per75" && board != "per95") return -1;
+    if (!a.has(3) || !all_digits(a.f[3], 3)) return -1;
+    int64_t rank = 0;
+    for (char ch : a.f[3]) rank = rank * 10 + (ch - '0');
+    if (rank < 1 || rank > 128) return -1;
+    std::string& o = out[8];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    append_i64(o, rank); o += '\t';
+    c_str(o, a, 4); o += '\t';
+    c_str(o, a, 5);
+    for (int i = 6; i < 10; ++i) {  // (numbers as the fs row's tpm: not finite -> NULL)
+      o += '\t';
+      c_num(o, a.has(i) ? parse_float(a.f[i]) : js::nan());
+    }
+    o += '\n';
+    return 8;
   }
   if (t == "jx") {
     std::string& o = out[3];

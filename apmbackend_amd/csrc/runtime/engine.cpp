@@ -236,6 +236,17 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       throw std::invalid_argument("sl stream: slo_classes must hold the empty class 0 and at least one class of 1 to 8 "
                                   "strictly ascending thresholds in 0 .. 2147483647; every class index must name one");
   }
+  if (want(OUT_TK)) {  // K18: the stream needs its setting (likewise before anything is allocated)
+    bool ok = cfg_.tk_k >= 1 && cfg_.tk_k <= TK_MAX_K && !cfg_.tk_by.empty() && cfg_.tk_by.size() <= (size_t)TK_MAX_BOARDS &&
+              std::isfinite(cfg_.tk_min_tpm) && cfg_.tk_min_tpm >= 0.0;
+    for (size_t i = 0; ok && i < cfg_.tk_by.size(); ++i) {
+      ok = cfg_.tk_by[i] >= TK_TPM && cfg_.tk_by[i] <= TK_P95;
+      for (size_t j = 0; ok && j < i; ++j) ok = cfg_.tk_by[j] != cfg_.tk_by[i];
+    }
+    if (!ok)
+      throw std::invalid_argument("tk stream: tk_k must lie in 1 .. 128, tk_by hold 1 to 4 distinct keys out of "
+                                  "0 .. 3 and tk_min_tpm be finite and >= 0");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -446,6 +457,16 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_slo_tmp_ = res_.dmalloc(slo_tmp_bytes_);
     res_.pin(h_slo_total_, 64);
     for (int k = 0; k < 2; ++k) ev_slo_[k] = res_.new_event();
+  }
+  if (want(OUT_TK)) {  // K18
+    tk_k_ = cfg_.tk_k;
+    const int32_t nb = (int32_t)cfg_.tk_by.size();
+    d_tk_scratch_ = res_.dmalloc(apm_topk_scratch_bytes(S, tk_k_, nb));
+    for (int k = 0; k < 2; ++k) {
+      res_.pin(h_tk_rec_[k], (size_t)nb * tk_k_ * sizeof(TopKRec));
+      res_.pin(h_tk_n_[k], 64);
+      ev_tk_[k] = res_.new_event();
+    }
   }
   if (want(OUT_LH)) {  // K15
     d_hist_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
@@ -2373,6 +2394,11 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   // release merges the tx pool, K12 formats), and the next append follows on this stream.
   if (want(OUT_WP)) winpct_rollover(wa, edge_ts);
   if (want(OUT_SL)) slo_rollover(wa, edge_ts);  // K17: the same argument (it reads what K16 reads)
+  // K18: last.  It reads d_win_ and d_perm_ only, and this position is safe for both: nothing
+  // queued after K8 writes d_win_ (K10 / K11 / the gather / K12 / K16 / K17 read it), d_perm_ is
+  // written by sync_format_tables() alone, which topk_rollover() calls on this stream ahead of its
+  // launches, and the next rollover's K8 -- the next writer of d_win_ -- follows on this stream.
+  if (want(OUT_TK)) topk_rollover(edge_ts);
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2527,8 +2553,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[8];
-        int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        std::string enc[9];
+        int64_t counts[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3166,6 +3192,71 @@ void Engine::download_slo(std::vector<SloRec>& rec, std::vector<int32_t>& nthr) 
   }
 }
 
+// ---- K18: tk rows.  Per board the k series with the largest key value, out of this rollover's
+// d_win_ in st order: two launches, the records land in pinned memory, the lane prints the rows
+// with the st row's helpers (at most 4 x 128 rows: no device text pass).
+void Engine::topk_rollover(int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();  // d_perm_ may not be uploaded yet when st / fs are off
+  {
+    // names of the series the lane has not seen (the stats thread owns series_ and its names)
+    std::lock_guard<std::mutex> g(tk_mu_);
+    if (tk_names_.size() > (size_t)n) tk_names_.clear();
+    for (int32_t s = (int32_t)tk_names_.size(); s < n; ++s)
+      tk_names_.emplace_back(servers_[series_[s].server], dict_.service_name(series_[s].service));
+  }
+  const int k = (int)(rollover_idx_ & 1);
+  out_wait(tk_task_[k]);  // slot k's previous rows are emitted
+  const int32_t nb = (int32_t)cfg_.tk_by.size();
+  TopKArgs ta{};
+  ta.win = d_win_;
+  ta.perm = d_perm_;
+  ta.n = n;
+  ta.n_series = n;
+  ta.k = tk_k_;
+  ta.nb = nb;
+  for (int32_t b = 0; b < nb; ++b) ta.by[b] = cfg_.tk_by[b];
+  ta.min_tpm = cfg_.tk_min_tpm;
+  ta.out = h_tk_rec_[k].d;
+  ta.out_n = h_tk_n_[k].d;
+  apm_topk(&ta, d_tk_scratch_, stream_);
+  HIP_OK(hipEventRecord(ev_tk_[k], stream_));
+  tk_task_[k] = post_out([this, k, nb, edge_ts]() {
+    HIP_OK(hipEventSynchronize(ev_tk_[k]));
+    static const char* key_name[4] = {"tpm", "average", "per75", "per95"};
+    std::string text;
+    std::vector<TopKRow> rows;
+    {
+      std::lock_guard<std::mutex> g(tk_mu_);
+      for (int32_t b = 0; b < nb; ++b) {
+        const int32_t cnt = std::min(std::max(h_tk_n_[k][b], 0), tk_k_);
+        for (int32_t r = 0; r < cnt; ++r) {
+          const TopKRec rec = h_tk_rec_[k][(size_t)b * tk_k_ + r];
+          if (rec.series < 0 || (size_t)rec.series >= tk_names_.size()) continue;
+          const auto& nm = tk_names_[(size_t)rec.series];
+          // fields 5.. are the st row's fields 3.. (fmt::st_line)
+          const std::string st = fmt::st_line(edge_ts, nm.first, nm.second, rec.w);
+          text += "tk|" + std::to_string(edge_ts) + "|" + key_name[cfg_.tk_by[b]] + "|" + std::to_string(r + 1) +
+                  st.substr(3 + std::to_string(edge_ts).size());
+          text += '\n';
+          rows.push_back(TopKRow{b, r + 1, rec.series, rec.w});
+        }
+      }
+      tk_last_.swap(rows);
+    }
+    if (!text.empty()) emit_bytes(OUT_TK, text.data(), text.size());
+  });
+}
+
+std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> Engine::leaderboard() {
+  flush();  // the stats thread and the output lane are idle
+  std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> out;
+  std::lock_guard<std::mutex> g(tk_mu_);
+  for (const TopKRow& r : tk_last_) out.emplace_back(cfg_.tk_by[(size_t)r.board], r.rank, r.series, r.w);
+  return out;
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3306,7 +3397,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk"};
   return n[k];
 }
 

@@ -24,6 +24,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -125,6 +126,12 @@ struct EngineConfig {
   std::vector<std::vector<int64_t>> slo_classes;
   std::map<std::string, int32_t> slo_services;
   int32_t slo_default = 0;
+  // tk stream (K18): rows per board (1 .. 128), the boards' keys in row order (1 to 4 distinct
+  // TopKKey values) and the tpm floor of a candidate (finite, >= 0); read at construction (OUT_TK
+  // in `outputs` without a valid setting is an error)
+  int32_t tk_k = 0;
+  std::vector<int32_t> tk_by;
+  double tk_min_tpm = 0.0;
   int async_stats = 1;      // overlap batch i's stats with batch i+1's parse + join
   // RCCL watchdog: a collective not complete after this long (a dead or wedged peer) aborts the
   // communicator and throws, so the supervisor restarts the rank group from its checkpoint
@@ -150,13 +157,13 @@ struct EngineConfig {
 //   FS            z -> alerts/db  fs lines (one per series per LAG)
 //   AL            alerts -> db    al lines
 //   SX            new: per-JVM rollup fused with JMX / VM gauges (K14), one line per server
-enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, N_OUT };
+enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, N_OUT };
 // Streams whose pending text a checkpoint stores (checkpoint.cpp).  The version-9 layout holds
-// exactly these; lh, wp and sl rows are taken by their consumer before a checkpoint and are not persisted.
+// exactly these; lh, wp, sl and tk rows are taken by their consumer before a checkpoint and are not persisted.
 constexpr int N_OUT_CKPT = OUT_FB + 1;
-// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl); the stats thread owns the rest
-constexpr uint32_t kLaneKinds =
-    (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP) | (1u << OUT_SL);
+// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk); the stats thread owns the rest
+constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP) |
+                                (1u << OUT_SL) | (1u << OUT_TK);
 const char* out_kind_name(int k);
 int out_kind_of(const std::string& name);
 
@@ -723,7 +730,7 @@ class Engine {
   std::mutex out_pool_mu_;
   bool st_has_job_ = false, st_busy_ = false, st_stop_ = false;
   std::string st_error_;
-  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl streams (kLaneKinds)
+  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk streams (kLaneKinds)
   std::thread out_thread_;
   std::mutex out_mu_;
   std::condition_variable out_cv_;
@@ -1258,9 +1265,31 @@ class Engine {
   void download_slo(std::vector<SloRec>& rec, std::vector<int32_t>& nthr);
  private:
 
+  // K18 tk rows (topk.hip), allocated when the stream is on: per board the k series with the
+  // largest key value at this rollover, selected on the device out of d_win_ in d_perm_ order.
+  // Queued last in the rollover.  The final kernel stores the records into one of two pinned
+  // slots; the output lane formats the (at most 512) rows.  No device state outlives a rollover.
+  void* d_tk_scratch_ = nullptr;
+  Mapped<TopKRec> h_tk_rec_[2];    // pinned [boards][k]
+  Mapped<int32_t> h_tk_n_[2];      // pinned [boards]
+  hipEvent_t ev_tk_[2] = {nullptr, nullptr};
+  uint64_t tk_task_[2] = {0, 0};
+  int tk_k_ = 0;
+  // The lane's own copy of every series' names, extended by the stats thread when it queues a
+  // rollover (tk_mu_): the lane never reads series_, servers_ or the service dictionary.
+  std::mutex tk_mu_;
+  std::vector<std::pair<std::string, std::string>> tk_names_;
+  struct TopKRow { int32_t board, rank, series; WinStat w; };
+  std::vector<TopKRow> tk_last_;   // the last rollover's records (tk_mu_)
+  void topk_rollover(int64_t edge_ts);
+ public:
+  // the last rollover's records per board in rank order: (the board's TopKKey, rank, series id, WinStat)
+  std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> leaderboard();
+ private:
+
   // text outputs
   std::string blob_[N_OUT];
-  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   std::shared_ptr<ByteSink> byte_sink_[N_OUT];
   bool fs_copy_ = false;
   bool db_copy_ = false;
@@ -1269,7 +1298,7 @@ class Engine {
   void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
-  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // K14 server rollup + exogenous context
   std::vector<double> h_ctx_;                    // [servers][CTX_FIELDS] (stats thread)
   bool ctx_dirty_ = false;

@@ -26,8 +26,9 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import as_bool, gpu_opt, latency_objectives, window_percentiles, zscore_lag_settings
-from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, StatEntry, TxEntry, WindowPctEntry, WindowSloEntry,
+from ..utils.config import as_bool, gpu_opt, latency_objectives, leaderboard, window_percentiles, zscore_lag_settings
+from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, StatEntry, TxEntry, WindowPctEntry,
+                             WindowSloEntry,
                              entry_from_csv, hist_bin, hist_lower, pct_ranks)
 from ..utils.timeparse import TzOffset, convert_string_date_to_ms, default_tz
 
@@ -669,7 +670,10 @@ class StatsOracle:
     def __init__(self, emit_stat: Callable[[str], None], emit_db: Callable[[str], None],
                  interval_len=10, window=30, buffer=6, emit_hist: Optional[Callable[[str], None]] = None,
                  emit_pct: Optional[Callable[[str], None]] = None, percentiles: Iterable[int] = (),
-                 emit_slo: Optional[Callable[[str], None]] = None, objectives: Optional[Dict[str, Any]] = None):
+                 emit_slo: Optional[Callable[[str], None]] = None, objectives: Optional[Dict[str, Any]] = None,
+                 emit_top: Optional[Callable[[str], None]] = None, board: Optional[Dict[str, Any]] = None):
+        self.emit_top = emit_top    # tk rows (docs/LEADERBOARD.md); None = stream off
+        self.board = board          # config.parse_leaderboard's result: {"k", "by", "minTpm"}
         self.emit_slo = emit_slo    # sl rows (docs/OBJECTIVES.md); None = stream off
         # config.parse_latency_objectives' result: {"default": [T, ...], "services": {name: [T, ...]}}
         self.objectives = objectives or {"default": [], "services": {}}
@@ -770,6 +774,27 @@ class StatsOracle:
         le = [(t, sum(1 for v in fin if v <= t)) for t in thr]
         return WindowSloEntry(edge_ts, server, service, len(fin), len(flat) - len(fin), le).to_csv()
 
+    def top_rows(self, st_rows: List[str]) -> List[str]:
+        """The tk rows of one rollover from its st rows (in emission order): per board of
+        ``self.board["by"]`` the k rows with the largest value of that field -- the value the st
+        row carries, i.e. after its rounding -- among the rows whose value is not NaN and whose
+        tpm is at least minTpm; ties keep the st order."""
+        ents = [entry_from_csv(r) for r in st_rows]
+        out: List[str] = []
+        for key in self.board["by"]:
+            cands = []
+            for pos, e in enumerate(ents):
+                v = getattr(e, key)
+                if v is None or v != v or not e.tpm >= self.board["minTpm"]:
+                    continue
+                cands.append((-v, pos))
+            cands.sort()
+            for rank, (_, pos) in enumerate(cands[:self.board["k"]], 1):
+                e = ents[pos]
+                out.append(LeaderboardEntry(e.timestamp, key, rank, e.server, e.service, e.tpm, e.average, e.per75,
+                                            e.per95).to_csv())
+        return out
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -782,6 +807,7 @@ class StatsOracle:
         if self.emit_hist is not None:
             for row in self.hist_rows(self.latest - 1 if prev is None else prev):
                 self.emit_hist(row)
+        st_rows: List[str] = []
         for server, srv in self.servers.items():
             for service, svc in srv.items():
                 win: List[List[int]] = []
@@ -804,6 +830,8 @@ class StatsOracle:
                 tpm = cnt / (self.window * self.interval_len / 60.0)
                 st = StatEntry.make(edge_ts, server, service, tpm, avg, p75, p95)
                 self.emit_stat(st.to_csv())
+                if self.emit_top is not None:
+                    st_rows.append(st.to_csv())
                 if self.emit_pct is not None and cnt != 0:
                     row = self.pct_row(edge_ts, server, service, win)
                     if row is not None:
@@ -812,6 +840,9 @@ class StatsOracle:
                     row = self.slo_row(edge_ts, server, service, win)
                     if row is not None:
                         self.emit_slo(row)
+        if self.emit_top is not None:
+            for row in self.top_rows(st_rows):
+                self.emit_top(row)
 
 
 # ----------------------------------------------------------------------------- z-score oracle
@@ -1041,6 +1072,7 @@ class PipelineOracle:
         self.lh: List[str] = []
         self.wp: List[str] = []
         self.sl: List[str] = []
+        self.tk: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1052,7 +1084,9 @@ class PipelineOracle:
                               emit_pct=self.wp.append if window_percentiles(cfg) else None,
                               percentiles=window_percentiles(cfg),
                               emit_slo=self.sl.append if latency_objectives(cfg) else None,
-                              objectives=latency_objectives(cfg))
+                              objectives=latency_objectives(cfg),
+                              emit_top=self.tk.append if leaderboard(cfg) else None,
+                              board=leaderboard(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

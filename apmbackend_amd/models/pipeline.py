@@ -21,7 +21,7 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 from .. import _native
 from ..models.oracle import file_kind, server_of
 from ..ops.parse_ref import tz_table
-from ..utils.config import latency_objectives, slo_tables, window_percentiles
+from ..utils.config import LEADERBOARD_KEYS, latency_objectives, leaderboard, slo_tables, window_percentiles
 from ..utils.timeparse import TzOffset
 
 log = logging.getLogger("apm.pipeline")
@@ -34,10 +34,13 @@ OUT_KINDS = ("transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh
 # tests/test_hist_engine_gpu.py pins.
 ALL_OUT_KINDS = OUT_KINDS + ("wp",)
 # ... and tests/test_winpct_engine_gpu.py pins ALL_OUT_KINDS; ENGINE_OUT_KINDS is engine.h's OutKind
-# in full and the tuple a stream's bit index comes from.
+# up to sl.
 ENGINE_OUT_KINDS = ALL_OUT_KINDS + ("sl",)
-# keep_text=True materialises these; lh (K15 latency histograms), wp (K16 window percentiles) and
-# sl (K17 threshold counts) are opt-in through `outputs` only
+# ... and tests/test_slo_model.py pins ENGINE_OUT_KINDS; NATIVE_OUT_KINDS is engine.h's OutKind in
+# full and the tuple a stream's bit index comes from.
+NATIVE_OUT_KINDS = ENGINE_OUT_KINDS + ("tk",)
+# keep_text=True materialises these; lh (K15 latency histograms), wp (K16 window percentiles),
+# sl (K17 threshold counts) and tk (K18 leaderboards) are opt-in through `outputs` only
 KEEP_TEXT_KINDS = tuple(k for k in OUT_KINDS if k != "lh")
 # What the reference persists (db_insert queue): released + audit tx, fs, al.  `transactions`
 # and `st` are internal hand-offs that only the AMQP bridge needs.
@@ -48,18 +51,18 @@ MAX_LAGS = 16  # apm_types.h MAX_LAGS: LAG capacity per engine (each LAG is an H
 def output_mask(kinds) -> int:
     m = 0
     for k in kinds:
-        m |= 1 << ENGINE_OUT_KINDS.index(k)
+        m |= 1 << NATIVE_OUT_KINDS.index(k)
     return m
 
 
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
                   **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
-    materialises every stream but the opt-in lh / wp / sl; `outputs` (iterable of ENGINE_OUT_KINDS) selects explicitly.
+    materialises every stream but the opt-in lh / wp / sl / tk; `outputs` (iterable of NATIVE_OUT_KINDS) selects explicitly.
     The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
     existed, `outputs` was ignored under keep_text).  "wp" takes its percentiles from
     gpu.windowPercentiles (ValueError when the list is missing or malformed), "sl" its thresholds
-    from gpu.latencyObjectives (likewise)."""
+    from gpu.latencyObjectives (likewise), "tk" its boards from gpu.leaderboard (likewise)."""
     g = cfg.get("gpu", {})
     win_pcts = window_percentiles(cfg)
     if "wp" in (outputs or ()) and not win_pcts:
@@ -67,6 +70,9 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
     slo_classes, slo_services, slo_default = slo_tables(latency_objectives(cfg))
     if "sl" in (outputs or ()) and not slo_classes:
         raise ValueError('outputs names "sl" but gpu.latencyObjectives holds no threshold')
+    board = leaderboard(cfg)
+    if "tk" in (outputs or ()) and not board:
+        raise ValueError('outputs names "tk" but gpu.leaderboard is not set')
     zc = cfg["streamCalcZScore"]
     ac = cfg["streamProcessAlerts"]
     sc = cfg["streamCalcStats"]
@@ -139,6 +145,11 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         "slo_classes": slo_classes,
         "slo_services": slo_services,
         "slo_default": slo_default,
+        # K18: the tk stream's rows per board, the boards' keys (kernel_api.h TopKKey codes, in row
+        # order) and the tpm floor, likewise read at construction (None: gpu.leaderboard is not set)
+        "tk_k": board["k"] if board else None,
+        "tk_by": [LEADERBOARD_KEYS.index(b) for b in board["by"]] if board else [],
+        "tk_min_tpm": board["minTpm"] if board else 0.0,
     }
     # intervalLengthInSeconds only scales the TPM divisor: the bucket label is endTs without its
     # last 4 digits whatever the interval (stream_calc_stats.js:89-96, :186), as here
@@ -215,7 +226,7 @@ class APMEngine:
     @classmethod
     def restart_required(cls, old: Dict[str, Any], new: Dict[str, Any]) -> List[str]:
         """The engine settings that differ between two engine_config results and are not applied
-        live (win_pcts, the slo_* tables, ...)."""
+        live (win_pcts, the slo_* tables, the tk_* settings, ...)."""
         return sorted(k for k in new if k not in cls.LIVE_KEYS and k not in ("outputs", "tz_table")
                       and new[k] != old.get(k))
 

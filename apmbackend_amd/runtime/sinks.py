@@ -60,10 +60,13 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
     "wp": ("dbPctTable", ["timestamp", "server", "service", "count", "nan", "pcts"]),
     # window threshold counts per latency objective (sl records, gpu.latencyObjectives): likewise
     "sl": ("dbSloTable", ["timestamp", "server", "service", "count", "nan", "le"]),
+    # per-rollover top-K series leaderboards (tk records, gpu.leaderboard): likewise
+    "tk": ("dbTopTable", ["timestamp", "board", "rank", "server", "service", "tpm", "average", "per75", "per95"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk")
 # tables of the record types the reference does not know (its config has no key for them)
-DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct", "sl": "apm_window_slo"}
+DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct", "sl": "apm_window_slo",
+                  "tk": "apm_leaderboard"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -149,7 +152,7 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
         elif c in ("stats", "entry", "bins", "pcts", "le"):
             out[c] = json.loads(v)
-        elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan") or rtype == "jx" and c not in ("server",):
+        elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan", "rank", "average", "per75", "per95") or rtype == "jx" and c not in ("server",):
             f = float(v)
             out[c] = int(f) if f.is_integer() and "." not in v and "e" not in v else f
         else:
@@ -332,7 +335,7 @@ def make_writer(ins_cfg: Dict[str, Any]) -> Writer:
 def save_resume(path: str, buffers: Dict[str, Deque[Dict[str, Any]]]):
     """util_methods.saveToResumeFile with the Map replacer: {"dataType":"Map","value":[...]}
     (atomic: tmp + rename)."""
-    # the reference's four buffers always; the fleet, histogram, percentile and objective buffers (our additions) only
+    # the reference's four buffers always; the fleet, histogram, percentile, objective and leaderboard buffers (our additions) only
     # when they hold rows
     doc = {"dataType": "Map", "value": [[t, [_json_row(r) for r in rows]] for t, rows in buffers.items()
                                         if t not in DEFAULT_TABLES or rows]}

@@ -19,6 +19,7 @@ import decimal
 import hashlib
 import json
 import logging
+import math
 import os
 import re
 import threading
@@ -91,6 +92,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "pctQueue": "window_pct",         # amqp mode: the queue the wp records go to
     "latencyObjectives": None,        # K17 "sl" stream: per-service latency thresholds, {"default": [500, 2000], "services": {...}} (docs/OBJECTIVES.md)
     "sloQueue": "window_slo",         # amqp mode: the queue the sl records go to
+    "leaderboard": None,              # K18 "tk" stream: per-rollover top-K series, {"k": 20, "by": ["per95", "average", "tpm"], "minTpm": 0} (docs/LEADERBOARD.md)
+    "topQueue": "leaderboard",        # amqp mode: the queue the tk records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -215,6 +218,45 @@ def slo_tables(obj: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[str
     return classes, services, default_class
 
 
+LEADERBOARD_KEYS = ("tpm", "average", "per75", "per95")  # kernel_api.h TopKKey, in code order
+LEADERBOARD_MAX_K = 128                                  # kernel_api.h TK_MAX_K
+LEADERBOARD_MAX_BOARDS = 4
+
+
+def parse_leaderboard(v: Any) -> Optional[Dict[str, Any]]:
+    """gpu.leaderboard -> {"k": int, "by": [name, ...], "minTpm": float}: ``k`` a JSON integer in
+    1 .. 128 (bool, float and str are rejected), ``by`` 1 to 4 distinct names out of tpm, average,
+    per75, per95 (the boards, in row order), ``minTpm`` optional (default 0), a finite number >= 0.
+    None -> None (stream off); anything else raises ValueError."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.leaderboard: an object with 'k', 'by' and optionally 'minTpm', got {v!r}")
+    extra = set(v) - {"k", "by", "minTpm"}
+    if extra:
+        raise ValueError(f"gpu.leaderboard: unknown key(s) {sorted(extra, key=str)!r}")
+    k = v.get("k")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= LEADERBOARD_MAX_K:
+        raise ValueError(f"gpu.leaderboard: k must be an integer in 1 .. {LEADERBOARD_MAX_K}, got {k!r}")
+    by = v.get("by")
+    if not isinstance(by, (list, tuple)) or not 1 <= len(by) <= LEADERBOARD_MAX_BOARDS:
+        raise ValueError(f"gpu.leaderboard: by must list 1 to {LEADERBOARD_MAX_BOARDS} keys, got {by!r}")
+    for name in by:
+        if not isinstance(name, str) or name not in LEADERBOARD_KEYS:
+            raise ValueError(f"gpu.leaderboard: by: {name!r} is not one of {', '.join(LEADERBOARD_KEYS)}")
+    if len(set(by)) != len(by):
+        raise ValueError(f"gpu.leaderboard: by names a key twice: {list(by)!r}")
+    m = v.get("minTpm", 0)
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or not math.isfinite(m) or m < 0:
+        raise ValueError(f"gpu.leaderboard: minTpm must be a finite number >= 0, got {m!r}")
+    return {"k": k, "by": list(by), "minTpm": float(m)}
+
+
+def leaderboard(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """The validated gpu.leaderboard of a config (None: off)."""
+    return parse_leaderboard(gpu_opt(cfg, "leaderboard"))
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -250,6 +292,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         parse_window_percentiles(merged["windowPercentiles"])  # ValueError: a bad list stops the load
     if "latencyObjectives" in merged:
         parse_latency_objectives(merged["latencyObjectives"])  # likewise
+    if "leaderboard" in merged:
+        parse_leaderboard(merged["leaderboard"])  # likewise
     return cfg
 
 

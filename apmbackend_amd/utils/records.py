@@ -438,6 +438,45 @@ class WindowSloEntry:
                 "le": {str(int(t)): int(c) for t, c in self.le}}
 
 
+# ---- tk: per-rollover top-K series leaderboards (docs/LEADERBOARD.md)
+LEADERBOARD_KEYS = ("tpm", "average", "per75", "per95")
+LEADERBOARD_MAX_K = 128
+
+
+def leaderboard_rank_from_text(s: Optional[str]) -> Optional[int]:
+    """A rank of 1 to 3 plain digits in 1 .. 128; None: malformed (copyenc.cpp holds the same rule)."""
+    r = _slo_int(s, 3) if s is not None else None
+    return r if r is not None and 1 <= r <= LEADERBOARD_MAX_K else None
+
+
+@dataclass
+class LeaderboardEntry:
+    """``tk|ts|board|rank|server|service|tpm|average|per75|per95`` -- at a rollover, the series of
+    rank ``rank`` (1 = largest) on the board of key ``board`` (tpm, average, per75 or per95) among
+    this rank's series, with the four numbers of the series' st row of the same rollover (no
+    reference counterpart)."""
+    timestamp: Num
+    board: str
+    rank: int
+    server: str
+    service: str
+    tpm: float
+    average: float
+    per75: float
+    per95: float
+    type: str = "tk"
+
+    def to_csv(self) -> str:
+        return (f"tk|{js_str(self.timestamp)}|{self.board}|{int(self.rank)}|{self.server}|{self.service}|"
+                f"{nf(self.tpm, 2)}|{nf(self.average)}|{nf(self.per75)}|{nf(self.per95)}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        n = _num_or_none
+        return {"timestamp": _ms_to_dt(self.timestamp), "board": self.board, "rank": int(self.rank),
+                "server": self.server, "service": self.service, "tpm": n(self.tpm), "average": n(self.average),
+                "per75": n(self.per75), "per95": n(self.per95)}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -493,7 +532,14 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
         a = _pad(arr, 7)
         return WindowSloEntry(parse_int(a[1]), a[2], a[3], parse_int(a[4]), parse_int(a[5]),
                               slo_pairs_from_text(a[6]))
+    if t == "tk":
+        a = _pad(arr, 10)
+        rank = leaderboard_rank_from_text(a[3])
+        if a[2] not in LEADERBOARD_KEYS or rank is None:  # (a malformed row is dropped, as copyenc.cpp does)
+            return None
+        pf = parse_float
+        return LeaderboardEntry(parse_int(a[1]), a[2], rank, a[4], a[5], pf(a[6]), pf(a[7]), pf(a[8]), pf(a[9]))
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk")
