@@ -584,7 +584,10 @@ __global__ __launch_bounds__(TB) void k_host_flags_bytes(const Event* __restrict
   val[i] = sel_pack(fl);
 }
 
-// host / map-header / walk lists, in event order (devscan.h over the batch's events only)
+// host / map-header / walk lists, in event order (devscan.h over the batch's events only).  Only
+// the host reads the host events and their indices, so `out` / `out_idx` are the device views of
+// its pinned buffers: the scatter's stores are the read-back (plain stores over the host link; the
+// host reads them after the parse stream's synchronize).
 struct SelValF {
   const uint64_t* val;
   __device__ uint64_t operator()(uint32_t i) const { return val[i]; }
@@ -2538,14 +2541,15 @@ size_t apm_dj_tmp_bytes(uint32_t max_ev, uint32_t max_out) {
   return q.need + 4096;
 }
 
+// The two counters the selection appends to -- the totals (a->n_host) and the byte-event list
+// sizes (dj_select_list_n) -- are zeroed by the caller earlier on the same stream: the parse
+// chain's chunk-table upload carries the fills (DeviceJoin::chunk_upload).
 int apm_dj_select_host(DJArgs* a, const uint32_t* d_n_ev, uint32_t max_ev, hipStream_t s) {
-  HIP_OK(hipMemsetAsync(a->n_host, 0, sizeof(SelCount), s));
   if (max_ev == 0) return 0;
   // the listed byte events: scratch in sel_pos (written by the selection scan only afterwards;
   // max_ev + 64 u64 words hold the max_ev u32 list entries and the two counts)
   uint32_t* list = reinterpret_cast<uint32_t*>(a->sel_pos);
-  uint32_t* list_n = list + max_ev;
-  HIP_OK(hipMemsetAsync(list_n, 0, 8, s));
+  uint32_t* list_n = dj_select_list_n(a->sel_pos, max_ev);
   const dim3 grid((max_ev + TB - 1) / TB);
   hipLaunchKernelGGL(k_host_flags, grid, dim3(TB), 0, s, a->ev, d_n_ev, a->bytes, a->host_flag, a->sel_val, a->aud,
                      a->n_host, max_ev, list, list_n);

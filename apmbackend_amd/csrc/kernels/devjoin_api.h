@@ -52,6 +52,13 @@ struct SelCount {
   uint32_t aud_bytes; // bytes of map / stopWatch name lines (bound of the carry text they add)
 };
 
+// The selection's byte-event list lives in DJArgs::sel_pos (max_ev u32 entries); its two sizes
+// (front / back) are the two u32 behind it.  The caller of apm_dj_select_host zeroes them, and
+// DJArgs::n_host, earlier on the same stream.
+inline uint32_t* dj_select_list_n(uint64_t* sel_pos, uint32_t max_ev) {
+  return reinterpret_cast<uint32_t*>(sel_pos) + max_ev;
+}
+
 // Everything one batch of the device join touches.  Device pointers unless noted.
 struct DJArgs {
   // ---- batch inputs
@@ -79,8 +86,8 @@ struct DJArgs {
   uint8_t* host_flag;             // [n_ev] SEL_* bits
   uint64_t* sel_val;              // [n_ev + 1] per-event counts, packed (devjoin.hip sel_unpack)
   uint64_t* sel_pos;              // [n_ev + 1] exclusive scan
-  Event* host_ev;                 // compacted host events
-  uint32_t* host_ev_idx;
+  Event* host_ev;                 // compacted host events (device view of pinned host memory)
+  uint32_t* host_ev_idx;          // their event indices (likewise)
   uint32_t* mh_idx;               // compacted audit map / header events (event indices)
   uint32_t* walk_idx;             // compacted audit walk events (event indices, line order per file)
   SelCount* n_host;               // device totals

@@ -96,7 +96,8 @@ struct RollupArgs {
   double* out;                    // [n_servers][ROLLUP_OUT]
 };
 
-// apm_copy_segs: up to 8 device -> device / host-mapped copies in one launch (stats.hip)
+// apm_copy_segs: up to 8 device -> device / host-mapped copies in one launch (stats.hip); a
+// segment without a source is a zero fill of its destination
 struct CopySeg {
   void* dst;
   const void* src;
@@ -107,6 +108,9 @@ struct CopySegs {
   int32_t n = 0;
   void add(void* d, const void* s, size_t b) {
     if (b) seg[n++] = CopySeg{d, s, b};
+  }
+  void zero(void* d, size_t b) {
+    if (b) seg[n++] = CopySeg{d, nullptr, b};
   }
 };
 

@@ -867,12 +867,17 @@ __global__ void k_ck_pack(const int32_t* __restrict__ cells, const int32_t* __re
 
 // Up to 8 copies in one launch (blockIdx.y = the copy): the join's sync-C read-back (counts,
 // rollover candidates, unresolved series, audit_db text) into host-mapped pinned memory as one
-// kernel instead of a blit per array.
+// kernel instead of a blit per array.  The parse chain's chunk tables go up the same way, with
+// the zero fills (segments without a source) of the counters its later kernels append to.
 __global__ void k_copy_segs(apm::CopySegs c) {
   const apm::CopySeg& g = c.seg[blockIdx.y];
   if (blockIdx.y >= (unsigned)c.n) return;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (!g.src) {
+    for (size_t i = t; i < g.bytes; i += stride) ((uint8_t*)g.dst)[i] = 0;
+    return;
+  }
   const uintptr_t al = (uintptr_t)g.dst | (uintptr_t)g.src;
   if ((al & 15) == 0) {
     const size_t n16 = g.bytes / 16;

@@ -69,16 +69,15 @@ DeviceJoin::DeviceJoin(const DevJoinConfig& cfg, Dictionary* dict, const std::ve
     s.d_bytes = (uint8_t*)res_.dmalloc_on(stream_, cfg_.max_batch_bytes + 256);
     s.d_events = (Event*)res_.dmalloc_on(stream_, (size_t)E * sizeof(Event));
     s.host_flag = (uint8_t*)res_.dmalloc_on(stream_, E + 64);
-    s.d_host_ev = (Event*)res_.dmalloc_on(stream_, (size_t)E * sizeof(Event));
-    s.d_host_idx = (uint32_t*)res_.dmalloc_on(stream_, (size_t)E * 4);
     s.d_mh_idx = (uint32_t*)res_.dmalloc_on(stream_, (size_t)E * 4);
     s.d_walk_idx = (uint32_t*)res_.dmalloc_on(stream_, (size_t)E * 4);
     s.d_aud = (AudF*)res_.dmalloc_on(stream_, (size_t)E * sizeof(AudF));
     s.d_n_host = (SelCount*)res_.dmalloc_on(stream_, 64);
+    // (every event of a batch may be a host event: E >= max_events entries each)
     res_.pin(s.h_host_ev, (size_t)E * sizeof(Event));
     res_.pin(s.h_host_idx, (size_t)E * 4);
     res_.pin(s.h_n_host, 64);
-    std::memset(s.h_n_host, 0, 64);
+    std::memset(s.h_n_host.h, 0, 64);
     s.d_chunk_next = (int32_t*)res_.dmalloc_on(stream_, ((size_t)cfg_.max_chunks + 2) * 4);
     s.d_chunk_first = (uint8_t*)res_.dmalloc_on(stream_, (size_t)cfg_.max_chunks + 2);
     res_.pin(s.h_chunk_next, ((size_t)cfg_.max_chunks + 2) * 4);
@@ -230,8 +229,8 @@ void DeviceJoin::select_host(int k, const uint32_t* d_n_ev, uint32_t max_ev, hip
   a.aud = s.d_aud;
   a.sel_val = d_sel_val_;
   a.sel_pos = d_sel_pos_;
-  a.host_ev = s.d_host_ev;
-  a.host_ev_idx = s.d_host_idx;
+  a.host_ev = s.h_host_ev.d;  // the scatter's stores are the read-back
+  a.host_ev_idx = s.h_host_idx.d;
   a.mh_idx = s.d_mh_idx;
   a.walk_idx = s.d_walk_idx;
   a.n_host = s.d_n_host;
@@ -239,15 +238,27 @@ void DeviceJoin::select_host(int k, const uint32_t* d_n_ev, uint32_t max_ev, hip
   a.tmp_bytes = sel_tmp_bytes_;
   if (apm_dj_select_host(&a, d_n_ev, std::min<uint32_t>(max_ev, cfg_.max_events), ps) != 0)
     throw std::runtime_error("device join: scan scratch too small");
-  HIP_OK(hipMemcpyAsync(s.h_n_host, s.d_n_host, sizeof(SelCount), hipMemcpyDeviceToHost, ps));
-  // speculative copy of the host events (last count + 25 %): usually all of them
-  s.spec = std::min<uint32_t>(cfg_.max_events, last_host_ + last_host_ / 4 + 256);
-  HIP_OK(hipMemcpyAsync(s.h_host_ev, s.d_host_ev, (size_t)s.spec * sizeof(Event), hipMemcpyDeviceToHost, ps));
-  HIP_OK(hipMemcpyAsync(s.h_host_idx, s.d_host_idx, (size_t)s.spec * 4, hipMemcpyDeviceToHost, ps));
+}
+
+void DeviceJoin::export_select(int k, CopySegs& cs) {
+  Slot& s = sl_[k];
+  cs.add(s.h_n_host.d, s.d_n_host, sizeof(SelCount));
+}
+
+void DeviceJoin::chunk_upload(int k, uint32_t max_ev, CopySegs& cs) {
+  Slot& s = sl_[k];
+  cs.add(s.d_chunk_next, s.h_chunk_next.d, (size_t)s.n_chunks * 4);
+  cs.add(s.d_chunk_first, s.h_chunk_first.d, s.n_chunks);
+  // The selection's counters.  The totals are this slot's: their previous values left with that
+  // batch's export launch, earlier on this stream.  The list sizes sit in the scratch both slots
+  // share, which only the parse stream's selection kernels touch, one batch after the other.
+  max_ev = std::min<uint32_t>(max_ev, cfg_.max_events);
+  cs.zero(s.d_n_host, sizeof(SelCount));
+  if (max_ev) cs.zero(dj_select_list_n(d_sel_pos_, max_ev), 8);
 }
 
 void DeviceJoin::set_chunks(int k, const std::vector<int32_t>& chunk_file, const uint32_t* d_chunk_file,
-                            const uint8_t* d_chunk_kind, hipStream_t ps) {
+                            const uint8_t* d_chunk_kind) {
   Slot& s = sl_[k];
   const uint32_t n = (uint32_t)chunk_file.size();
   std::unordered_map<int32_t, int32_t> last;
@@ -262,27 +273,10 @@ void DeviceJoin::set_chunks(int k, const std::vector<int32_t>& chunk_file, const
     }
     last[chunk_file[c]] = (int32_t)c;
   }
-  if (n) {
-    HIP_OK(hipMemcpyAsync(s.d_chunk_next, s.h_chunk_next, (size_t)n * 4, hipMemcpyHostToDevice, ps));
-    HIP_OK(hipMemcpyAsync(s.d_chunk_first, s.h_chunk_first, n, hipMemcpyHostToDevice, ps));
-  }
   s.d_chunk_file = d_chunk_file;
   s.d_chunk_kind = d_chunk_kind;
   s.n_chunks = n;
   s.chunk_file = chunk_file;
-}
-
-void DeviceJoin::finish_select(int k, hipStream_t ps) {
-  Slot& s = sl_[k];
-  const uint32_t n = s.h_n_host->host;
-  if (n > s.spec) {
-    HIP_OK(hipMemcpyAsync(s.h_host_ev + s.spec, s.d_host_ev + s.spec, (size_t)(n - s.spec) * sizeof(Event),
-                          hipMemcpyDeviceToHost, ps));
-    HIP_OK(hipMemcpyAsync(s.h_host_idx + s.spec, s.d_host_idx + s.spec, (size_t)(n - s.spec) * 4,
-                          hipMemcpyDeviceToHost, ps));
-    HIP_OK(hipStreamSynchronize(ps));
-  }
-  last_host_ = n;
 }
 
 // ---------------------------------------------------------------------------- host pre-pass
@@ -873,7 +867,7 @@ void DeviceJoin::ensure_rest(uint32_t n_ev, uint64_t bytes) {
 void DeviceJoin::prepass_ahead(int k, const uint8_t* hb, const ParallelFor& parallel) {
   if (ahead_k_ >= 0) throw std::runtime_error("device join: a pre-pass is already ahead");
   // hops_ / hbuf_ hold the running batch's ops (register_misses reads hbuf_ after sync A)
-  host_prepass(k, hb, sl_[k].h_n_host->host, parallel, hops_ahead_, hbuf_ahead_);
+  host_prepass(k, hb, sl_[k].h_n_host.h->host, parallel, hops_ahead_, hbuf_ahead_);
   ahead_k_ = k;
 }
 
@@ -892,7 +886,7 @@ void DeviceJoin::run(int k, const uint8_t* hb, uint32_t n_ev, uint64_t n_bytes, 
     ahead_k_ = -1;
   } else {
     if (ahead_k_ >= 0) throw std::runtime_error("device join: pre-pass ahead for another slot");
-    host_prepass(k, hb, s.h_n_host->host, parallel, hops_, hbuf_);
+    host_prepass(k, hb, s.h_n_host.h->host, parallel, hops_, hbuf_);
   }
   phase_t[1] = clock_ms();
   spans.clear();

@@ -1,8 +1,9 @@
 // Host driver of the GPU join (kernels/devjoin.hip): one per engine.
 //
 // Per batch (ingest thread):
-//   1. the parse stream selects the events the GPU does not resolve alone (apm_dj_select_host)
-//      and copies them to pinned memory with the parse counts;
+//   1. the parse stream selects the events the GPU does not resolve alone (apm_dj_select_host):
+//      its scatter writes them straight into the slot's host-mapped pinned buffers, and the
+//      engine's one export launch at the end of the chain carries their counts;
 //   2. host pre-pass (this file): the field re-derivation of PM_HOST lines (and of audit lines
 //      the GPU cannot read alone) becomes HostOps (sorted by event);
 //   3. join kernels (ops, audit trail K5, SOAP scan, grouping, expiry, group walk, placement)
@@ -31,6 +32,8 @@
 #include "join.h"
 
 namespace apm {
+
+struct CopySegs;  // kernels/kernel_api.h
 
 struct DevJoinConfig {
   uint32_t max_events = 1u << 20;   // events (relevant lines) per batch (< 2^21: packed selection scan)
@@ -82,13 +85,19 @@ class DeviceJoin {
   }
   void swap_stage(int k) { std::swap(sl_[k].d_bytes, d_stage_bytes_); }
   Event* d_events(int k) { return sl_[k].d_events; }
-  // after the parse kernels (parse stream): select host events, queue their D2H (speculative)
+  // after the parse kernels (parse stream): select host events (written to the slot's mapped
+  // pinned buffers by the selection's scatter; nothing is copied here)
   void select_host(int k, const uint32_t* d_n_ev, uint32_t max_ev, hipStream_t ps);
-  // chunk tables of slot k for the SOAP chain (host computes next / first per file)
+  // chunk tables of slot k for the SOAP chain (host computes next / first per file); no launch:
+  // chunk_upload() names what the caller's one upload launch has to carry
   void set_chunks(int k, const std::vector<int32_t>& chunk_file, const uint32_t* d_chunk_file,
-                  const uint8_t* d_chunk_kind, hipStream_t ps);
-  // after the parse stream synced: finish the host-event copy (n_ev known)
-  void finish_select(int k, hipStream_t ps);
+                  const uint8_t* d_chunk_kind);
+  // Slot k's share of the parse chain's first launch (apm_copy_segs, before the parse kernels):
+  // chunk_next / chunk_first from their pinned tables (set_chunks filled them), and the zero
+  // fills of the two counters select_host's kernels append to.  max_ev: as for select_host.
+  void chunk_upload(int k, uint32_t max_ev, CopySegs& cs);
+  // Slot k's share of the chain's last launch: the selection totals into mapped pinned memory.
+  void export_select(int k, CopySegs& cs);
   // the batch join; host_bytes = the host copy of the batch (same layout as d_bytes(k))
   // `parallel(n, fn)` runs fn(0..n-1) on the engine's worker pool (host pre-pass per file)
   using ParallelFor = std::function<void(int, const std::function<void(int)>&)>;
@@ -151,20 +160,20 @@ class DeviceJoin {
     uint8_t* d_bytes = nullptr;
     Event* d_events = nullptr;
     uint8_t* host_flag = nullptr;
-    Event* d_host_ev = nullptr;
-    uint32_t* d_host_idx = nullptr;
     uint32_t* d_mh_idx = nullptr;      // audit map / header events
     uint32_t* d_walk_idx = nullptr;    // audit block-walk events
     AudF* d_aud = nullptr;             // audit fields per event (parse-side selection writes them)
     SelCount* d_n_host = nullptr;
-    Event* h_host_ev = nullptr;        // pinned
-    uint32_t* h_host_idx = nullptr;    // pinned
-    SelCount* h_n_host = nullptr;      // pinned
-    uint32_t spec = 0;                 // host events already copied speculatively
+    // host-mapped pinned (.d: the device view): the selection's scatter writes the host events
+    // and their indices ([max_events]), the chain's export launch the totals; read after the
+    // parse stream's synchronize
+    Mapped<Event> h_host_ev;
+    Mapped<uint32_t> h_host_idx;
+    Mapped<SelCount> h_n_host;
     int32_t* d_chunk_next = nullptr;
     uint8_t* d_chunk_first = nullptr;
-    int32_t* h_chunk_next = nullptr;   // pinned
-    uint8_t* h_chunk_first = nullptr;  // pinned
+    Mapped<int32_t> h_chunk_next;      // pinned, read over the host link by the upload launch
+    Mapped<uint8_t> h_chunk_first;
     const uint32_t* d_chunk_file = nullptr;
     const uint8_t* d_chunk_kind = nullptr;
     uint32_t n_chunks = 0;
@@ -238,7 +247,6 @@ class DeviceJoin {
   uint8_t* d_hbuf_ = nullptr;
   size_t d_hops_cap_ = 0, d_hbuf_cap_ = 0;
   std::vector<PrepassTask> tasks_;
-  uint32_t last_host_ = 0;
   void* d_sel_tmp_ = nullptr;  // rocprim scratch of the host-event selection (parse stream)
   size_t sel_tmp_bytes_ = 0;
   uint64_t audit_errors_ = 0, host_pm_ = 0, host_invalid_acct_ = 0, host_events_ = 0, events_ = 0, tx_ = 0, tx_db_ = 0;

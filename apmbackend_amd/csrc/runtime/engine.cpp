@@ -912,19 +912,35 @@ void Engine::launch_parse(ParseSlot& ps, const uint8_t* host_bytes, uint64_t n_b
   Event* devents = dev() ? dj_->d_events(k) : d_events_;
   if (!staged) HIP_OK(hipMemcpyAsync(dbytes, ps.hb, off, hipMemcpyHostToDevice, parse_stream_));
   // (apm_parse_batch zeroes the 64 bytes after the batch inside its first kernel)
-  h2d(d_chunk_begin_[k], ps.h_chunk_begin, (n_chunks + 1) * 4, parse_stream_);
-  h2d(d_chunk_kind_[k], ps.h_chunk_kind, n_chunks + 1, parse_stream_);
-  h2d(d_chunk_file_[k], ps.h_chunk_file, (n_chunks + 1) * 4, parse_stream_);
+  // The chunk tables go up in one launch (a kernel reading the pinned tables over the host link,
+  // see h2d below): the parse's three and, with the device join, the SOAP chain's next / first
+  // links and the zero fills of the selection's counters (DeviceJoin::chunk_upload).
+  {
+    CopySegs up;
+    up.add(d_chunk_begin_[k], HipRes::device_alias(ps.h_chunk_begin), (size_t)(n_chunks + 1) * 4);
+    up.add(d_chunk_kind_[k], HipRes::device_alias(ps.h_chunk_kind), n_chunks + 1);
+    up.add(d_chunk_file_[k], HipRes::device_alias(ps.h_chunk_file), (size_t)(n_chunks + 1) * 4);
+    if (dev()) {
+      dj_->set_chunks(k, ps.chunk_file, d_chunk_file_[k], d_chunk_kind_[k]);
+      dj_->chunk_upload(k, cfg_.max_lines, up);
+    }
+    apm_copy_segs(&up, parse_stream_);
+  }
   if (apm_parse_batch(dbytes, off, d_chunk_begin_[k], d_chunk_kind_[k], d_chunk_file_[k], n_chunks, d_parse_ws_,
                       cfg_.max_lines, devents, d_counts_, d_counts_ + 1, d_watermark_, d_file_open_, &cfg_.tz,
                       parse_stream_) != 0)
     throw std::runtime_error("parse workspace too small");
-  if (dev()) {
-    dj_->set_chunks(k, ps.chunk_file, d_chunk_file_[k], d_chunk_kind_[k], parse_stream_);
-    dj_->select_host(k, d_counts_, cfg_.max_lines, parse_stream_);
+  if (dev()) dj_->select_host(k, d_counts_, cfg_.max_lines, parse_stream_);
+  // The chain's results leave in one launch too: the event / line counts, the watermark and the
+  // selection totals, stored into the slot's host-mapped pinned words (read after finish_parse's
+  // synchronize).  The selected host events are already there: the selection's scatter wrote them.
+  {
+    CopySegs ex;
+    ex.add(HipRes::device_alias(ps.h_counts), d_counts_, 8);
+    ex.add(HipRes::device_alias(ps.h_watermark), d_watermark_, 8);
+    if (dev()) dj_->export_select(k, ex);
+    apm_copy_segs(&ex, parse_stream_);
   }
-  d2h(ps.h_counts, d_counts_, 8, parse_stream_);
-  d2h(ps.h_watermark, d_watermark_, 8, parse_stream_);
   // Prefetched parse: the event count is only known on the device, so copy a guess (the last
   // batch's count + 25 %) right behind the kernels.  The DMA then runs during the current
   // batch's host join instead of on the ingest thread's critical path (15 MB, ~0.3 ms), and
@@ -966,9 +982,7 @@ void Engine::finish_parse(ParseSlot& ps) {
   if (ps.n_lines > cfg_.max_lines) throw std::runtime_error("batch has more lines than max_lines");
   metrics_.lines += ps.n_lines;
   metrics_.events += ps.n_events;
-  if (dev()) {
-    dj_->finish_select((int)(&ps - pslot_), parse_stream_);
-  } else if (ps.n_events > ps.spec_copied) {
+  if (!dev() && ps.n_events > ps.spec_copied) {  // (device join: its host events are already here)
     const uint32_t lo = ps.spec_copied;
     HIP_OK(hipMemcpyAsync(ps.h_events + lo, d_events_ + lo, (size_t)(ps.n_events - lo) * sizeof(Event),
                           hipMemcpyDeviceToHost, parse_stream_));
@@ -2150,7 +2164,9 @@ void Engine::stats_for_batch_dev(DevJoinBatch& b, double batch_t0) {
 // Small per-batch transfers between device memory and pinned (hipHostMalloc) host buffers run
 // as kernel copies over the host link (apm_copy): hipMemcpyAsync of a few KB from pinned memory
 // held the calling thread for up to 0.6 ms on this pool (trace span u.hops.h2d), a launch never
-// does.  Bulk transfers (batch bytes, st/fs text) stay on the DMA engines.
+// does.  Bulk transfers (batch bytes, st/fs text) stay on the DMA engines.  Each such launch is a
+// host-link round trip on its stream, however small, so the parse chain packs its own into two
+// (launch_parse: apm_copy_segs for the chunk tables going up and for the results coming back).
 void Engine::h2d(void* d, const void* h, size_t n, hipStream_t s) {
   if (n == 0) return;
   apm_copy(d, HipRes::device_alias(h), n, s);
