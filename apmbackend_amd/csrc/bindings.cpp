@@ -135,6 +135,16 @@ EngineConfig config_from(const py::dict& d) {
     if (d.contains("slo_services")) c.slo_services = d["slo_services"].cast<std::map<std::string, int32_t>>();
     c.slo_default = get<int32_t>(d, "slo_default", 0);
   }
+  if (d.contains("svc_pcts")) {
+    auto v = d["svc_pcts"].cast<std::vector<int64_t>>();
+    if (v.size() > 8) throw std::invalid_argument("svc_pcts: at most 8 percentiles");
+    c.n_svc_pcts = (int32_t)v.size();
+    for (size_t i = 0; i < v.size(); ++i) {
+      if (v[i] < 1 || v[i] > 100000 || (i && v[i] <= v[i - 1]))
+        throw std::invalid_argument("svc_pcts: strictly ascending integers in 1 .. 100000 (percentile * 1000)");
+      c.svc_pcts[i] = (int32_t)v[i];
+    }
+  }
   if (d.contains("tk_k") && !d["tk_k"].is_none()) {  // (the constructor checks them when the tk stream is on)
     c.tk_k = d["tk_k"].cast<int32_t>();
     if (d.contains("tk_by")) c.tk_by = d["tk_by"].cast<std::vector<int32_t>>();
@@ -598,6 +608,21 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("svcwins", [](Engine& e) {
+        // per service (name, servers, m, nan, sum, [sum2 per configured percentile]) of the last
+        // rollover's K19 value pass, in the order of each service's first series in emission order
+        std::vector<std::string> names;
+        std::vector<SvcRec> rec;
+        e.download_svcwins(names, rec);
+        const int nq = e.svc_nq();
+        py::list out;
+        for (size_t i = 0; i < rec.size(); ++i) {
+          py::list v;
+          for (int j = 0; j < nq && rec[i].m > 0; ++j) v.append(py::int_(rec[i].sum2[j]));
+          out.append(py::make_tuple(names[i], rec[i].servers, rec[i].m, rec[i].nan, py::int_(rec[i].sum), v));
+        }
+        return out;
+      })
       .def("leaderboard", [](Engine& e) {
         // the last rollover's K18 records: (board, rank, series id, tpm, avg, p75, p95), raw doubles
         std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> rows;
@@ -656,15 +681,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[9];
-    int64_t counts[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::string out[10];
+    int64_t counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[9] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk"};
-    for (int k = 0; k < 9; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[10] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv"};
+    for (int k = 0; k < 10; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -855,6 +880,10 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("slo_stage_bytes", []() { return apm_slo_stage_bytes(); });
   // tk leaderboards (topk.hip): emission positions per block of the tile pass, and the survivors the
   // final block reads per sweep (tests bracket both)
+  // sv service windows (svcwin.hip): the sample total and window length up to which the value pass
+  // keeps a service in its 32-lane group (tests bracket them)
+  m.def("svcwin_group_max", []() { return apm_svcwin_group_max(); });
+  m.def("svcwin_group_win", []() { return apm_svcwin_group_win(); });
   m.def("apm_topk_tile", []() { return apm_topk_tile(); });
   m.def("apm_topk_final_span", []() { return apm_topk_final_span(); });
   m.def("topk_select", [](const std::vector<std::tuple<double, double, double, double, int32_t>>& win_rows,

@@ -283,6 +283,48 @@ struct TopKArgs {
   uint64_t* sc_key;             // [nb][tiles][k] tile survivors: order key (0: unused slot)
   int32_t* sc_pos;              // [nb][tiles][k] their emission positions
 };
+// K19 sv rows: exact per-service window stats across servers (svcwin.hip, docs/SERVICEWINDOW.md).
+// The unit of work is a group: the series of one service (CSR grp_off / grp_mem, members in
+// emission order, grp_pos their emission positions).  The value pass reads the window K8 just read
+// of every active member and writes one record per group over the union of their samples; the text
+// pass prints, at the emission position of a group's first active member when m >= 1:
+//   sv|<edge ts>|service|<servers>|<m>|<nan>|<sum>|<p>:<v>,<p>:<v>,...
+struct SvcRec {
+  int32_t servers;              // active members
+  int32_t m, nan;               // samples that are not / are ELAPSED_NAN
+  int32_t first_pos;            // emission position of the first active member (-1: none)
+  long long sum;                // of the m finite samples
+  long long sum2[WP_MAX_Q];     // per percentile: sum of the one or two ranks read (one rank: twice it)
+};
+struct SvcWinArgs {
+  WindowArgs w;                 // K8's arguments of this rollover (spill lists sorted; w.out = K8's result)
+  int32_t nq;                   // 1 .. WP_MAX_Q
+  int32_t q[WP_MAX_Q];          // percentile * 1000, strictly ascending, 1 .. 100000
+  int32_t n_groups;
+  const int32_t* grp_off;       // [n_groups + 1]
+  const int32_t* grp_mem;       // [n_series] member series, group by group, each in emission order
+  const int32_t* grp_pos;       // [n_series] their emission positions
+  SvcRec* rec;                  // [n_groups]
+  int32_t* big_list;            // [n_groups] groups deferred to the block pass
+  int32_t* big_n;
+};
+struct SvcWinTextArgs {
+  const SvcRec* rec;            // [n_groups]
+  const int32_t* series_grp;    // [n_series] group of a series
+  const int32_t* perm;          // [n] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;
+  int32_t n_series;
+  int32_t n_groups;
+  int32_t nq;
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  char ptxt[WP_MAX_Q][8];       // "<p>:" per percentile (at most "99.999:")
+  int32_t plen[WP_MAX_Q];
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_svcwin_row_bound(max name bytes, nq) * n_groups bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -421,6 +463,19 @@ int32_t apm_topk_final_span();   // survivors the final block reads per sweep (i
 size_t apm_topk_scratch_bytes(int32_t n_max, int32_t k, int32_t nb);
 // both launches for all boards; `scratch` holds apm_topk_scratch_bytes(a->n, a->k, a->nb) bytes
 void apm_topk(apm::TopKArgs* a, void* scratch, hipStream_t stream);
+// svcwin.hip
+// the value pass' two paths (tests bracket them): a service stays in its 32-lane group while the
+// window has at most apm_svcwin_group_win() buckets and its active members' windows hold at most
+// apm_svcwin_group_max() samples together; every other service is selected by a whole block
+int32_t apm_svcwin_group_max();
+int32_t apm_svcwin_group_win();
+size_t apm_svcwin_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for a service name of `name_bytes` bytes and nq percentiles
+size_t apm_svcwin_row_bound(size_t name_bytes, int32_t nq);
+void apm_svcwin_values(apm::SvcWinArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_svcwin_plan(apm::SvcWinTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_svcwin_write(apm::SvcWinTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

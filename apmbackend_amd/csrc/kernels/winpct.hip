@@ -31,19 +31,7 @@ constexpr int WP_GROUP_WIN = HW;       // window buckets a group covers (one per
 constexpr int WP_BLOCK = 512;          // threads per series (block pass)
 constexpr int WP_BIG_GRID = 512;       // blocks of the block pass (they loop over big_list)
 constexpr int WP_TEXT_BLOCK = 256;
-constexpr int WP_SCALE = 100000;       // q of 100 %
-
-// The (lo, hi) ranks among m >= 1 ascending samples for percentile q / 1000: t = q m; a multiple
-// of 100000 reads rank t / 100000 - 1; else i = ceil(t / 100000) - 1 = floor(t / 100000) and
-// (i, i + 1), or (i, i) at the last sample.  m == 1: rank 0.
-__device__ __forceinline__ void wp_ranks(int m, int q, int& lo, int& hi) {
-  if (m == 1) { lo = hi = 0; return; }
-  const long long t = (long long)q * (long long)m;
-  const int i = (int)(t / WP_SCALE);
-  if (t % WP_SCALE == 0) { lo = hi = i - 1; return; }
-  lo = i;
-  hi = i == m - 1 ? i : i + 1;
-}
+// (the integer rank rule, wp_ranks, lives in winsort.h: K19 reads the same ranks)
 
 __global__ __launch_bounds__(WP_WAVES * APM_WAVE) void k_winpct_group(WinPctArgs a) {
   __shared__ int32_t tile[WP_WAVES * 2][WP_GROUP_MAX];

@@ -1,8 +1,10 @@
-// Window-sample helpers shared by K8 (stats.hip) and K16 (winpct.hip): the 32-lane DPP moves and
+// Window-sample helpers shared by K8 (stats.hip), K16 (winpct.hip), K17 (slo.hip) and K19
+// (svcwin.hip): the 32-lane DPP moves and
 // register sorting networks of the two-series-per-wave kernels, the block-wide visit of a series'
 // window samples, and the exact radix select of R order statistics.  Moved out of stats.hip
 // unchanged (as spill.h was for K15); window_select_ranks<R> is K8's four-rank select with the
-// rank count a template parameter.
+// rank count a template parameter, window_select_visit<R> the same with the sample visit one as
+// well; wp_ranks is the integer rank rule of the wp / sv percentiles.
 #pragma once
 #include "kernel_api.h"
 #include "spill.h"
@@ -152,7 +154,7 @@ __device__ __forceinline__ void for_each_window_sample(const WindowArgs& a, int 
   }
 }
 
-// Exact k-th smallest samples of series s's window, R ranks (ascending order of all samples,
+// Exact k-th smallest of the samples `visit` enumerates, R ranks (ascending order of all samples,
 // ELAPSED_NAN = INT32_MIN first) selected together by the whole block: K8's radix select
 // (stats.hip window_select), 8 bits per pass, four passes over the window's samples, with the
 // rank count a template parameter.  Ranks whose keys agree in the bits fixed so far would count
@@ -161,10 +163,11 @@ __device__ __forceinline__ void for_each_window_sample(const WindowArgs& a, int 
 // others read its row, so a sample costs one LDS atomic per distinct prefix instead of R.
 // `hist` holds R x 256 LDS bins.  Returns the R keys in LDS: after the call (it ends in a
 // __syncthreads) key[r] ^ 0x80000000 is the sample of rank ranks[r].  Every thread of the block
-// calls it with the same arguments.
-template <int R>
-__device__ __forceinline__ const uint32_t* window_select_ranks(const WindowArgs& a, int s, const int (&ranks)[R],
-                                                               uint32_t* hist) {
+// calls it with the same arguments.  `visit(f)` calls f(sample) for every sample once, the samples
+// shared out over the block's threads, and is called four times (one series' window:
+// window_select_ranks below; the windows of a service's series: svcwin.hip).
+template <int R, class V>
+__device__ __forceinline__ const uint32_t* window_select_visit(V&& visit, const int (&ranks)[R], uint32_t* hist) {
   __shared__ uint32_t prefix[R];
   __shared__ int32_t want[R];
 #pragma unroll
@@ -191,7 +194,7 @@ __device__ __forceinline__ const uint32_t* window_select_ranks(const WindowArgs&
       if ((int)threadIdx.x == r) my_row = row;
     }
     __syncthreads();
-    for_each_window_sample(a, s, [&](int32_t v) {
+    visit([&](int32_t v) {
       const uint32_t u = (uint32_t)v ^ 0x80000000u;  // order-preserving unsigned key
       const uint32_t bin = (u >> shift) & 255u;
 #pragma unroll
@@ -214,6 +217,27 @@ __device__ __forceinline__ const uint32_t* window_select_ranks(const WindowArgs&
     __syncthreads();
   }
   return prefix;
+}
+
+// the ranks of series s's window
+template <int R>
+__device__ __forceinline__ const uint32_t* window_select_ranks(const WindowArgs& a, int s, const int (&ranks)[R],
+                                                               uint32_t* hist) {
+  return window_select_visit<R>([&](auto&& f) { for_each_window_sample(a, s, f); }, ranks, hist);
+}
+
+constexpr int WP_SCALE = 100000;       // q of 100 %
+
+// The (lo, hi) ranks among m >= 1 ascending samples for percentile q / 1000: t = q m; a multiple
+// of 100000 reads rank t / 100000 - 1; else i = ceil(t / 100000) - 1 = floor(t / 100000) and
+// (i, i + 1), or (i, i) at the last sample.  m == 1: rank 0.
+__device__ __forceinline__ void wp_ranks(int m, int q, int& lo, int& hi) {
+  if (m == 1) { lo = hi = 0; return; }
+  const long long t = (long long)q * (long long)m;
+  const int i = (int)(t / WP_SCALE);
+  if (t % WP_SCALE == 0) { lo = hi = i - 1; return; }
+  lo = i;
+  hi = i == m - 1 ? i : i + 1;
 }
 
 }  // namespace apm

@@ -863,6 +863,7 @@ std::string Engine::load_small_state(const std::string& path) {
     perm_uploaded_ = 0;
     series_service_uploaded_ = 0;
     svc_csr_n_ = -1;
+    sv_built_n_ = -1;  // (K19: its member lists are rebuilt from the series table)
   }
   const int32_t n = n_series_;
 

@@ -237,9 +237,38 @@ bool half_from_text(std::string_view s, int64_t& sum2) {
   return true;
 }
 void append_i64(std::string& o, int64_t v) { o += std::to_string(v); }
+// "<p>:<v>,<p>:<v>,..." (wp and sv rows) -> the members of a JSON object appended to js ("{" is
+// there already); a malformed pair is dropped
+void append_pct_pairs(std::string& js, std::string_view rest) {
+  while (!rest.empty()) {
+    const size_t e = rest.find(',');
+    const std::string_view pr = rest.substr(0, e);
+    rest = e == std::string_view::npos ? std::string_view() : rest.substr(e + 1);
+    const size_t c = pr.find(':');
+    const int64_t q = pct_from_text(pr.substr(0, c));
+    int64_t sum2 = 0;
+    if (q < 0 || c == std::string_view::npos || !half_from_text(pr.substr(c + 1), sum2)) continue;  // (dropped)
+    if (js.size() > 1) js += ',';
+    // the canonical texts again: q / 1000 without trailing zeros, sum2 / 2 as an integer or x.5
+    js += '"';
+    append_i64(js, q / 1000);
+    if (q % 1000) {
+      char fr[4] = {(char)('0' + q % 1000 / 100), (char)('0' + q % 100 / 10), (char)('0' + q % 10), 0};
+      int n = 3;
+      while (fr[n - 1] == '0') --n;
+      js += '.';
+      js.append(fr, (size_t)n);
+    }
+    js += "\":";
+    const int64_t m = sum2 < 0 ? -sum2 : sum2;
+    if (sum2 < 0) js += '-';
+    append_i64(js, m / 2);
+    if (m & 1) js += ".5";
+  }
+}
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[9]*/) {
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[10]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -343,32 +372,7 @@ int encode_line(std::string_view line, std::string* out /*[9]*/) {
     c_num(o, a.has(4) ? js::parse_int(a.f[4]) : js::nan()); o += '\t';
     c_num(o, a.has(5) ? js::parse_int(a.f[5]) : js::nan()); o += '\t';
     std::string js = "{";
-    std::string_view rest = a.has(6) ? a.f[6] : std::string_view();
-    while (!rest.empty()) {
-      const size_t e = rest.find(',');
-      const std::string_view pr = rest.substr(0, e);
-      rest = e == std::string_view::npos ? std::string_view() : rest.substr(e + 1);
-      const size_t c = pr.find(':');
-      const int64_t q = pct_from_text(pr.substr(0, c));
-      int64_t sum2 = 0;
-      if (q < 0 || c == std::string_view::npos || !half_from_text(pr.substr(c + 1), sum2)) continue;  // (dropped)
-      if (js.size() > 1) js += ',';
-      // the canonical texts again: q / 1000 without trailing zeros, sum2 / 2 as an integer or x.5
-      js += '"';
-      append_i64(js, q / 1000);
-      if (q % 1000) {
-        char fr[4] = {(char)('0' + q % 1000 / 100), (char)('0' + q % 100 / 10), (char)('0' + q % 10), 0};
-        int n = 3;
-        while (fr[n - 1] == '0') --n;
-        js += '.';
-        js.append(fr, (size_t)n);
-      }
-      js += "\":";
-      const int64_t m = sum2 < 0 ? -sum2 : sum2;
-      if (sum2 < 0) js += '-';
-      append_i64(js, m / 2);
-      if (m & 1) js += ".5";
-    }
+    append_pct_pairs(js, a.has(6) ? a.f[6] : std::string_view());
     js += '}';
     copy_escape(o, js);
     o += '\n';
@@ -429,6 +433,33 @@ int encode_line(std::string_view line, std::string* out /*[9]*/) {
     }
     o += '\n';
     return 8;
+  }
+  if (t == "sv") {  // service window: timestamp, service, servers, count, nan, elapsed_sum, pcts json
+    // (utils/records.py entry_from_csv holds the same rules) a row whose servers, count or nan is not
+    // 1 to 10 plain digits, or whose sum is not 1 to 18 digits after an optional '-', is dropped
+    for (int i = 3; i <= 5; ++i)
+      if (!a.has(i) || !all_digits(a.f[i], 10)) return -1;
+    if (!a.has(6)) return -1;
+    const bool sneg = !a.f[6].empty() && a.f[6][0] == '-';
+    const std::string_view sdig = sneg ? a.f[6].substr(1) : a.f[6];
+    if (!all_digits(sdig, 18)) return -1;
+    std::string& o = out[9];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    for (int i = 3; i <= 5; ++i) {
+      int64_t v = 0;
+      for (char ch : a.f[i]) v = v * 10 + (ch - '0');
+      append_i64(o, v); o += '\t';
+    }
+    int64_t sv = 0;
+    for (char ch : sdig) sv = sv * 10 + (ch - '0');
+    append_i64(o, sneg ? -sv : sv); o += '\t';
+    std::string js = "{";
+    append_pct_pairs(js, a.has(7) ? a.f[7] : std::string_view());
+    js += '}';
+    copy_escape(o, js);
+    o += '\n';
+    return 9;
   }
   if (t == "jx") {
     std::string& o = out[3];

@@ -247,6 +247,13 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       throw std::invalid_argument("tk stream: tk_k must lie in 1 .. 128, tk_by hold 1 to 4 distinct keys out of "
                                   "0 .. 3 and tk_min_tpm be finite and >= 0");
   }
+  if (want(OUT_SV)) {  // K19: the stream needs its list (likewise before anything is allocated)
+    const int nq = cfg_.n_svc_pcts;
+    bool ok = nq >= 1 && nq <= WP_MAX_Q;
+    for (int j = 0; ok && j < nq; ++j)
+      ok = cfg_.svc_pcts[j] >= 1 && cfg_.svc_pcts[j] <= 100000 && (j == 0 || cfg_.svc_pcts[j] > cfg_.svc_pcts[j - 1]);
+    if (!ok) throw std::invalid_argument("sv stream: svc_pcts must hold 1 to 8 strictly ascending percentiles");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -467,6 +474,20 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       res_.pin(h_tk_n_[k], 64);
       ev_tk_[k] = res_.new_event();
     }
+  }
+  if (want(OUT_SV)) {  // K19
+    d_sv_off_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_sv_mem_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    d_sv_pos_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    d_sv_grp_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    d_sv_rec_ = (SvcRec*)res_.dmalloc((size_t)S * sizeof(SvcRec));
+    d_sv_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_sv_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_sv_off_txt_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    sv_tmp_bytes_ = apm_svcwin_tmp_bytes(S);
+    d_sv_tmp_ = res_.dmalloc(sv_tmp_bytes_);
+    res_.pin(h_sv_total_, 64);
+    for (int k = 0; k < 2; ++k) ev_sv_[k] = res_.new_event();
   }
   if (want(OUT_LH)) {  // K15
     d_hist_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
@@ -2415,6 +2436,11 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   // written by sync_format_tables() alone, which topk_rollover() calls on this stream ahead of its
   // launches, and the next rollover's K8 -- the next writer of d_win_ -- follows on this stream.
   if (want(OUT_TK)) topk_rollover(edge_ts);
+  // K19: after K18, for K16's reason (docs/PERCENTILES.md "Where it is queued"): it reads what
+  // K16 reads -- window cells, counts, the sorted spill lists, d_win_ -- and nothing queued since
+  // K8 writes any of them; its own tables (the service CSR) are uploaded on this stream ahead of
+  // its launches, and the next append follows on this stream.
+  if (want(OUT_SV)) svcwin_rollover(wa, edge_ts);
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2569,8 +2595,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[9];
-        int64_t counts[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::string enc[10];
+        int64_t counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3273,6 +3299,139 @@ std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> Engine::leaderboard(
   return out;
 }
 
+// ---- K19: sv rows.  One row per service whose active series hold a non-NaN sample, at the
+// position of the service's first st row, with the st rows' timestamp: value pass over the union of
+// the K8 windows of each service's series, then count / scan / write of the text.
+
+// The service -> member series CSR, rebuilt when series were added since the last build (a resume
+// clears h_perm_ and starts over: the lists follow from the series table).  One pass over the
+// emission order: a service's row is where its first member stands, its members keep that order.
+void Engine::sync_service_groups() {
+  const int32_t n = n_series_;
+  if (sv_built_n_ == n) return;
+  std::unordered_map<int32_t, int32_t> grp_of;  // local dictionary service id -> row
+  grp_of.reserve((size_t)n);
+  h_sv_grp_.assign((size_t)n, -1);
+  std::vector<int32_t> cnt;
+  for (int32_t i = 0; i < n; ++i) {
+    const int32_t s = h_perm_[(size_t)i];
+    auto it = grp_of.find(series_[(size_t)s].service);
+    if (it == grp_of.end()) {
+      it = grp_of.emplace(series_[(size_t)s].service, (int32_t)cnt.size()).first;
+      cnt.push_back(0);
+    }
+    h_sv_grp_[(size_t)s] = it->second;
+    ++cnt[(size_t)it->second];
+  }
+  sv_groups_ = (int32_t)cnt.size();
+  h_sv_off_.assign((size_t)sv_groups_ + 1, 0);
+  for (int32_t g = 0; g < sv_groups_; ++g) h_sv_off_[(size_t)g + 1] = h_sv_off_[(size_t)g] + cnt[(size_t)g];
+  h_sv_mem_.resize((size_t)n);
+  h_sv_pos_.resize((size_t)n);
+  std::vector<int32_t> at(h_sv_off_.begin(), h_sv_off_.end() - 1);
+  for (int32_t i = 0; i < n; ++i) {
+    const int32_t s = h_perm_[(size_t)i];
+    const int32_t w = at[(size_t)h_sv_grp_[(size_t)s]]++;
+    h_sv_mem_[(size_t)w] = s;
+    h_sv_pos_[(size_t)w] = i;
+  }
+  auto up = [&](int32_t* d, const std::vector<int32_t>& h) {
+    const size_t nb = h.size() * 4;
+    if (!nb) return;
+    char* st = stage(nb);
+    std::memcpy(st, h.data(), nb);
+    h2d(d, st, nb, stream_);
+    stage_done();
+  };
+  up(d_sv_off_, h_sv_off_);
+  up(d_sv_mem_, h_sv_mem_);
+  up(d_sv_pos_, h_sv_pos_);
+  up(d_sv_grp_, h_sv_grp_);
+  sv_built_n_ = n;
+}
+
+void Engine::svcwin_rollover(const WindowArgs& wa, int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();   // h_perm_ / d_perm_ and the names cover every series
+  sync_service_groups();
+  const int nq = cfg_.n_svc_pcts;
+  SvcWinArgs va{};
+  va.w = wa;
+  va.nq = nq;
+  for (int j = 0; j < nq; ++j) va.q[j] = cfg_.svc_pcts[j];
+  va.n_groups = sv_groups_;
+  va.grp_off = d_sv_off_;
+  va.grp_mem = d_sv_mem_;
+  va.grp_pos = d_sv_pos_;
+  va.rec = d_sv_rec_;
+  va.big_list = d_sv_big_;
+  va.big_n = d_sv_big_ + cfg_.max_series;
+  apm_svcwin_values(&va, stream_);
+  SvcWinTextArgs ta{};
+  ta.rec = d_sv_rec_;
+  ta.series_grp = d_sv_grp_;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n;
+  ta.n_series = n;
+  ta.n_groups = sv_groups_;
+  ta.nq = nq;
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  for (int j = 0; j < nq; ++j) {
+    // the canonical text of q / 1000: trailing zeros and a trailing point dropped (as K16 prints it)
+    const int q = cfg_.svc_pcts[j];
+    char fr[8];
+    int len = std::snprintf(ta.ptxt[j], sizeof ta.ptxt[j], "%d", q / 1000);
+    if (q % 1000) {
+      int k = std::snprintf(fr, sizeof fr, "%03d", q % 1000);
+      while (fr[k - 1] == '0') --k;
+      ta.ptxt[j][len++] = '.';
+      for (int i = 0; i < k; ++i) ta.ptxt[j][len++] = fr[i];
+    }
+    ta.ptxt[j][len++] = ':';
+    ta.plen[j] = len;
+  }
+  ta.len = d_sv_len_;
+  ta.off = d_sv_off_txt_;
+  const int k = sv_k_;
+  sv_k_ ^= 1;
+  out_wait(sv_task_[k]);  // slot k's previous D2H + emission is done
+  // the output bound needs no length pass: every row is at most apm_svcwin_row_bound bytes
+  const size_t cap = (size_t)sv_groups_ * apm_svcwin_row_bound(max_name_len_, nq) + 64;
+  if (cap > sv_out_cap_[k]) d_sv_out_[k] = (char*)res_.regrow(d_sv_out_[k], sv_out_cap_[k], cap, stream_);
+  ta.out = d_sv_out_[k];
+  if (apm_svcwin_plan(&ta, d_sv_tmp_, sv_tmp_bytes_, stream_) != 0) throw std::runtime_error("service window scan failed");
+  apm_svcwin_write(&ta, stream_);
+  {
+    ExportArgs ex{};
+    ex.add(ta.off + n, h_sv_total_.d + k, 4);
+    apm_export(&ex, stream_);
+  }
+  HIP_OK(hipEventRecord(ev_sv_[k], stream_));
+  const char* dst = d_sv_out_[k];
+  sv_task_[k] = post_out([this, k, dst]() {
+    HIP_OK(hipEventSynchronize(ev_sv_[k]));
+    const size_t total = h_sv_total_[k];
+    if (!total) return;
+    res_.reserve(h_sv_text_[k], total, total * 2 + (1 << 20));
+    lane_d2h(h_sv_text_[k], dst, total);
+    lane_sync();
+    emit_bytes(OUT_SV, h_sv_text_[k], total);
+  });
+}
+
+void Engine::download_svcwins(std::vector<std::string>& names, std::vector<SvcRec>& rec) {
+  names.clear(); rec.clear();
+  if (!want(OUT_SV) || sv_groups_ == 0 || sv_built_n_ < 0) return;  // (the lists the last rollover ran with)
+  rec.resize((size_t)sv_groups_);
+  HIP_OK(hipMemcpyAsync(rec.data(), d_sv_rec_, rec.size() * sizeof(SvcRec), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  for (int32_t g = 0; g < sv_groups_; ++g)
+    names.push_back(dict_.service_name(series_[(size_t)h_sv_mem_[(size_t)h_sv_off_[(size_t)g]]].service));
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3413,7 +3572,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv"};
   return n[k];
 }
 

@@ -132,6 +132,10 @@ struct EngineConfig {
   int32_t tk_k = 0;
   std::vector<int32_t> tk_by;
   double tk_min_tpm = 0.0;
+  // sv stream (K19): the percentiles as q = p * 1000, strictly ascending, 1 .. 100000; read at
+  // construction (OUT_SV in `outputs` without a valid list is an error)
+  int32_t n_svc_pcts = 0;
+  int32_t svc_pcts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int async_stats = 1;      // overlap batch i's stats with batch i+1's parse + join
   // RCCL watchdog: a collective not complete after this long (a dead or wedged peer) aborts the
   // communicator and throws, so the supervisor restarts the rank group from its checkpoint
@@ -157,13 +161,13 @@ struct EngineConfig {
 //   FS            z -> alerts/db  fs lines (one per series per LAG)
 //   AL            alerts -> db    al lines
 //   SX            new: per-JVM rollup fused with JMX / VM gauges (K14), one line per server
-enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, N_OUT };
+enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, OUT_SV, N_OUT };
 // Streams whose pending text a checkpoint stores (checkpoint.cpp).  The version-9 layout holds
-// exactly these; lh, wp, sl and tk rows are taken by their consumer before a checkpoint and are not persisted.
+// exactly these; lh, wp, sl, tk and sv rows are taken by their consumer before a checkpoint and are not persisted.
 constexpr int N_OUT_CKPT = OUT_FB + 1;
-// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk); the stats thread owns the rest
+// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk, sv); the stats thread owns the rest
 constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP) |
-                                (1u << OUT_SL) | (1u << OUT_TK);
+                                (1u << OUT_SL) | (1u << OUT_TK) | (1u << OUT_SV);
 const char* out_kind_name(int k);
 int out_kind_of(const std::string& name);
 
@@ -730,7 +734,7 @@ class Engine {
   std::mutex out_pool_mu_;
   bool st_has_job_ = false, st_busy_ = false, st_stop_ = false;
   std::string st_error_;
-  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk streams (kLaneKinds)
+  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk / sv streams (kLaneKinds)
   std::thread out_thread_;
   std::mutex out_mu_;
   std::condition_variable out_cv_;
@@ -1287,9 +1291,39 @@ class Engine {
   std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> leaderboard();
  private:
 
+  // K19 sv rows (svcwin.hip), allocated when the stream is on: exact stats of the union of the K8
+  // windows of a service's series, one row per service, queued last in the rollover.  The stats
+  // thread keeps a CSR of service -> member series (grouped by the local dictionary service id,
+  // rows in the order of each service's first member in emission order, members in emission order)
+  // and rebuilds and uploads it, through the stager, at the first rollover after series were added.
+  // No device state outlives a rollover; two device / pinned text slots, as for st / fs.
+  std::vector<int32_t> h_sv_off_, h_sv_mem_, h_sv_pos_, h_sv_grp_;  // [groups + 1], [n], [n], [n] (stats thread)
+  int32_t sv_groups_ = 0;
+  int32_t sv_built_n_ = -1;                                 // n_series_ the CSR was built for
+  int32_t *d_sv_off_ = nullptr, *d_sv_mem_ = nullptr, *d_sv_pos_ = nullptr, *d_sv_grp_ = nullptr;  // [S + 1], [S], [S], [S]
+  SvcRec* d_sv_rec_ = nullptr;                              // [S]
+  int32_t* d_sv_big_ = nullptr;                             // [S] block-pass list, [S] its length
+  uint32_t *d_sv_len_ = nullptr, *d_sv_off_txt_ = nullptr;  // [S + 1]
+  void* d_sv_tmp_ = nullptr;
+  size_t sv_tmp_bytes_ = 0;
+  char* d_sv_out_[2] = {nullptr, nullptr};
+  size_t sv_out_cap_[2] = {0, 0};
+  PinnedBuf<char> h_sv_text_[2];  // pinned (output lane)
+  Mapped<uint32_t> h_sv_total_;   // pinned [2]: bytes of slot k's rows
+  hipEvent_t ev_sv_[2] = {nullptr, nullptr};
+  uint64_t sv_task_[2] = {0, 0};
+  int sv_k_ = 0;
+  void sync_service_groups();
+  void svcwin_rollover(const WindowArgs& wa, int64_t edge_ts);
+ public:
+  // (tests) the value pass' result of the last rollover: per service its name and record
+  void download_svcwins(std::vector<std::string>& names, std::vector<SvcRec>& rec);
+  int32_t svc_nq() const { return cfg_.n_svc_pcts; }
+ private:
+
   // text outputs
   std::string blob_[N_OUT];
-  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   std::shared_ptr<ByteSink> byte_sink_[N_OUT];
   bool fs_copy_ = false;
   bool db_copy_ = false;
@@ -1298,7 +1332,7 @@ class Engine {
   void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
-  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // K14 server rollup + exogenous context
   std::vector<double> h_ctx_;                    // [servers][CTX_FIELDS] (stats thread)
   bool ctx_dirty_ = false;

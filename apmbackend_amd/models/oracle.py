@@ -26,10 +26,11 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import as_bool, gpu_opt, latency_objectives, leaderboard, window_percentiles, zscore_lag_settings
-from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, StatEntry, TxEntry, WindowPctEntry,
-                             WindowSloEntry,
-                             entry_from_csv, hist_bin, hist_lower, pct_ranks)
+from ..utils.config import (as_bool, gpu_opt, latency_objectives, leaderboard, service_window, window_percentiles,
+                            zscore_lag_settings)
+from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, ServiceWindowEntry,
+                             StatEntry, TxEntry, WindowPctEntry, WindowSloEntry, entry_from_csv, hist_bin, hist_lower,
+                             pct_ranks)
 from ..utils.timeparse import TzOffset, convert_string_date_to_ms, default_tz
 
 NAN = float("nan")
@@ -671,7 +672,10 @@ class StatsOracle:
                  interval_len=10, window=30, buffer=6, emit_hist: Optional[Callable[[str], None]] = None,
                  emit_pct: Optional[Callable[[str], None]] = None, percentiles: Iterable[int] = (),
                  emit_slo: Optional[Callable[[str], None]] = None, objectives: Optional[Dict[str, Any]] = None,
-                 emit_top: Optional[Callable[[str], None]] = None, board: Optional[Dict[str, Any]] = None):
+                 emit_top: Optional[Callable[[str], None]] = None, board: Optional[Dict[str, Any]] = None,
+                 emit_svc: Optional[Callable[[str], None]] = None, svc_percentiles: Iterable[int] = ()):
+        self.emit_svc = emit_svc    # sv rows (docs/SERVICEWINDOW.md); None = stream off
+        self.svc_percentiles = [int(q) for q in svc_percentiles]  # q = p * 1000 (config.service_window)
         self.emit_top = emit_top    # tk rows (docs/LEADERBOARD.md); None = stream off
         self.board = board          # config.parse_leaderboard's result: {"k", "by", "minTpm"}
         self.emit_slo = emit_slo    # sl rows (docs/OBJECTIVES.md); None = stream off
@@ -795,6 +799,26 @@ class StatsOracle:
                                             e.per95).to_csv())
         return out
 
+    def svc_rows(self, edge_ts: int, wins: "OrderedDict[str, List[List[int]]]") -> List[str]:
+        """The sv rows of one rollover.  ``wins`` maps a service to the windows (flat sample lists)
+        of its series with an st row, services in the order of their first st row: per service the
+        series count, the samples that are not NaN (count, sum, percentiles by the integer rank
+        rule over their union) and the NaN count; no row without such a sample."""
+        rows = []
+        for service, members in wins.items():
+            flat = [v for w in members for v in w]
+            # the engine stores int32; anything else is its NaN sentinel (engine.cpp)
+            fin = sorted(int(v) for v in flat if v == v and -2147483647 <= v <= 2147483647)
+            if not fin:
+                continue
+            pcts = []
+            for q in self.svc_percentiles:
+                lo, hi = pct_ranks(len(fin), q)
+                pcts.append((q, fin[lo] + fin[hi]))
+            rows.append(ServiceWindowEntry(edge_ts, service, len(members), len(fin), len(flat) - len(fin), sum(fin),
+                                           pcts).to_csv())
+        return rows
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -808,6 +832,7 @@ class StatsOracle:
             for row in self.hist_rows(self.latest - 1 if prev is None else prev):
                 self.emit_hist(row)
         st_rows: List[str] = []
+        svc_wins: "OrderedDict[str, List[List[int]]]" = OrderedDict()
         for server, srv in self.servers.items():
             for service, svc in srv.items():
                 win: List[List[int]] = []
@@ -832,6 +857,8 @@ class StatsOracle:
                 self.emit_stat(st.to_csv())
                 if self.emit_top is not None:
                     st_rows.append(st.to_csv())
+                if self.emit_svc is not None:
+                    svc_wins.setdefault(service, []).append([v for arr in win for v in arr])
                 if self.emit_pct is not None and cnt != 0:
                     row = self.pct_row(edge_ts, server, service, win)
                     if row is not None:
@@ -843,6 +870,9 @@ class StatsOracle:
         if self.emit_top is not None:
             for row in self.top_rows(st_rows):
                 self.emit_top(row)
+        if self.emit_svc is not None:
+            for row in self.svc_rows(edge_ts, svc_wins):
+                self.emit_svc(row)
 
 
 # ----------------------------------------------------------------------------- z-score oracle
@@ -1073,6 +1103,7 @@ class PipelineOracle:
         self.wp: List[str] = []
         self.sl: List[str] = []
         self.tk: List[str] = []
+        self.sv: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1086,7 +1117,9 @@ class PipelineOracle:
                               emit_slo=self.sl.append if latency_objectives(cfg) else None,
                               objectives=latency_objectives(cfg),
                               emit_top=self.tk.append if leaderboard(cfg) else None,
-                              board=leaderboard(cfg))
+                              board=leaderboard(cfg),
+                              emit_svc=self.sv.append if service_window(cfg) else None,
+                              svc_percentiles=service_window(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

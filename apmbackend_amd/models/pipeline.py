@@ -21,7 +21,8 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 from .. import _native
 from ..models.oracle import file_kind, server_of
 from ..ops.parse_ref import tz_table
-from ..utils.config import LEADERBOARD_KEYS, latency_objectives, leaderboard, slo_tables, window_percentiles
+from ..utils.config import (LEADERBOARD_KEYS, latency_objectives, leaderboard, service_window, slo_tables,
+                            window_percentiles)
 from ..utils.timeparse import TzOffset
 
 log = logging.getLogger("apm.pipeline")
@@ -36,11 +37,15 @@ ALL_OUT_KINDS = OUT_KINDS + ("wp",)
 # ... and tests/test_winpct_engine_gpu.py pins ALL_OUT_KINDS; ENGINE_OUT_KINDS is engine.h's OutKind
 # up to sl.
 ENGINE_OUT_KINDS = ALL_OUT_KINDS + ("sl",)
-# ... and tests/test_slo_model.py pins ENGINE_OUT_KINDS; NATIVE_OUT_KINDS is engine.h's OutKind in
-# full and the tuple a stream's bit index comes from.
+# ... and tests/test_slo_model.py pins ENGINE_OUT_KINDS; NATIVE_OUT_KINDS is engine.h's OutKind up
+# to tk.
 NATIVE_OUT_KINDS = ENGINE_OUT_KINDS + ("tk",)
+# ... and tests/test_topk_model.py pins NATIVE_OUT_KINDS; DEVICE_OUT_KINDS is engine.h's OutKind in
+# full and the tuple a stream's bit index comes from.
+DEVICE_OUT_KINDS = NATIVE_OUT_KINDS + ("sv",)
 # keep_text=True materialises these; lh (K15 latency histograms), wp (K16 window percentiles),
-# sl (K17 threshold counts) and tk (K18 leaderboards) are opt-in through `outputs` only
+# sl (K17 threshold counts), tk (K18 leaderboards) and sv (K19 per-service window stats) are opt-in
+# through `outputs` only
 KEEP_TEXT_KINDS = tuple(k for k in OUT_KINDS if k != "lh")
 # What the reference persists (db_insert queue): released + audit tx, fs, al.  `transactions`
 # and `st` are internal hand-offs that only the AMQP bridge needs.
@@ -51,18 +56,19 @@ MAX_LAGS = 16  # apm_types.h MAX_LAGS: LAG capacity per engine (each LAG is an H
 def output_mask(kinds) -> int:
     m = 0
     for k in kinds:
-        m |= 1 << NATIVE_OUT_KINDS.index(k)
+        m |= 1 << DEVICE_OUT_KINDS.index(k)
     return m
 
 
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
                   **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
-    materialises every stream but the opt-in lh / wp / sl / tk; `outputs` (iterable of NATIVE_OUT_KINDS) selects explicitly.
+    materialises every stream but the opt-in lh / wp / sl / tk / sv; `outputs` (iterable of DEVICE_OUT_KINDS) selects explicitly.
     The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
     existed, `outputs` was ignored under keep_text).  "wp" takes its percentiles from
     gpu.windowPercentiles (ValueError when the list is missing or malformed), "sl" its thresholds
-    from gpu.latencyObjectives (likewise), "tk" its boards from gpu.leaderboard (likewise)."""
+    from gpu.latencyObjectives (likewise), "tk" its boards from gpu.leaderboard (likewise), "sv" its percentiles
+    from gpu.serviceWindow (likewise)."""
     g = cfg.get("gpu", {})
     win_pcts = window_percentiles(cfg)
     if "wp" in (outputs or ()) and not win_pcts:
@@ -73,6 +79,9 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
     board = leaderboard(cfg)
     if "tk" in (outputs or ()) and not board:
         raise ValueError('outputs names "tk" but gpu.leaderboard is not set')
+    svc_pcts = service_window(cfg)
+    if "sv" in (outputs or ()) and not svc_pcts:
+        raise ValueError('outputs names "sv" but gpu.serviceWindow is not set')
     zc = cfg["streamCalcZScore"]
     ac = cfg["streamProcessAlerts"]
     sc = cfg["streamCalcStats"]
@@ -150,6 +159,8 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         "tk_k": board["k"] if board else None,
         "tk_by": [LEADERBOARD_KEYS.index(b) for b in board["by"]] if board else [],
         "tk_min_tpm": board["minTpm"] if board else 0.0,
+        # K19: the percentiles of the sv stream as q = p * 1000, likewise read at construction
+        "svc_pcts": svc_pcts,
     }
     # intervalLengthInSeconds only scales the TPM divisor: the bucket label is endTs without its
     # last 4 digits whatever the interval (stream_calc_stats.js:89-96, :186), as here
@@ -226,7 +237,7 @@ class APMEngine:
     @classmethod
     def restart_required(cls, old: Dict[str, Any], new: Dict[str, Any]) -> List[str]:
         """The engine settings that differ between two engine_config results and are not applied
-        live (win_pcts, the slo_* tables, the tk_* settings, ...)."""
+        live (win_pcts, the slo_* tables, the tk_* settings, svc_pcts, ...)."""
         return sorted(k for k in new if k not in cls.LIVE_KEYS and k not in ("outputs", "tz_table")
                       and new[k] != old.get(k))
 

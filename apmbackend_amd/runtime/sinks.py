@@ -62,11 +62,13 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
     "sl": ("dbSloTable", ["timestamp", "server", "service", "count", "nan", "le"]),
     # per-rollover top-K series leaderboards (tk records, gpu.leaderboard): likewise
     "tk": ("dbTopTable", ["timestamp", "board", "rank", "server", "service", "tpm", "average", "per75", "per95"]),
+    # exact per-service window stats across servers (sv records, gpu.serviceWindow): likewise
+    "sv": ("dbSvcTable", ["timestamp", "service", "servers", "count", "nan", "elapsed_sum", "pcts"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv")
 # tables of the record types the reference does not know (its config has no key for them)
 DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct", "sl": "apm_window_slo",
-                  "tk": "apm_leaderboard"}
+                  "tk": "apm_leaderboard", "sv": "apm_service_window"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -120,7 +122,9 @@ def copy_field(v: Any) -> str:
 
 
 def copy_row(rtype: str, row: Dict[str, Any]) -> str:
-    return "\t".join(copy_field(row.get(c)) for c in COLUMNS[rtype][1]) + "\n"
+    # (sv's elapsed_sum is a bigint that may pass 2^53: its digits, never a JS number's text)
+    return "\t".join(str(int(row[c])) if c == "elapsed_sum" else copy_field(row.get(c))
+                     for c in COLUMNS[rtype][1]) + "\n"
 
 
 def _copy_unescape(s: str) -> Optional[str]:
@@ -152,6 +156,8 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
         elif c in ("stats", "entry", "bins", "pcts", "le"):
             out[c] = json.loads(v)
+        elif c in ("servers", "elapsed_sum"):  # (sv: plain integers; the sum may pass 2^53)
+            out[c] = int(v)
         elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan", "rank", "average", "per75", "per95") or rtype == "jx" and c not in ("server",):
             f = float(v)
             out[c] = int(f) if f.is_integer() and "." not in v and "e" not in v else f

@@ -94,6 +94,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "sloQueue": "window_slo",         # amqp mode: the queue the sl records go to
     "leaderboard": None,              # K18 "tk" stream: per-rollover top-K series, {"k": 20, "by": ["per95", "average", "tpm"], "minTpm": 0} (docs/LEADERBOARD.md)
     "topQueue": "leaderboard",        # amqp mode: the queue the tk records go to
+    "serviceWindow": None,            # K19 "sv" stream: exact per-service window stats across servers, {"percentiles": [50, 75, 95, 99]} (docs/SERVICEWINDOW.md)
+    "svcQueue": "service_window",     # amqp mode: the queue the sv records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -257,6 +259,32 @@ def leaderboard(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
     return parse_leaderboard(gpu_opt(cfg, "leaderboard"))
 
 
+def parse_service_window(v: Any) -> List[int]:
+    """gpu.serviceWindow -> [q] (q = p * 1000) of its ``percentiles`` list, which follows the rules
+    of gpu.windowPercentiles (parse_window_percentiles) and must hold at least one entry.
+    None -> [] (stream off); an object without such a list, with any other member, or a value of
+    any other type raises ValueError."""
+    if v is None:
+        return []
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.serviceWindow: an object with 'percentiles', got {v!r}")
+    extra = set(v) - {"percentiles"}
+    if extra:
+        raise ValueError(f"gpu.serviceWindow: unknown key(s) {sorted(extra, key=str)!r}")
+    try:
+        qs = parse_window_percentiles(v.get("percentiles"))
+    except ValueError as e:
+        raise ValueError(str(e).replace("gpu.windowPercentiles", "gpu.serviceWindow.percentiles", 1)) from None
+    if not qs:
+        raise ValueError("gpu.serviceWindow: percentiles must list 1 to 8 percentiles")
+    return qs
+
+
+def service_window(cfg: Dict[str, Any]) -> List[int]:
+    """The validated gpu.serviceWindow percentiles of a config as integers q = p * 1000 ([]: off)."""
+    return parse_service_window(gpu_opt(cfg, "serviceWindow"))
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -294,6 +322,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         parse_latency_objectives(merged["latencyObjectives"])  # likewise
     if "leaderboard" in merged:
         parse_leaderboard(merged["leaderboard"])  # likewise
+    if "serviceWindow" in merged:
+        parse_service_window(merged["serviceWindow"])  # likewise
     return cfg
 
 

@@ -477,6 +477,45 @@ class LeaderboardEntry:
                 "per75": n(self.per75), "per95": n(self.per95)}
 
 
+# ---- sv: exact per-service window stats across servers (docs/SERVICEWINDOW.md).  Integers only.
+def _svc_int(s: Optional[str], max_len: int = 10, signed: bool = False) -> Optional[int]:
+    """A plain decimal of 1 to ``max_len`` digits, with a leading '-' when ``signed``; None: malformed
+    (copyenc.cpp holds the same rule)."""
+    if s is None:
+        return None
+    neg = signed and s.startswith("-")
+    d = s[1:] if neg else s
+    if not (d.isascii() and d.isdigit() and len(d) <= max_len):
+        return None
+    return -int(d) if neg else int(d)
+
+
+@dataclass
+class ServiceWindowEntry:
+    """``sv|ts|service|servers|m|nan|sum|p:v,p:v,...`` -- at a rollover, the union of the K8 windows
+    of a service's ``servers`` contributing series: ``m`` non-NaN samples (``nan`` counts the
+    others), their int64 ``sum`` and their exact percentiles (no reference counterpart).  ``pcts``
+    holds (q, sum2) integer pairs as WindowPctEntry does."""
+    timestamp: Num
+    service: str
+    servers: int
+    count: int
+    nan: int
+    elapsed_sum: int
+    pcts: List[tuple]
+    type: str = "sv"
+
+    def to_csv(self) -> str:
+        pairs = ",".join(f"{pct_text(q)}:{half_text(v)}" for q, v in self.pcts)
+        return (f"sv|{js_str(self.timestamp)}|{self.service}|{int(self.servers)}|{int(self.count)}|"
+                f"{int(self.nan)}|{int(self.elapsed_sum)}|{pairs}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "service": self.service, "servers": int(self.servers),
+                "count": int(self.count), "nan": int(self.nan), "elapsed_sum": int(self.elapsed_sum),
+                "pcts": {pct_text(q): (v // 2 if v % 2 == 0 else v / 2) for q, v in self.pcts}}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -539,7 +578,20 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
             return None
         pf = parse_float
         return LeaderboardEntry(parse_int(a[1]), a[2], rank, a[4], a[5], pf(a[6]), pf(a[7]), pf(a[8]), pf(a[9]))
+    if t == "sv":
+        a = _pad(arr, 8)
+        srv, cnt, nan = _svc_int(a[3]), _svc_int(a[4]), _svc_int(a[5])
+        tot = _svc_int(a[6], 18, signed=True)
+        if srv is None or cnt is None or nan is None or tot is None:  # (a malformed row is dropped, as copyenc.cpp does)
+            return None
+        pcts = []
+        for pr in (a[7] or "").split(","):
+            p, _sep, v = pr.partition(":")
+            q, s2 = _pct_from_text(p), _half_from_text(v)
+            if q is not None and s2 is not None:  # (a malformed pair is dropped, likewise)
+                pcts.append((q, s2))
+        return ServiceWindowEntry(parse_int(a[1]), a[2], srv, cnt, nan, tot, pcts)
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv")
