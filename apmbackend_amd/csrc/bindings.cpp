@@ -58,7 +58,10 @@ TzTable tz_from(const py::dict& d) {
   tz.offset_ms[0] = 0;
   if (d.contains("tz_table")) {
     auto rows = d["tz_table"].cast<std::vector<std::pair<int64_t, int64_t>>>();
-    tz.n = (int)std::min<size_t>(rows.size(), 64);
+    // ops/parse_ref.py tz_table picks the rows around a centre time; cutting here would keep the
+    // oldest instead
+    if (rows.size() > 64) throw std::invalid_argument("tz_table: more than 64 rows");
+    tz.n = (int)rows.size();
     for (int i = 0; i < tz.n; ++i) { tz.local_start[i] = rows[i].first; tz.offset_ms[i] = rows[i].second; }
     if (tz.n == 0) { tz.n = 1; tz.local_start[0] = INT64_MIN / 2; tz.offset_ms[0] = 0; }
   }

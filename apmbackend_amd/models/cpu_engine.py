@@ -18,9 +18,9 @@ _KIND_NAMES = {0: "SOAP", 1: "SERVER", 2: "APP"}
 
 
 class CpuOracleEngine:
-    def __init__(self, cfg: Dict[str, Any]):
+    def __init__(self, cfg: Dict[str, Any], tz: Optional[TzOffset] = None):
         g = cfg.get("gpu", {})
-        self.tz = TzOffset(g.get("timezone", "local"))
+        self.tz = tz if tz is not None else TzOffset(g.get("timezone", "local"))
         self.files_: List[Tuple[str, int, str]] = []
         self._server = {}
         self.P = PipelineOracle(copy.deepcopy(cfg), self.tz, alert_clock=g.get("alertClock", "entry"),

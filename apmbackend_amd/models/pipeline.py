@@ -16,6 +16,7 @@ from __future__ import annotations
 import logging
 import math
 import os
+import time
 from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 from .. import _native
@@ -61,14 +62,16 @@ def output_mask(kinds) -> int:
 
 
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
-                  **kw) -> Dict[str, Any]:
+                  tz: Optional[TzOffset] = None, tz_centre_ms: Optional[int] = None, **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
     materialises every stream but the opt-in lh / wp / sl / tk / sv; `outputs` (iterable of DEVICE_OUT_KINDS) selects explicitly.
     The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
     existed, `outputs` was ignored under keep_text).  "wp" takes its percentiles from
     gpu.windowPercentiles (ValueError when the list is missing or malformed), "sl" its thresholds
     from gpu.latencyObjectives (likewise), "tk" its boards from gpu.leaderboard (likewise), "sv" its percentiles
-    from gpu.serviceWindow (likewise)."""
+    from gpu.serviceWindow (likewise).  `tz` (a TzOffset) stands in for gpu.timezone; the zone's
+    transition table is centred on `tz_centre_ms` (default: the wall clock now, see
+    ops.parse_ref.tz_table)."""
     g = cfg.get("gpu", {})
     win_pcts = window_percentiles(cfg)
     if "wp" in (outputs or ()) and not win_pcts:
@@ -91,7 +94,8 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         raise ValueError(f"at most {MAX_LAGS} LAG settings are supported per engine")
     suppressed_lags = {int(x) for x in ac.get("suppressedLags", [])}
     ring = {"float64": 8, "float32": 4, "bfloat16": 2, "bf16": 2}.get(g.get("ringDtype", "float64"), 8)
-    tz = TzOffset(g.get("timezone", "local"))
+    if tz is None:
+        tz = TzOffset(g.get("timezone", "local"))
     d = {
         "device": device,
         "max_series": int(g.get("maxSeries", 1 << 17)),
@@ -129,7 +133,7 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         "record_ttl_ms": float(g.get("recordTtlSeconds", 120)) * 1000.0,
         "acct_ttl_ms": float(g.get("acctTtlSeconds", 120)) * 1000.0,
         "need_ttl_ms": float(g.get("needTtlSeconds", 30)) * 1000.0,
-        "tz_table": tz_table(tz),
+        "tz_table": tz_table(tz, tz_centre_ms),
         "join_threads": int(g.get("joinThreads", 0)),
         "pin_threads": bool(g.get("pinThreads", False)),
         "coll_timeout_ms": float(g.get("collectiveTimeoutSeconds", 300)) * 1000.0,
@@ -217,10 +221,16 @@ def _reload_generation(cfg: Dict[str, Any]) -> int:
 
 
 class APMEngine:
-    def __init__(self, cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None, **kw):
+    def __init__(self, cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
+                 tz: Optional[TzOffset] = None, tz_centre_ms: Optional[int] = None, **kw):
         self.cfg = cfg
         self.N = _native.load()
-        self.ecfg = engine_config(cfg, device, keep_text, outputs, **kw)
+        # the engine's zone (tz, else gpu.timezone as read now) and the time its transition table is
+        # centred on (the wall clock at construction).  Both are kept: the zone is not applied live,
+        # and a reload neither searches the zone's transitions again nor moves the table
+        self.tz = tz if tz is not None else TzOffset(cfg.get("gpu", {}).get("timezone", "local"))
+        self.tz_centre_ms = int(time.time() * 1000) if tz_centre_ms is None else int(tz_centre_ms)
+        self.ecfg = engine_config(cfg, device, keep_text, outputs, tz=self.tz, tz_centre_ms=self.tz_centre_ms, **kw)
         self.eng = self.N.Engine(self.ecfg)
         self.file_ids: Dict[str, int] = {}
         self.apply_overrides(cfg)
@@ -247,7 +257,7 @@ class APMEngine:
         (removeStaleLagData), every alert gate replaced -- staged now, applied by the engine at the
         next batch boundary (the same boundary on every lock-step rank).  Returns the engine
         settings that changed but need a restart (they are not applied)."""
-        new = engine_config(cfg, self.ecfg["device"], outputs=())
+        new = engine_config(cfg, self.ecfg["device"], outputs=(), tz=self.tz, tz_centre_ms=self.tz_centre_ms)
         restart = self.restart_required(self.ecfg, new)
         if restart:
             log.warning("config reload: %s changed but need a restart (not applied)", ", ".join(restart))

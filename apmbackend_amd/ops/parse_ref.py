@@ -11,12 +11,15 @@ implementation: the regex semantics are covered by the oracle tests.
 """
 from __future__ import annotations
 
+import logging
 import math
 from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from ..utils.timeparse import TzOffset, make_date_ms
+from ..utils.timeparse import SCAN_HI_MS, SCAN_LO_MS, TzOffset, make_date_ms
+
+log = logging.getLogger("apm.parse_ref")
 
 FILE_SOAP, FILE_SERVER, FILE_APP = 0, 1, 2
 LK_NONE, LK_EJB_ENTRY, LK_EJB_EXIT, LK_CT_ENTRY, LK_CT_EXIT, LK_SOAP, LK_APP = range(7)
@@ -387,21 +390,65 @@ def parse_batch(chunks: Sequence[Tuple[int, bytes]], tz: TzOffset, file_open: di
     return ev, line_idx, wm, buf
 
 
-def tz_table(tz: TzOffset, years=(1990, 2100)) -> List[Tuple[int, int]]:
-    """(local_start_ms, offset_ms) rows for the device/host TzTable (fixed zones: one row)."""
+TZ_ROWS = 64  # kernels/common.h TzTable: it travels by value in the parse kernels' arguments
+TZ_FIRST_START = -(1 << 61)
+
+
+def tz_rows(base_offset_ms: int, transitions, centre_ms: int, max_rows: int = TZ_ROWS):
+    """Transitions ``(utc_ms, offset_before, offset_after)`` -> ``(local_start_ms, offset_ms)`` rows
+    for local_to_utc (kernels/common.h), and whether any transition had to be left out.
+
+    A row starts at ``T + max(offset_before, offset_after)``: the local times a transition skips
+    (spring) or repeats (autumn) all lie before it, so they keep the offset from before the
+    transition, as ECMA-262's LocalTime and PEP 495 ``fold=0`` read them.  The first row starts
+    at TZ_FIRST_START.  Of more than ``max_rows - 1`` transitions, those around ``centre_ms`` are
+    kept: ``max_rows // 2`` after it and the rest before it (more on one side when the other has
+    fewer).  Outside them the nearest row's offset holds."""
+    tr = list(transitions)
+    keep = max_rows - 1
+    k = sum(1 for t, _, _ in tr if t <= centre_ms)
+    lo, hi = max(0, k - (keep - max_rows // 2)), min(len(tr), k + max_rows // 2)
+    lo = max(0, min(lo, hi - keep))
+    hi = min(len(tr), max(hi, lo + keep))
+    kept = tr[lo:hi]
+    start = lambda x: x[0] + max(x[1], x[2])
+    rows = [(TZ_FIRST_START, kept[0][1] if kept else base_offset_ms)]
+    rows += [(start(x), x[2]) for x in kept]
+    cover = (start(tr[lo - 1]) if lo > 0 else TZ_FIRST_START, start(tr[hi]) if hi < len(tr) else -TZ_FIRST_START)
+    return rows, cover
+
+
+def tz_coverage(tz: TzOffset, centre_ms: int = None):
+    """(rows, (lo, hi)): the TzTable rows for ``tz`` centred on ``centre_ms`` (default: the wall
+    clock now) and the local times lo <= t < hi for which they are exact.  A zone read from the
+    zone database is searched for transitions over timeparse.SCAN_LO_MS .. SCAN_HI_MS only, which
+    bounds the coverage too.  See tz_rows and docs/ARCHITECTURE.md."""
     if tz.fixed_ms is not None:
-        return [(-(1 << 61), tz.fixed_ms)]
-    import datetime as dt
-    rows = []
-    prev = None
-    t = dt.datetime(years[0], 1, 1, tzinfo=dt.timezone.utc)
-    end = dt.datetime(years[1], 1, 1, tzinfo=dt.timezone.utc)
-    step = dt.timedelta(hours=1)
-    while t < end and len(rows) < 64:
-        ms = int(t.timestamp() * 1000)
-        off = tz.offset_ms_for_utc(ms)
-        if off != prev:
-            rows.append((ms + off if rows else -(1 << 61), off))
-            prev = off
-        t += step if rows and len(rows) > 1 else dt.timedelta(days=7)
+        return [(TZ_FIRST_START, tz.fixed_ms)], (TZ_FIRST_START, -TZ_FIRST_START)
+    if centre_ms is None:
+        import time
+        centre_ms = int(time.time() * 1000)
+    base, tr = tz.base_and_transitions()
+    rows, (lo, hi) = tz_rows(base, tr, int(centre_ms))
+    if getattr(tz, "_trans", None) is None:  # found by search: nothing is known outside its span
+        lo, hi = max(lo, SCAN_LO_MS + 86400000), min(hi, SCAN_HI_MS - 86400000)
+    return rows, (lo, hi)
+
+
+_warned = set()  # (zone, coverage) that tz_table has warned about
+
+
+def tz_table(tz: TzOffset, centre_ms: int = None) -> List[Tuple[int, int]]:
+    """(local_start_ms, offset_ms) rows for the device/host TzTable (fixed zones: one row); a
+    warning is logged when the zone has more transitions than the table holds, once per process
+    for a zone and span (engines and config reloads build the same table again and again)."""
+    rows, (lo, hi) = tz_coverage(tz, centre_ms)
+    if len(rows) - 1 < len(tz.base_and_transitions()[1]) and (tz.spec, lo, hi) not in _warned:
+        _warned.add((tz.spec, lo, hi))
+        import datetime as dt
+        day = lambda ms: ("the end of time" if abs(ms) >= -TZ_FIRST_START else
+                          (dt.datetime(1970, 1, 1) + dt.timedelta(milliseconds=ms)).strftime("%Y-%m-%d"))
+        log.warning("timezone %s has %d transitions, the table holds %d: local times before %s or from %s on "
+                    "get the nearest row's offset", tz.spec, len(tz.base_and_transitions()[1]), TZ_ROWS - 1,
+                    day(lo), day(hi))
     return rows

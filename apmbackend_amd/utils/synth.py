@@ -57,9 +57,14 @@ class SynthConfig:
     logid_pad: int = 0
     seed: int = 1234
     tz_offset_ms: int = 0             # log timestamps written in this offset (UTC default)
+    # a zone (utils.timeparse.TzOffset): each log timestamp is written in the offset the zone has
+    # at that instant, and tz_offset_ms is not used
+    tz: Optional[object] = None
 
 
-def fmt_ts(ms: int, tz_offset_ms: int = 0) -> str:
+def fmt_ts(ms: int, tz_offset_ms: int = 0, tz=None) -> str:
+    if tz is not None:
+        tz_offset_ms = tz.offset_ms_for_utc(ms)
     t = dt.datetime(1970, 1, 1) + dt.timedelta(milliseconds=ms + tz_offset_ms)
     return t.strftime("%Y-%m-%d %H:%M:%S,") + f"{t.microsecond // 1000:03d}"
 
@@ -107,7 +112,7 @@ class Generator:
             self._emit(server, kind, ts, f"    <ns2:field{int(r * 9)}>value{int(r * 1000)}</ns2:field{int(r * 9)}>")
         else:
             lvl = "DEBUG" if r < 0.6 else "INFO "
-            self._emit(server, kind, ts, f"[{log_id}] {fmt_ts(ts, self.cfg.tz_offset_ms)} {lvl} "
+            self._emit(server, kind, ts, f"[{log_id}] {fmt_ts(ts, self.cfg.tz_offset_ms, self.cfg.tz)} {lvl} "
                                          f"[com.acme.svc.Handler{int(r * 50)}] processed step {int(r * 1e6)}")
 
     def transaction(self, server: str, t0: int, idx: int):
@@ -137,7 +142,7 @@ class Generator:
         self._emit(server, "soap_io.log", soap_t + 1, f"=== jbossId={log_id} IO=O")
         # top-level EJB timing
         self._emit(server, "server.log", t0,
-                   f"[{lid}] {fmt_ts(t0, tz)} INFO  [CommonTiming] The EJB call started for bean "
+                   f"[{lid}] {fmt_ts(t0, tz, c.tz)} INFO  [CommonTiming] The EJB call started for bean "
                    f"Delegation method: {ejb}")
         for _ in range(c.noise_lines_per_tx):
             kind = rng.choice(["server.log", "app.log", "app.log"])
@@ -165,16 +170,16 @@ class Generator:
             baf = rng.random() < c.baf_fraction
             pre = f"[baf][x:y:{acct}] " if baf else ""
             self._emit(server, "app.log", s_t,
-                       f"[{lid}] {fmt_ts(s_t, tz)} {pre}INFO  CommonTiming::Start: {svc} begin")
+                       f"[{lid}] {fmt_ts(s_t, tz, c.tz)} {pre}INFO  CommonTiming::Start: {svc} begin")
             self._emit(server, "app.log", e_t,
-                       f"[{lid}] {fmt_ts(e_t, tz)} {pre}INFO  CommonTiming::Stop: {svc} - total time {el} ms")
+                       f"[{lid}] {fmt_ts(e_t, tz, c.tz)} {pre}INFO  CommonTiming::Stop: {svc} - total time {el} ms")
         if use_audit:
             autr = f"A{idx:07d}{server}"
             ta = t0 + 2
-            self._emit(server, "app.log", ta, f"[{log_id}] {fmt_ts(ta, tz)} [baf][x:{acct}] INFO  auditTrailId={autr}")
+            self._emit(server, "app.log", ta, f"[{log_id}] {fmt_ts(ta, tz, c.tz)} [baf][x:{acct}] INFO  auditTrailId={autr}")
             tb = t_end - 1
             block = [f"Audit Trail id : {autr}",
-                     f"[{log_id}] {fmt_ts(tb, tz)} INFO  com.acme.Audit: RequestTrace [stopWatchList="]
+                     f"[{log_id}] {fmt_ts(tb, tz, c.tz)} INFO  com.acme.Audit: RequestTrace [stopWatchList="]
             rules_el = rng.randint(1, 40)
             for svc, s_t, e_t, el in sub_records:
                 block.append(f"  {svc}:[{el} millis] ok")
@@ -189,7 +194,7 @@ class Generator:
             for ln in block:
                 self._emit(server, "app.log", tb, ln)
         self._emit(server, "server.log", t_end,
-                   f"[{lid}] {fmt_ts(t_end, tz)} INFO  [CommonTiming] Total time taken for: {ejb} - {total} ms")
+                   f"[{lid}] {fmt_ts(t_end, tz, c.tz)} INFO  [CommonTiming] Total time taken for: {ejb} - {total} ms")
 
     def generate(self) -> Dict[str, List[Tuple[int, int, str]]]:
         c = self.cfg

@@ -13,11 +13,13 @@ UTC-offset table, so both sides agree bit-for-bit on the integer millisecond res
 """
 from __future__ import annotations
 
+import bisect
+import datetime as dt
 import math
 import os
 import re
 import time
-from typing import Optional
+from typing import Callable, List, Optional, Sequence, Tuple
 
 _SPLIT_RE = re.compile(r"-|\s+|:|,")
 _ISO_RE = re.compile(
@@ -68,14 +70,54 @@ def make_date_ms(y: float, mon0: float, d: float, h: float, mi: float, s: float,
     return float(day * 86400000 + t)
 
 
+EPOCH_UTC = dt.datetime(1970, 1, 1, tzinfo=dt.timezone.utc)
+WEEK_MS = 7 * 86400000
+# the span searched for a zone's transitions (1900-01-01 .. 2200-01-01 UTC)
+SCAN_LO_MS = -2208988800000
+SCAN_HI_MS = 7258118400000
+
+Transition = Tuple[int, int, int]  # (utc_ms of the first instant of the new offset, offset before, offset after)
+
+
+def find_transitions(offset_at: Callable[[int], int], lo_ms: int = SCAN_LO_MS, hi_ms: int = SCAN_HI_MS,
+                     step_ms: int = WEEK_MS) -> List[Transition]:
+    """Every change of ``offset_at(utc_ms)`` in (lo_ms, hi_ms], exact to the millisecond: probes
+    at most ``step_ms`` apart, then a bisection between two probes that differ.  Two changes less
+    than ``step_ms`` apart that cancel each other are not seen."""
+    out: List[Transition] = []
+    t = lo_ms
+    prev = offset_at(t)
+    while t < hi_ms:
+        u = min(t + step_ms, hi_ms)
+        if offset_at(u) == prev:
+            t = u
+            continue
+        a, b = t, u  # offset_at(a) == prev != offset_at(b)
+        while b - a > 1:
+            m = (a + b) // 2
+            if offset_at(m) == prev:
+                a = m
+            else:
+                b = m
+        new = offset_at(b)
+        out.append((b, prev, new))
+        prev, t = new, b  # a further change inside (b, u] is found from here
+    return out
+
+
 class TzOffset:
     """UTC offset provider. ``local`` uses the process zone at parse time; ``UTC``/``+HH:MM``
-    are fixed; IANA names use zoneinfo (first occurrence in a DST overlap)."""
+    are fixed; IANA names use zoneinfo; ``from_transitions`` takes the zone's transitions as
+    data.  A local time that a transition skips or repeats is read with the offset from before
+    the transition (ECMA-262 LocalTime / PEP 495 ``fold=0``)."""
 
     def __init__(self, spec: str = "local"):
         self.spec = spec or "local"
         self.fixed_ms: Optional[int] = None
         self.zone = None
+        self._trans: Optional[List[Transition]] = None  # set: the zone is this list and _base
+        self._base = 0
+        self._found: Optional[List[Transition]] = None
         if self.spec.upper() in ("UTC", "Z", "GMT"):
             self.fixed_ms = 0
         elif re.match(r"^[+-]\d{2}:?\d{2}$", self.spec):
@@ -86,29 +128,65 @@ class TzOffset:
             from zoneinfo import ZoneInfo
             self.zone = ZoneInfo(self.spec)
 
+    @classmethod
+    def from_transitions(cls, base_offset_ms: int, transitions: Sequence[Transition],
+                         spec: str = "transitions") -> "TzOffset":
+        """A zone given as data: ``base_offset_ms`` holds before the first transition, then each
+        ``(utc_ms, offset_before, offset_after)`` in turn.  Needs no zone database."""
+        tz = cls("UTC")
+        tz.spec = spec
+        tz.fixed_ms = None
+        tz._base = int(base_offset_ms)
+        tz._trans = sorted((int(t), int(a), int(b)) for t, a, b in transitions)
+        prev = tz._base
+        for _, a, b in tz._trans:
+            if a != prev or a == b:
+                raise ValueError("transitions do not chain: each offset_before must be the offset in force")
+            prev = b
+        tz._utc_starts = [t for t, _, _ in tz._trans]
+        tz._local_starts = [t + max(a, b) for t, a, b in tz._trans]
+        return tz
+
+    def base_and_transitions(self) -> Tuple[int, List[Transition]]:
+        """(offset before the first transition, transitions) over the searched span."""
+        if self.fixed_ms is not None:
+            return self.fixed_ms, []
+        if self._trans is not None:
+            return self._base, self._trans
+        if self._found is None:
+            self._found = find_transitions(self.offset_ms_for_utc)
+        return self.offset_ms_for_utc(SCAN_LO_MS), self._found
+
     def local_to_utc(self, local_ms: float) -> float:
         if math.isnan(local_ms):
             return NAN
         if self.fixed_ms is not None:
             return local_ms - self.fixed_ms
+        if self._trans is not None:
+            # the row rule of the device table: a transition's offset holds from T + max(before, after)
+            i = bisect.bisect_right(self._local_starts, local_ms)
+            return local_ms - (self._trans[i - 1][2] if i else self._base)
         if self.zone is not None:
-            import datetime as dt
             base = dt.datetime(1970, 1, 1) + dt.timedelta(milliseconds=local_ms)
-            off = self.zone.utcoffset(base.replace(fold=0))
-            return local_ms - off.total_seconds() * 1000.0
+            off = base.replace(tzinfo=self.zone, fold=0).utcoffset()
+            return local_ms - (off.days * 86400000 + off.seconds * 1000 + off.microseconds // 1000)
         # process-local zone: JS uses the offset in effect at that local time
         guess = local_ms / 1000.0
         off = -time.altzone if time.localtime(guess).tm_isdst > 0 else -time.timezone
         return local_ms - off * 1000.0
 
     def offset_ms_for_utc(self, utc_ms: float) -> int:
+        """The zone's offset at the instant ``utc_ms``."""
         if self.fixed_ms is not None:
             return self.fixed_ms
+        if self._trans is not None:
+            i = bisect.bisect_right(self._utc_starts, utc_ms)
+            return self._trans[i - 1][2] if i else self._base
         if self.zone is not None:
-            import datetime as dt
-            t = dt.datetime.fromtimestamp(utc_ms / 1000.0, tz=dt.timezone.utc)
-            return int(self.zone.utcoffset(t.replace(tzinfo=None)).total_seconds() * 1000)
-        lt = time.localtime(utc_ms / 1000.0)
+            t = EPOCH_UTC + dt.timedelta(milliseconds=math.floor(utc_ms))
+            off = t.astimezone(self.zone).utcoffset()
+            return off.days * 86400000 + off.seconds * 1000 + off.microseconds // 1000
+        lt = time.localtime(math.floor(utc_ms / 1000.0))
         return int(lt.tm_gmtoff * 1000)
 
 
@@ -122,24 +200,26 @@ def default_tz() -> TzOffset:
     return _DEFAULT_TZ
 
 
-def parse_iso(s: str) -> float:
+def parse_iso(s: str, tz: Optional[TzOffset] = None) -> float:
+    """``new Date(s)`` for the ISO date-time form; a stamp without an offset is local time in
+    ``tz`` (the configured zone; ``default_tz()`` when none is given)."""
     m = _ISO_RE.match(s)
     if not m:
         return NAN
-    y, mo, d, h, mi, sec, frac, tz = m.groups()
+    y, mo, d, h, mi, sec, frac, zone = m.groups()
     y, mo, d, h, mi = int(y), int(mo), int(d), int(h), int(mi)
     sec = int(sec) if sec else 0
     ms = int((frac or "0")[:3].ljust(3, "0"))
     if not (1 <= mo <= 12 and 1 <= d <= 31 and h <= 24 and mi <= 59 and sec <= 59):
         return NAN
     t = make_date_ms(y, mo - 1, d, h, mi, sec, ms)
-    if tz is None:
+    if zone is None:
         # ES2015+: date-time forms without offset are local time
-        return default_tz().local_to_utc(t)
-    if tz == "Z":
+        return (tz or default_tz()).local_to_utc(t)
+    if zone == "Z":
         return t
-    sgn = -1 if tz[0] == "-" else 1
-    tzd = tz[1:].replace(":", "")
+    sgn = -1 if zone[0] == "-" else 1
+    tzd = zone[1:].replace(":", "")
     off = (int(tzd[:2]) * 60 + int(tzd[2:])) * 60000
     return t - sgn * off
 
@@ -149,7 +229,7 @@ def convert_string_date_to_ms(date_str: Optional[str], tz: Optional[TzOffset] = 
     if not date_str:
         return None
     if re.search(r"T.*-", date_str):
-        return parse_iso(date_str)
+        return parse_iso(date_str, tz)
     arr = _SPLIT_RE.split(date_str.strip())
     get = lambda i: arr[i] if i < len(arr) else None
     nums = [js_number(get(i)) if get(i) is not None else NAN for i in range(7)]
