@@ -5,7 +5,7 @@
 // 80k series and two LAGs that is ~25 MB of text per 10 s interval, far too much to format on
 // the host thread that owns the pipeline.  The classic two-pass scheme:
 //   pass 1  one lane per series in emission order: line lengths (st, sum over LAGs of fs)
-//   scan    exclusive prefix sums (rocprim) -> byte offsets
+//   scan    exclusive prefix sums (textpass.h) -> byte offsets
 //   pass 2  same lane re-formats straight into the output at its offset
 // Number printing reproduces Number.prototype.toFixed exactly: the rounding decision uses the
 // error-free product x*10^f = p + e (fma), ties to the larger n (ECMA-262 21.1.3.3), then the
@@ -14,9 +14,7 @@
 // an integer; from 1e21 JS prints String(x).  Only |x| >= 2^127 is not exact (flagged, counted).
 #include "kernel_api.h"  // (common.h pulls <cstring> in before rocprim)
 #include "devjoin_dev.h"
-#include "textout.h"
-
-#include "prim.h"
+#include "textpass.h"
 
 #include <cstdlib>
 
@@ -153,21 +151,6 @@ constexpr int FMT_WAVE_LINES = 64;
 // to 162 VGPRs (profiles/r5_q .. r5_u).
 constexpr uint32_t FMT_LDS = 8192;
 
-__device__ __forceinline__ void wave_copy_out(const char* __restrict__ lds, char* __restrict__ out, uint32_t g0,
-                                              uint32_t g1) {
-  const uint32_t a0 = g0 & ~3u;
-  const uint32_t nd = (g1 - a0 + 3) / 4;
-  for (uint32_t d = threadIdx.x; d < nd; d += FMT_WAVE_LINES) {
-    const uint32_t ga = a0 + 4 * d;
-    if (ga >= g0 && ga + 4 <= g1) {
-      *reinterpret_cast<uint32_t*>(out + ga) = *reinterpret_cast<const uint32_t*>(lds + 4 * d);
-    } else {  // the block's first / last dword is shared with a neighbour: byte stores
-      for (uint32_t b = 0; b < 4; ++b)
-        if (ga + b >= g0 && ga + b < g1) out[ga + b] = lds[4 * d + b];
-    }
-  }
-}
-
 template <uint32_t LDS>
 __global__ __launch_bounds__(FMT_WAVE_LINES) void k_format_write(FormatArgs a, int32_t st_blocks) {
   __shared__ __align__(16) char stage[LDS];
@@ -188,7 +171,7 @@ __global__ __launch_bounds__(FMT_WAVE_LINES) void k_format_write(FormatArgs a, i
     o.finish();
   }
   __syncthreads();
-  if (lds) wave_copy_out(stage, out, g0, g1);
+  if (lds) block_copy_out<FMT_WAVE_LINES>(stage, out, g0, g1);
 }
 
 // ---- fb: fleet baseline rows ------------------------------------------------------------
@@ -295,7 +278,7 @@ __global__ __launch_bounds__(FMT_WAVE_LINES) void k_fleet_rows(FleetFormatArgs a
   bool fb2 = false;
   if (i < n && len) fleet_row<true>(a, i, lds ? stage + (off - (g0 & ~3u)) : a.out + off, fb2);
   __syncthreads();
-  if (lds) wave_copy_out(stage, a.out, g0, g1);
+  if (lds) block_copy_out<FMT_WAVE_LINES>(stage, a.out, g0, g1);
 }
 
 // mode 0: nf(x, f); 1: js_fixed as a JSON number; 2: js_fixed as a COPY field
@@ -323,15 +306,7 @@ __global__ void k_fixed_batch(const double* x, int n, int f, int mode, char* out
 extern "C" {
 using namespace apm;
 
-static int fmt_scan_lens(PrimScratch& sc, const uint32_t* len, uint32_t* off, size_t n, hipStream_t stream) {
-  return prim_exclusive_scan(sc, len, off, 0u, n, rocprim::plus<uint32_t>(), stream);
-}
-
-size_t apm_format_tmp_bytes(int32_t n_max) {
-  PrimScratch q;
-  fmt_scan_lens(q, nullptr, nullptr, (size_t)n_max + 1, 0);
-  return q.need;
-}
+size_t apm_format_tmp_bytes(int32_t n_max) { return text_scan_tmp_bytes(n_max); }
 
 // Lengths + scan: afterwards st_off/fs_off[0..n] hold exclusive offsets, [n] = total bytes.
 // The *_len / *_off arrays hold n + 1 entries.
@@ -341,8 +316,8 @@ int apm_format_plan(FormatArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stre
   const int32_t lanes = a->n * a->n_lags + 1;  // >= n + 1 (n_lags >= 1)
   hipLaunchKernelGGL(k_format_len, dim3((lanes + 255) / 256), dim3(256), 0, stream, *a);
   PrimScratch sc(tmp, tmp_bytes);
-  if (fmt_scan_lens(sc, a->st_len, a->st_off, (size_t)a->n + 1, stream) != 0) return -1;
-  return fmt_scan_lens(sc, a->fs_len, a->fs_off, (size_t)a->n * a->n_lags + 1, stream);
+  if (text_scan(sc, a->st_len, a->st_off, (size_t)a->n + 1, stream) != 0) return -1;
+  return text_scan(sc, a->fs_len, a->fs_off, (size_t)a->n * a->n_lags + 1, stream);
 }
 
 // Test hook: nf(x[i], f) (mode 0) or js_fixed(x[i], f, json = mode == 1) (modes 1, 2) into 32-byte

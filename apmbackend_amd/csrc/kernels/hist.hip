@@ -2,7 +2,7 @@
 // histogram (docs/HISTOGRAM.md), encoded on the GPU like the st / fs rows (format.hip):
 //   count  per emission position: 120-counter LDS histogram of the bucket's samples (inline cell +
 //          the series' run in the slot's sorted spill list), row length from the non-zero bins
-//   scan   exclusive prefix sums (rocprim) -> byte offsets
+//   scan   exclusive prefix sums (textpass.h) -> byte offsets
 //   write  the same histogram again, each lane prints its bins at its offset inside the row
 // A bucket reads 1 / window of what K8 reads, so rebuilding the histogram in the write pass is
 // cheaper than keeping 120 counters per series between the passes.
@@ -14,9 +14,8 @@
 // each, lane 31 the newline; a lane's offset inside the row is the scan of the lanes' byte counts.
 #include "kernel_api.h"  // (common.h pulls <cstring> in before rocprim)
 #include "devjoin_dev.h"
-#include "textout.h"
+#include "textpass.h"
 
-#include "prim.h"
 #include "spill.h"
 
 namespace apm {
@@ -167,15 +166,7 @@ using namespace apm;
 
 int32_t apm_hist_group_max() { return HIST_GROUP_MAX; }
 
-static int hist_scan(PrimScratch& sc, const uint32_t* len, uint32_t* off, size_t n, hipStream_t stream) {
-  return prim_exclusive_scan(sc, len, off, 0u, n, rocprim::plus<uint32_t>(), stream);
-}
-
-size_t apm_hist_tmp_bytes(int32_t n_max) {
-  PrimScratch q;
-  hist_scan(q, nullptr, nullptr, (size_t)n_max + 1, 0);
-  return q.need;
-}
+size_t apm_hist_tmp_bytes(int32_t n_max) { return text_scan_tmp_bytes(n_max); }
 
 // "lh|" + ts (<= 23) + names + 2 separators + count| + nan| (11 each) + 120 pairs of at most
 // 10 + 1 + 10 digits and a comma + newline
@@ -190,7 +181,7 @@ int apm_hist_plan(HistArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream) 
   hipLaunchKernelGGL(k_hist_group<false>, dim3(hist_group_blocks(a->n)), dim3(HIST_GROUPS * HIST_LANES), 0, stream, *a);
   hipLaunchKernelGGL(k_hist_big<false>, dim3(HIST_BIG_GRID), dim3(HIST_BLOCK), 0, stream, *a);
   PrimScratch sc(tmp, tmp_bytes);
-  return hist_scan(sc, a->len, a->off, (size_t)a->n + 1, stream);
+  return text_scan(sc, a->len, a->off, (size_t)a->n + 1, stream);
 }
 
 void apm_hist_write(HistArgs* a, hipStream_t stream) {

@@ -12,12 +12,12 @@
 // Only integers: c_j = #{v != ELAPSED_NAN : v <= T_j}, cumulative by construction.
 // Text pass: K12's count / scan / write shape; k_slo_write stages a 64-row block in LDS and stores
 // the block's contiguous byte range one dword per lane (k_format_write's way); a block over the
-// stage stores its rows directly through textout.h.
+// stage stores its rows directly through textout.h.  The length kernel, the scan and the stage's
+// copy-out are textpass.h's.
 #include "kernel_api.h"  // (common.h pulls <cstring> in before rocprim)
 #include "devjoin_dev.h"
-#include "textout.h"
+#include "textpass.h"
 
-#include "prim.h"
 #include "spill.h"
 #include "winsort.h"
 
@@ -210,34 +210,14 @@ __device__ __forceinline__ int32_t sl_row_series(const SloTextArgs& a, int32_t i
   return k >= 1 && a.rec[s].m >= 1 ? s : -1;
 }
 
-__global__ __launch_bounds__(SL_LEN_BLOCK) void k_slo_len(SloTextArgs a) {
-  const int32_t i = (int32_t)(blockIdx.x * SL_LEN_BLOCK + threadIdx.x);
-  if (i > a.n) return;
-  uint32_t len = 0;  // (position n: the scan sentinel -> total)
-  if (i < a.n) {
+// the length pass' row policy (k_text_len)
+struct SlRow {
+  static __device__ __forceinline__ uint32_t len(const SloTextArgs& a, int32_t i) {
     int cls = 0, k = 0;
     const int32_t s = sl_row_series(a, i, cls, k);
-    if (s >= 0) len = sl_row<false>(a, s, cls, k, nullptr);
+    return s >= 0 ? sl_row<false>(a, s, cls, k, nullptr) : 0u;
   }
-  a.len[i] = len;
-}
-
-// the block's byte range [g0, g1) from the stage (laid out like the output from g0 & ~3 on): one
-// dword per lane per store; the first / last dword, shared with the neighbouring blocks, bytewise
-__device__ __forceinline__ void sl_copy_out(const char* __restrict__ lds, char* __restrict__ out, uint32_t g0,
-                                            uint32_t g1) {
-  const uint32_t a0 = g0 & ~3u;
-  const uint32_t nd = (g1 - a0 + 3) / 4;
-  for (uint32_t d = threadIdx.x; d < nd; d += SL_ROWS) {
-    const uint32_t ga = a0 + 4 * d;
-    if (ga >= g0 && ga + 4 <= g1) {
-      *reinterpret_cast<uint32_t*>(out + ga) = *reinterpret_cast<const uint32_t*>(lds + 4 * d);
-    } else {
-      for (uint32_t b = 0; b < 4; ++b)
-        if (ga + b >= g0 && ga + b < g1) out[ga + b] = lds[4 * d + b];
-    }
-  }
-}
+};
 
 __global__ __launch_bounds__(SL_ROWS) void k_slo_write(SloTextArgs a) {
   __shared__ __align__(16) char stage[SL_STAGE];
@@ -256,7 +236,7 @@ __global__ __launch_bounds__(SL_ROWS) void k_slo_write(SloTextArgs a) {
     }
   }
   __syncthreads();
-  if (lds) sl_copy_out(stage, a.out, g0, g1);
+  if (lds) block_copy_out<SL_ROWS>(stage, a.out, g0, g1);
 }
 
 }  // namespace
@@ -269,15 +249,7 @@ using namespace apm;
 int32_t apm_slo_group_max() { return SL_GROUP_MAX; }
 int32_t apm_slo_stage_bytes() { return (int32_t)SL_STAGE; }
 
-static int slo_scan(PrimScratch& sc, const uint32_t* len, uint32_t* off, size_t n, hipStream_t stream) {
-  return prim_exclusive_scan(sc, len, off, 0u, n, rocprim::plus<uint32_t>(), stream);
-}
-
-size_t apm_slo_tmp_bytes(int32_t n_max) {
-  PrimScratch q;
-  slo_scan(q, nullptr, nullptr, (size_t)n_max + 1, 0);
-  return q.need;
-}
+size_t apm_slo_tmp_bytes(int32_t n_max) { return text_scan_tmp_bytes(n_max); }
 
 // "sl|" + ts (<= 23) + names + 2 separators + m| + nan| (11 each) + 8 pairs of at most 10 + 10
 // digits, a colon and a comma + newline
@@ -295,12 +267,7 @@ void apm_slo_values(SloArgs* a, hipStream_t stream) {
 }
 
 int apm_slo_plan(SloTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream) {
-  if (a->n <= 0) return 0;
-  // (n + 1 positions: position n stores the scan sentinel)
-  hipLaunchKernelGGL(k_slo_len, dim3((uint32_t)((a->n + 1 + SL_LEN_BLOCK - 1) / SL_LEN_BLOCK)), dim3(SL_LEN_BLOCK), 0,
-                     stream, *a);
-  PrimScratch sc(tmp, tmp_bytes);
-  return slo_scan(sc, a->len, a->off, (size_t)a->n + 1, stream);
+  return text_plan<SlRow, SL_LEN_BLOCK>(a, tmp, tmp_bytes, stream);
 }
 
 void apm_slo_write(SloTextArgs* a, hipStream_t stream) {

@@ -16,12 +16,12 @@
 // Only integers: the rank rule is K16's wp_ranks on q = p * 1000, a value the int64 sum of the two
 // ranks (one rank: twice the sample).
 // Text pass: K12's count / scan / write shape, one lane per emission position, through textout.h:
-// a position prints the row of its series' service when it is the first active member's.
+// a position prints the row of its series' service when it is the first active member's.  The
+// length kernel, the scan and the half-value printer are textpass.h's.
 #include "kernel_api.h"  // (common.h pulls <cstring> in before rocprim)
 #include "devjoin_dev.h"
-#include "textout.h"
+#include "textpass.h"
 
-#include "prim.h"
 #include "spill.h"
 #include "winsort.h"
 
@@ -287,12 +287,7 @@ __device__ __forceinline__ uint32_t sv_row(const SvcWinTextArgs& a, int32_t g, i
     if (j < a.nq) {
       if (j) o.c(',');
       o.sb(a.ptxt[j], a.plen[j]);
-      const long long v = r.sum2[j];
-      // |v| <= 2^32: the integer half fits 32 bits
-      const unsigned long long mag = v < 0 ? (unsigned long long)(-v) : (unsigned long long)v;
-      if (v < 0) o.c('-');
-      o.u32((uint32_t)(mag >> 1));
-      if (mag & 1ull) o.lit(".5");
+      text_half(o, r.sum2[j]);
     }
   }
   o.c('\n');
@@ -309,17 +304,14 @@ __device__ __forceinline__ int32_t sv_row_group(const SvcWinTextArgs& a, int32_t
   return a.rec[g].m >= 1 && a.rec[g].first_pos == i ? g : -1;
 }
 
-__global__ __launch_bounds__(SV_TEXT_BLOCK) void k_svcwin_len(SvcWinTextArgs a) {
-  const int32_t i = (int32_t)(blockIdx.x * SV_TEXT_BLOCK + threadIdx.x);
-  if (i > a.n) return;
-  uint32_t len = 0;  // (position n: the scan sentinel -> total)
-  if (i < a.n) {
+// the length pass' row policy (k_text_len)
+struct SvRow {
+  static __device__ __forceinline__ uint32_t len(const SvcWinTextArgs& a, int32_t i) {
     int32_t s;
     const int32_t g = sv_row_group(a, i, s);
-    if (g >= 0) len = sv_row<false>(a, g, s, nullptr);
+    return g >= 0 ? sv_row<false>(a, g, s, nullptr) : 0u;
   }
-  a.len[i] = len;
-}
+};
 
 __global__ __launch_bounds__(SV_TEXT_BLOCK) void k_svcwin_write(SvcWinTextArgs a) {
   const int32_t i = (int32_t)(blockIdx.x * SV_TEXT_BLOCK + threadIdx.x);
@@ -339,15 +331,7 @@ using namespace apm;
 int32_t apm_svcwin_group_max() { return SV_GROUP_MAX; }
 int32_t apm_svcwin_group_win() { return SV_GROUP_WIN; }
 
-static int svcwin_scan(PrimScratch& sc, const uint32_t* len, uint32_t* off, size_t n, hipStream_t stream) {
-  return prim_exclusive_scan(sc, len, off, 0u, n, rocprim::plus<uint32_t>(), stream);
-}
-
-size_t apm_svcwin_tmp_bytes(int32_t n_max) {
-  PrimScratch q;
-  svcwin_scan(q, nullptr, nullptr, (size_t)n_max + 1, 0);
-  return q.need;
-}
+size_t apm_svcwin_tmp_bytes(int32_t n_max) { return text_scan_tmp_bytes(n_max); }
 
 // "sv|" + ts (<= 23) + name + separator + servers| + m| + nan| (11 each) + sum| (a sign, 19
 // digits) + nq pairs of at most 7 label bytes, a sign, 10 digits, ".5" and a comma + newline
@@ -365,19 +349,14 @@ void apm_svcwin_values(SvcWinArgs* a, hipStream_t stream) {
   hipLaunchKernelGGL(k_svcwin_big, dim3(SV_BIG_GRID), dim3(SV_BLOCK), 0, stream, *a);
 }
 
-static uint32_t svcwin_text_blocks(int32_t n) { return (uint32_t)((n + 1 + SV_TEXT_BLOCK - 1) / SV_TEXT_BLOCK); }
-
 int apm_svcwin_plan(SvcWinTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream) {
-  if (a->n <= 0) return 0;
-  // (n + 1 positions: position n stores the scan sentinel)
-  hipLaunchKernelGGL(k_svcwin_len, dim3(svcwin_text_blocks(a->n)), dim3(SV_TEXT_BLOCK), 0, stream, *a);
-  PrimScratch sc(tmp, tmp_bytes);
-  return svcwin_scan(sc, a->len, a->off, (size_t)a->n + 1, stream);
+  return text_plan<SvRow, SV_TEXT_BLOCK>(a, tmp, tmp_bytes, stream);
 }
 
 void apm_svcwin_write(SvcWinTextArgs* a, hipStream_t stream) {
   if (a->n <= 0) return;
-  hipLaunchKernelGGL(k_svcwin_write, dim3(svcwin_text_blocks(a->n)), dim3(SV_TEXT_BLOCK), 0, stream, *a);
+  // (the length pass' grid: n + 1 positions)
+  hipLaunchKernelGGL(k_svcwin_write, dim3(text_len_blocks(a->n, SV_TEXT_BLOCK)), dim3(SV_TEXT_BLOCK), 0, stream, *a);
 }
 
 }  // extern "C"

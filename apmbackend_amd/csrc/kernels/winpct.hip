@@ -12,12 +12,12 @@
 //          tile whose size would be one more boundary.
 // Only integers: the rank rule is calcPercentile in exact rational arithmetic on q = p * 1000
 // (wp_ranks), the value the int64 sum of the two ranks (one rank: twice the sample).
-// Text pass: K12's count / scan / write shape, one lane per emission position, through textout.h.
+// Text pass: K12's count / scan / write shape, one lane per emission position, through textout.h;
+// the length kernel, the scan and the half-value printer are textpass.h's.
 #include "kernel_api.h"  // (common.h pulls <cstring> in before rocprim)
 #include "devjoin_dev.h"
-#include "textout.h"
+#include "textpass.h"
 
-#include "prim.h"
 #include "spill.h"
 #include "winsort.h"
 
@@ -193,12 +193,7 @@ __device__ __forceinline__ uint32_t wp_row(const WinPctTextArgs& a, int32_t s, c
     if (j < a.nq) {
       if (j) o.c(',');
       o.sb(a.ptxt[j], a.plen[j]);
-      const long long v = a.sum2[(size_t)s * a.nq + j];
-      // |v| <= 2^32: the integer half fits 32 bits
-      const unsigned long long mag = v < 0 ? (unsigned long long)(-v) : (unsigned long long)v;
-      if (v < 0) o.c('-');
-      o.u32((uint32_t)(mag >> 1));
-      if (mag & 1ull) o.lit(".5");
+      text_half(o, a.sum2[(size_t)s * a.nq + j]);
     }
   }
   o.c('\n');
@@ -213,16 +208,13 @@ __device__ __forceinline__ int32_t wp_row_series(const WinPctTextArgs& a, int32_
   return a.m[s] >= 1 ? s : -1;
 }
 
-__global__ __launch_bounds__(WP_TEXT_BLOCK) void k_winpct_len(WinPctTextArgs a) {
-  const int32_t i = (int32_t)(blockIdx.x * WP_TEXT_BLOCK + threadIdx.x);
-  if (i > a.n) return;
-  uint32_t len = 0;  // (position n: the scan sentinel -> total)
-  if (i < a.n) {
+// the length pass' row policy (k_text_len)
+struct WpRow {
+  static __device__ __forceinline__ uint32_t len(const WinPctTextArgs& a, int32_t i) {
     const int32_t s = wp_row_series(a, i);
-    if (s >= 0) len = wp_row<false>(a, s, nullptr);
+    return s >= 0 ? wp_row<false>(a, s, nullptr) : 0u;
   }
-  a.len[i] = len;
-}
+};
 
 __global__ __launch_bounds__(WP_TEXT_BLOCK) void k_winpct_write(WinPctTextArgs a) {
   const int32_t i = (int32_t)(blockIdx.x * WP_TEXT_BLOCK + threadIdx.x);
@@ -241,15 +233,7 @@ using namespace apm;
 int32_t apm_winpct_group_max() { return WP_GROUP_MAX; }
 int32_t apm_winpct_group_win() { return WP_GROUP_WIN; }
 
-static int winpct_scan(PrimScratch& sc, const uint32_t* len, uint32_t* off, size_t n, hipStream_t stream) {
-  return prim_exclusive_scan(sc, len, off, 0u, n, rocprim::plus<uint32_t>(), stream);
-}
-
-size_t apm_winpct_tmp_bytes(int32_t n_max) {
-  PrimScratch q;
-  winpct_scan(q, nullptr, nullptr, (size_t)n_max + 1, 0);
-  return q.need;
-}
+size_t apm_winpct_tmp_bytes(int32_t n_max) { return text_scan_tmp_bytes(n_max); }
 
 // "wp|" + ts (<= 23) + names + 2 separators + m| + nan| (11 each) + nq pairs of at most 7 label
 // bytes, a sign, 10 digits, ".5" and a comma + newline
@@ -267,19 +251,14 @@ void apm_winpct_values(WinPctArgs* a, hipStream_t stream) {
   hipLaunchKernelGGL(k_winpct_big, dim3(WP_BIG_GRID), dim3(WP_BLOCK), 0, stream, *a);
 }
 
-static uint32_t winpct_text_blocks(int32_t n) { return (uint32_t)((n + 1 + WP_TEXT_BLOCK - 1) / WP_TEXT_BLOCK); }
-
 int apm_winpct_plan(WinPctTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream) {
-  if (a->n <= 0) return 0;
-  // (n + 1 positions: position n stores the scan sentinel)
-  hipLaunchKernelGGL(k_winpct_len, dim3(winpct_text_blocks(a->n)), dim3(WP_TEXT_BLOCK), 0, stream, *a);
-  PrimScratch sc(tmp, tmp_bytes);
-  return winpct_scan(sc, a->len, a->off, (size_t)a->n + 1, stream);
+  return text_plan<WpRow, WP_TEXT_BLOCK>(a, tmp, tmp_bytes, stream);
 }
 
 void apm_winpct_write(WinPctTextArgs* a, hipStream_t stream) {
   if (a->n <= 0) return;
-  hipLaunchKernelGGL(k_winpct_write, dim3(winpct_text_blocks(a->n)), dim3(WP_TEXT_BLOCK), 0, stream, *a);
+  // (the length pass' grid: n + 1 positions)
+  hipLaunchKernelGGL(k_winpct_write, dim3(text_len_blocks(a->n, WP_TEXT_BLOCK)), dim3(WP_TEXT_BLOCK), 0, stream, *a);
 }
 
 }  // extern "C"

@@ -433,13 +433,7 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_wp_sum2_ = (long long*)res_.dmalloc((size_t)S * nq * 8);
     d_wp_m_ = (int32_t*)res_.dmalloc((size_t)S * 4);
     d_wp_nan_ = (int32_t*)res_.dmalloc((size_t)S * 4);
-    d_wp_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    d_wp_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    d_wp_off_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    wp_tmp_bytes_ = apm_winpct_tmp_bytes(S);
-    d_wp_tmp_ = res_.dmalloc(wp_tmp_bytes_);
-    res_.pin(h_wp_total_, 64);
-    for (int k = 0; k < 2; ++k) ev_wp_[k] = res_.new_event();
+    text_alloc(wp_, OUT_WP, apm_winpct_tmp_bytes(S));
   }
   if (want(OUT_SL)) {  // K17
     const int32_t C = (int32_t)cfg_.slo_classes.size();  // (checked at the top of the constructor)
@@ -457,13 +451,7 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_slo_cls_ = (int32_t*)res_.dmalloc((size_t)S * 4);
     HIP_OK(hipMemset(d_slo_cls_, 0, (size_t)S * 4));  // class 0 until a series' class is uploaded
     d_slo_rec_ = (SloRec*)res_.dmalloc((size_t)S * sizeof(SloRec));
-    d_slo_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    d_slo_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    d_slo_off_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    slo_tmp_bytes_ = apm_slo_tmp_bytes(S);
-    d_slo_tmp_ = res_.dmalloc(slo_tmp_bytes_);
-    res_.pin(h_slo_total_, 64);
-    for (int k = 0; k < 2; ++k) ev_slo_[k] = res_.new_event();
+    text_alloc(sl_, OUT_SL, apm_slo_tmp_bytes(S));
   }
   if (want(OUT_TK)) {  // K18
     tk_k_ = cfg_.tk_k;
@@ -481,23 +469,9 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_sv_pos_ = (int32_t*)res_.dmalloc((size_t)S * 4);
     d_sv_grp_ = (int32_t*)res_.dmalloc((size_t)S * 4);
     d_sv_rec_ = (SvcRec*)res_.dmalloc((size_t)S * sizeof(SvcRec));
-    d_sv_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    d_sv_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    d_sv_off_txt_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    sv_tmp_bytes_ = apm_svcwin_tmp_bytes(S);
-    d_sv_tmp_ = res_.dmalloc(sv_tmp_bytes_);
-    res_.pin(h_sv_total_, 64);
-    for (int k = 0; k < 2; ++k) ev_sv_[k] = res_.new_event();
+    text_alloc(sv_, OUT_SV, apm_svcwin_tmp_bytes(S));
   }
-  if (want(OUT_LH)) {  // K15
-    d_hist_len_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    d_hist_off_ = (uint32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    d_hist_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
-    hist_tmp_bytes_ = apm_hist_tmp_bytes(S);
-    d_hist_tmp_ = res_.dmalloc(hist_tmp_bytes_);
-    res_.pin(h_hist_total_, 64);
-    for (int k = 0; k < 2; ++k) ev_hist_[k] = res_.new_event();
-  }
+  if (want(OUT_LH)) text_alloc(lh_, OUT_LH, apm_hist_tmp_bytes(S));  // K15
   {
     const char* f = std::getenv("APM_TXCOPY_FORCE_FALLBACK");
     txcopy_force_fb_ = f && f[0] == '1';
@@ -3018,6 +2992,62 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   });
 }
 
+// ---- The text streams of a rollover (lh, wp, sl, sv): buffers and the slot protocol, once.
+void Engine::text_alloc(TextStream& t, int kind, size_t tmp_bytes) {
+  const size_t S = (size_t)cfg_.max_series;
+  t.kind = kind;
+  t.len = (uint32_t*)res_.dmalloc((S + 1) * 4);
+  t.off = (uint32_t*)res_.dmalloc((S + 1) * 4);
+  t.big = (int32_t*)res_.dmalloc((S + 1) * 4);
+  t.tmp_bytes = tmp_bytes;
+  t.tmp = res_.dmalloc(tmp_bytes);
+  res_.pin(t.total, 64);
+  for (int k = 0; k < 2; ++k) t.ev[k] = res_.new_event();
+}
+
+char* Engine::text_begin(TextStream& t, size_t bound) {
+  const int k = t.k ^= 1;
+  out_wait(t.task[k]);  // slot k's previous D2H + emission is done
+  if (bound > t.out_cap[k]) t.out[k] = (char*)res_.regrow(t.out[k], t.out_cap[k], bound, stream_);
+  return t.out[k];
+}
+
+void Engine::text_end(TextStream& t, int32_t n) {
+  const int k = t.k;
+  {
+    ExportArgs ex{};
+    ex.add(t.off + n, t.total.d + k, 4);
+    apm_export(&ex, stream_);
+  }
+  HIP_OK(hipEventRecord(t.ev[k], stream_));
+  const char* dst = t.out[k];
+  TextStream* ts = &t;
+  t.task[k] = post_out([this, ts, k, dst]() {
+    HIP_OK(hipEventSynchronize(ts->ev[k]));
+    const size_t total = ts->total[k];
+    if (!total) return;
+    res_.reserve(ts->text[k], total, total * 2 + (1 << 20));
+    lane_d2h(ts->text[k], dst, total);
+    lane_sync();
+    emit_bytes(ts->kind, ts->text[k], total);
+  });
+}
+
+// "<p>:" for q = p * 1000, the canonical text of q / 1000: trailing zeros and a trailing point
+// dropped (the wp and sv rows' percentile labels).  Returns its length.
+static int32_t pct_label(char (&txt)[8], int q) {
+  char fr[8];
+  int len = std::snprintf(txt, sizeof txt, "%d", q / 1000);
+  if (q % 1000) {
+    int k = std::snprintf(fr, sizeof fr, "%03d", q % 1000);
+    while (fr[k - 1] == '0') --k;
+    txt[len++] = '.';
+    for (int i = 0; i < k; ++i) txt[len++] = fr[i];
+  }
+  txt[len++] = ':';
+  return len;
+}
+
 // ---- K15: lh rows.  A rollover from `prev` to L reports every bucket that K8 reads now and did
 // not read at the previous rollover: max(prev - buffer, L - keep - 1) < b <= L - buffer, ascending
 // (one bucket unless `latest` jumped).  A bucket without a ring slot holds no sample: no launch.
@@ -3042,35 +3072,15 @@ void Engine::hist_bucket(int64_t b, int slot) {
   ha.n = n;
   ha.slot = slot;
   ha.ts_len = std::snprintf(ha.ts, sizeof ha.ts, "%lld|", (long long)(b * 10000));
-  ha.len = d_hist_len_;
-  ha.off = d_hist_off_;
-  ha.big_list = d_hist_big_;
-  ha.big_n = d_hist_big_ + cfg_.max_series;
-  const int k = hist_k_;
-  hist_k_ ^= 1;
-  out_wait(hist_task_[k]);  // slot k's previous D2H + emission is done
+  ha.len = lh_.len;
+  ha.off = lh_.off;
+  ha.big_list = lh_.big;
+  ha.big_n = lh_.big + cfg_.max_series;
   // the output bound needs no length pass: every row is at most apm_hist_row_bound bytes
-  const size_t cap = (size_t)n * apm_hist_row_bound(max_name_len_) + 64;
-  if (cap > hist_out_cap_[k]) d_hist_out_[k] = (char*)res_.regrow(d_hist_out_[k], hist_out_cap_[k], cap, stream_);
-  ha.out = d_hist_out_[k];
-  if (apm_hist_plan(&ha, d_hist_tmp_, hist_tmp_bytes_, stream_) != 0) throw std::runtime_error("histogram scan failed");
+  ha.out = text_begin(lh_, (size_t)n * apm_hist_row_bound(max_name_len_) + 64);
+  if (apm_hist_plan(&ha, lh_.tmp, lh_.tmp_bytes, stream_) != 0) throw std::runtime_error("histogram scan failed");
   apm_hist_write(&ha, stream_);
-  {
-    ExportArgs ex{};
-    ex.add(ha.off + n, h_hist_total_.d + k, 4);
-    apm_export(&ex, stream_);
-  }
-  HIP_OK(hipEventRecord(ev_hist_[k], stream_));
-  const char* dst = d_hist_out_[k];
-  hist_task_[k] = post_out([this, k, dst]() {
-    HIP_OK(hipEventSynchronize(ev_hist_[k]));
-    const size_t total = h_hist_total_[k];
-    if (!total) return;
-    res_.reserve(h_hist_text_[k], total, total * 2 + (1 << 20));
-    lane_d2h(h_hist_text_[k], dst, total);
-    lane_sync();
-    emit_bytes(OUT_LH, h_hist_text_[k], total);
-  });
+  text_end(lh_, n);
 }
 
 // ---- K16: wp rows.  One row per st row whose window holds a non-NaN sample, in st order, with
@@ -3087,8 +3097,8 @@ void Engine::winpct_rollover(const WindowArgs& wa, int64_t edge_ts) {
   pa.sum2 = d_wp_sum2_;
   pa.m = d_wp_m_;
   pa.nan = d_wp_nan_;
-  pa.big_list = d_wp_big_;
-  pa.big_n = d_wp_big_ + cfg_.max_series;
+  pa.big_list = wp_.big;
+  pa.big_n = wp_.big + cfg_.max_series;
   apm_winpct_values(&pa, stream_);
   WinPctTextArgs ta{};
   ta.sum2 = d_wp_sum2_;
@@ -3101,47 +3111,14 @@ void Engine::winpct_rollover(const WindowArgs& wa, int64_t edge_ts) {
   ta.n_series = n;
   ta.nq = nq;
   ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
-  for (int j = 0; j < nq; ++j) {
-    // the canonical text of q / 1000: trailing zeros and a trailing point dropped
-    const int q = cfg_.win_pcts[j];
-    char fr[8];
-    int len = std::snprintf(ta.ptxt[j], sizeof ta.ptxt[j], "%d", q / 1000);
-    if (q % 1000) {
-      int k = std::snprintf(fr, sizeof fr, "%03d", q % 1000);
-      while (fr[k - 1] == '0') --k;
-      ta.ptxt[j][len++] = '.';
-      for (int i = 0; i < k; ++i) ta.ptxt[j][len++] = fr[i];
-    }
-    ta.ptxt[j][len++] = ':';
-    ta.plen[j] = len;
-  }
-  ta.len = d_wp_len_;
-  ta.off = d_wp_off_;
-  const int k = wp_k_;
-  wp_k_ ^= 1;
-  out_wait(wp_task_[k]);  // slot k's previous D2H + emission is done
+  for (int j = 0; j < nq; ++j) ta.plen[j] = pct_label(ta.ptxt[j], cfg_.win_pcts[j]);
+  ta.len = wp_.len;
+  ta.off = wp_.off;
   // the output bound needs no length pass: every row is at most apm_winpct_row_bound bytes
-  const size_t cap = (size_t)n * apm_winpct_row_bound(max_name_len_, nq) + 64;
-  if (cap > wp_out_cap_[k]) d_wp_out_[k] = (char*)res_.regrow(d_wp_out_[k], wp_out_cap_[k], cap, stream_);
-  ta.out = d_wp_out_[k];
-  if (apm_winpct_plan(&ta, d_wp_tmp_, wp_tmp_bytes_, stream_) != 0) throw std::runtime_error("percentile scan failed");
+  ta.out = text_begin(wp_, (size_t)n * apm_winpct_row_bound(max_name_len_, nq) + 64);
+  if (apm_winpct_plan(&ta, wp_.tmp, wp_.tmp_bytes, stream_) != 0) throw std::runtime_error("percentile scan failed");
   apm_winpct_write(&ta, stream_);
-  {
-    ExportArgs ex{};
-    ex.add(ta.off + n, h_wp_total_.d + k, 4);
-    apm_export(&ex, stream_);
-  }
-  HIP_OK(hipEventRecord(ev_wp_[k], stream_));
-  const char* dst = d_wp_out_[k];
-  wp_task_[k] = post_out([this, k, dst]() {
-    HIP_OK(hipEventSynchronize(ev_wp_[k]));
-    const size_t total = h_wp_total_[k];
-    if (!total) return;
-    res_.reserve(h_wp_text_[k], total, total * 2 + (1 << 20));
-    lane_d2h(h_wp_text_[k], dst, total);
-    lane_sync();
-    emit_bytes(OUT_WP, h_wp_text_[k], total);
-  });
+  text_end(wp_, n);
 }
 
 void Engine::download_winpcts(std::vector<int32_t>& m, std::vector<int32_t>& nan, std::vector<long long>& sum2) {
@@ -3174,8 +3151,8 @@ void Engine::slo_rollover(const WindowArgs& wa, int64_t edge_ts) {
   va.thr = thr;
   va.n_classes = n_slo_classes_;
   va.rec = d_slo_rec_;
-  va.big_list = d_slo_big_;
-  va.big_n = d_slo_big_ + cfg_.max_series;
+  va.big_list = sl_.big;
+  va.big_n = sl_.big + cfg_.max_series;
   apm_slo_values(&va, stream_);
   SloTextArgs ta{};
   ta.rec = d_slo_rec_;
@@ -3189,33 +3166,13 @@ void Engine::slo_rollover(const WindowArgs& wa, int64_t edge_ts) {
   ta.n = n;
   ta.n_series = n;
   ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
-  ta.len = d_slo_len_;
-  ta.off = d_slo_off_;
-  const int k = slo_k_;
-  slo_k_ ^= 1;
-  out_wait(slo_task_[k]);  // slot k's previous D2H + emission is done
+  ta.len = sl_.len;
+  ta.off = sl_.off;
   // the output bound needs no length pass: every row is at most apm_slo_row_bound bytes
-  const size_t cap = (size_t)n * apm_slo_row_bound(max_name_len_) + 64;
-  if (cap > slo_out_cap_[k]) d_slo_out_[k] = (char*)res_.regrow(d_slo_out_[k], slo_out_cap_[k], cap, stream_);
-  ta.out = d_slo_out_[k];
-  if (apm_slo_plan(&ta, d_slo_tmp_, slo_tmp_bytes_, stream_) != 0) throw std::runtime_error("objective scan failed");
+  ta.out = text_begin(sl_, (size_t)n * apm_slo_row_bound(max_name_len_) + 64);
+  if (apm_slo_plan(&ta, sl_.tmp, sl_.tmp_bytes, stream_) != 0) throw std::runtime_error("objective scan failed");
   apm_slo_write(&ta, stream_);
-  {
-    ExportArgs ex{};
-    ex.add(ta.off + n, h_slo_total_.d + k, 4);
-    apm_export(&ex, stream_);
-  }
-  HIP_OK(hipEventRecord(ev_slo_[k], stream_));
-  const char* dst = d_slo_out_[k];
-  slo_task_[k] = post_out([this, k, dst]() {
-    HIP_OK(hipEventSynchronize(ev_slo_[k]));
-    const size_t total = h_slo_total_[k];
-    if (!total) return;
-    res_.reserve(h_slo_text_[k], total, total * 2 + (1 << 20));
-    lane_d2h(h_slo_text_[k], dst, total);
-    lane_sync();
-    emit_bytes(OUT_SL, h_slo_text_[k], total);
-  });
+  text_end(sl_, n);
 }
 
 void Engine::download_slo(std::vector<SloRec>& rec, std::vector<int32_t>& nthr) {
@@ -3365,8 +3322,8 @@ void Engine::svcwin_rollover(const WindowArgs& wa, int64_t edge_ts) {
   va.grp_mem = d_sv_mem_;
   va.grp_pos = d_sv_pos_;
   va.rec = d_sv_rec_;
-  va.big_list = d_sv_big_;
-  va.big_n = d_sv_big_ + cfg_.max_series;
+  va.big_list = sv_.big;
+  va.big_n = sv_.big + cfg_.max_series;
   apm_svcwin_values(&va, stream_);
   SvcWinTextArgs ta{};
   ta.rec = d_sv_rec_;
@@ -3379,47 +3336,14 @@ void Engine::svcwin_rollover(const WindowArgs& wa, int64_t edge_ts) {
   ta.n_groups = sv_groups_;
   ta.nq = nq;
   ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
-  for (int j = 0; j < nq; ++j) {
-    // the canonical text of q / 1000: trailing zeros and a trailing point dropped (as K16 prints it)
-    const int q = cfg_.svc_pcts[j];
-    char fr[8];
-    int len = std::snprintf(ta.ptxt[j], sizeof ta.ptxt[j], "%d", q / 1000);
-    if (q % 1000) {
-      int k = std::snprintf(fr, sizeof fr, "%03d", q % 1000);
-      while (fr[k - 1] == '0') --k;
-      ta.ptxt[j][len++] = '.';
-      for (int i = 0; i < k; ++i) ta.ptxt[j][len++] = fr[i];
-    }
-    ta.ptxt[j][len++] = ':';
-    ta.plen[j] = len;
-  }
-  ta.len = d_sv_len_;
-  ta.off = d_sv_off_txt_;
-  const int k = sv_k_;
-  sv_k_ ^= 1;
-  out_wait(sv_task_[k]);  // slot k's previous D2H + emission is done
+  for (int j = 0; j < nq; ++j) ta.plen[j] = pct_label(ta.ptxt[j], cfg_.svc_pcts[j]);  // (as K16 prints them)
+  ta.len = sv_.len;
+  ta.off = sv_.off;
   // the output bound needs no length pass: every row is at most apm_svcwin_row_bound bytes
-  const size_t cap = (size_t)sv_groups_ * apm_svcwin_row_bound(max_name_len_, nq) + 64;
-  if (cap > sv_out_cap_[k]) d_sv_out_[k] = (char*)res_.regrow(d_sv_out_[k], sv_out_cap_[k], cap, stream_);
-  ta.out = d_sv_out_[k];
-  if (apm_svcwin_plan(&ta, d_sv_tmp_, sv_tmp_bytes_, stream_) != 0) throw std::runtime_error("service window scan failed");
+  ta.out = text_begin(sv_, (size_t)sv_groups_ * apm_svcwin_row_bound(max_name_len_, nq) + 64);
+  if (apm_svcwin_plan(&ta, sv_.tmp, sv_.tmp_bytes, stream_) != 0) throw std::runtime_error("service window scan failed");
   apm_svcwin_write(&ta, stream_);
-  {
-    ExportArgs ex{};
-    ex.add(ta.off + n, h_sv_total_.d + k, 4);
-    apm_export(&ex, stream_);
-  }
-  HIP_OK(hipEventRecord(ev_sv_[k], stream_));
-  const char* dst = d_sv_out_[k];
-  sv_task_[k] = post_out([this, k, dst]() {
-    HIP_OK(hipEventSynchronize(ev_sv_[k]));
-    const size_t total = h_sv_total_[k];
-    if (!total) return;
-    res_.reserve(h_sv_text_[k], total, total * 2 + (1 << 20));
-    lane_d2h(h_sv_text_[k], dst, total);
-    lane_sync();
-    emit_bytes(OUT_SV, h_sv_text_[k], total);
-  });
+  text_end(sv_, n);  // (one position per series: a service's row stands at its first member's)
 }
 
 void Engine::download_svcwins(std::vector<std::string>& names, std::vector<SvcRec>& rec) {

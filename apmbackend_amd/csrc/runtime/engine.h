@@ -1202,38 +1202,44 @@ class Engine {
   PinnedBuf<uint32_t> h_fs_off_[2];
   size_t fs_rows_[2] = {0, 0};
 
+  // A rollover stream whose rows are printed on the device (lh, wp, sl, sv): the buffers of its
+  // count / scan / write text pass and two device / pinned text slots, as for st / fs.  A rollover
+  // takes the other slot than the one before it; a slot is reused only after its output-lane task
+  // is done, and the lane reads a slot's total only after the slot's event.  Allocated when the
+  // stream is on (text_alloc); text_begin / text_end carry the slot protocol.
+  struct TextStream {
+    int kind = 0;                             // the stream's OUT_* kind
+    uint32_t *len = nullptr, *off = nullptr;  // [S + 1]
+    int32_t* big = nullptr;                   // [S] block-pass list of the value pass, [S] its length
+    void* tmp = nullptr;                      // the scan's scratch
+    size_t tmp_bytes = 0;
+    char* out[2] = {nullptr, nullptr};
+    size_t out_cap[2] = {0, 0};
+    PinnedBuf<char> text[2];                  // pinned (output lane)
+    Mapped<uint32_t> total;                   // pinned [2]: bytes of slot k's rows
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint64_t task[2] = {0, 0};
+    int k = 1;                                // the slot the last rollover took
+  };
+  void text_alloc(TextStream& t, int kind, size_t tmp_bytes);
+  // the next slot, free of its previous task, and its device output of at least `bound` bytes
+  char* text_begin(TextStream& t, size_t bound);
+  // after the plan and write launches over n positions: t.off[n] -> the slot's pinned total, the
+  // slot's event, and the output-lane task that copies and emits the rows
+  void text_end(TextStream& t, int32_t n);
+
   // K15 lh rows (hist.hip), allocated when the stream is on: every bucket is reported once, at the
-  // rollover that first has it in the K8 window.  Two device / pinned slots, as for st / fs.
-  uint32_t *d_hist_len_ = nullptr, *d_hist_off_ = nullptr;  // [S + 1]
-  int32_t* d_hist_big_ = nullptr;                            // [S] block-pass list, [S] its length
-  void* d_hist_tmp_ = nullptr;
-  size_t hist_tmp_bytes_ = 0;
-  char* d_hist_out_[2] = {nullptr, nullptr};
-  size_t hist_out_cap_[2] = {0, 0};
-  PinnedBuf<char> h_hist_text_[2];  // pinned (output lane)
-  Mapped<uint32_t> h_hist_total_;   // pinned [2]: bytes of slot k's rows
-  hipEvent_t ev_hist_[2] = {nullptr, nullptr};
-  uint64_t hist_task_[2] = {0, 0};
-  int hist_k_ = 0;
+  // rollover that first has it in the K8 window.
+  TextStream lh_;
   void hist_rollover(int64_t L, int64_t prev);
   void hist_bucket(int64_t b, int slot);
 
   // K16 wp rows (winpct.hip), allocated when the stream is on: exact percentiles of the window K8
   // read, queued behind the rollover's alert chain and st / fs formatting.  No device state
-  // outlives a rollover; two device / pinned text slots, as for st / fs.
+  // outlives a rollover; the text pass and its slots are wp_'s.
   long long* d_wp_sum2_ = nullptr;                          // [S][nq]
   int32_t *d_wp_m_ = nullptr, *d_wp_nan_ = nullptr;         // [S]
-  int32_t* d_wp_big_ = nullptr;                             // [S] block-pass list, [S] its length
-  uint32_t *d_wp_len_ = nullptr, *d_wp_off_ = nullptr;      // [S + 1]
-  void* d_wp_tmp_ = nullptr;
-  size_t wp_tmp_bytes_ = 0;
-  char* d_wp_out_[2] = {nullptr, nullptr};
-  size_t wp_out_cap_[2] = {0, 0};
-  PinnedBuf<char> h_wp_text_[2];  // pinned (output lane)
-  Mapped<uint32_t> h_wp_total_;   // pinned [2]: bytes of slot k's rows
-  hipEvent_t ev_wp_[2] = {nullptr, nullptr};
-  uint64_t wp_task_[2] = {0, 0};
-  int wp_k_ = 0;
+  TextStream wp_;
   void winpct_rollover(const WindowArgs& wa, int64_t edge_ts);
  public:
   // (tests) the value pass' result of the last rollover: per series m, nan and nq sums
@@ -1249,17 +1255,7 @@ class Engine {
   int32_t* d_slo_cls_ = nullptr;                            // [S]
   std::vector<int32_t> h_slo_cls_;                          // its host mirror (stats thread)
   SloRec* d_slo_rec_ = nullptr;                             // [S]
-  int32_t* d_slo_big_ = nullptr;                            // [S] block-pass list, [S] its length
-  uint32_t *d_slo_len_ = nullptr, *d_slo_off_ = nullptr;    // [S + 1]
-  void* d_slo_tmp_ = nullptr;
-  size_t slo_tmp_bytes_ = 0;
-  char* d_slo_out_[2] = {nullptr, nullptr};
-  size_t slo_out_cap_[2] = {0, 0};
-  PinnedBuf<char> h_slo_text_[2];  // pinned (output lane)
-  Mapped<uint32_t> h_slo_total_;   // pinned [2]: bytes of slot k's rows
-  hipEvent_t ev_slo_[2] = {nullptr, nullptr};
-  uint64_t slo_task_[2] = {0, 0};
-  int slo_k_ = 0;
+  TextStream sl_;                                           // the text pass and its slots
   int32_t slo_cls_uploaded_ = 0;                            // series whose class is on the device
   int32_t slo_class_of(int32_t s) const;
   void upload_slo_classes(int32_t lo);
@@ -1296,23 +1292,13 @@ class Engine {
   // thread keeps a CSR of service -> member series (grouped by the local dictionary service id,
   // rows in the order of each service's first member in emission order, members in emission order)
   // and rebuilds and uploads it, through the stager, at the first rollover after series were added.
-  // No device state outlives a rollover; two device / pinned text slots, as for st / fs.
+  // No device state outlives a rollover; the text pass and its slots are sv_'s.
   std::vector<int32_t> h_sv_off_, h_sv_mem_, h_sv_pos_, h_sv_grp_;  // [groups + 1], [n], [n], [n] (stats thread)
   int32_t sv_groups_ = 0;
   int32_t sv_built_n_ = -1;                                 // n_series_ the CSR was built for
   int32_t *d_sv_off_ = nullptr, *d_sv_mem_ = nullptr, *d_sv_pos_ = nullptr, *d_sv_grp_ = nullptr;  // [S + 1], [S], [S], [S]
   SvcRec* d_sv_rec_ = nullptr;                              // [S]
-  int32_t* d_sv_big_ = nullptr;                             // [S] block-pass list, [S] its length
-  uint32_t *d_sv_len_ = nullptr, *d_sv_off_txt_ = nullptr;  // [S + 1]
-  void* d_sv_tmp_ = nullptr;
-  size_t sv_tmp_bytes_ = 0;
-  char* d_sv_out_[2] = {nullptr, nullptr};
-  size_t sv_out_cap_[2] = {0, 0};
-  PinnedBuf<char> h_sv_text_[2];  // pinned (output lane)
-  Mapped<uint32_t> h_sv_total_;   // pinned [2]: bytes of slot k's rows
-  hipEvent_t ev_sv_[2] = {nullptr, nullptr};
-  uint64_t sv_task_[2] = {0, 0};
-  int sv_k_ = 0;
+  TextStream sv_;
   void sync_service_groups();
   void svcwin_rollover(const WindowArgs& wa, int64_t edge_ts);
  public:
