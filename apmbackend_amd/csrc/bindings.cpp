@@ -148,6 +148,26 @@ EngineConfig config_from(const py::dict& d) {
       c.svc_pcts[i] = (int32_t)v[i];
     }
   }
+  if (d.contains("rw_buckets")) {  // K20 (the constructor checks the bound against the window)
+    auto v = d["rw_buckets"].cast<std::vector<int64_t>>();
+    if (v.size() > 4) throw std::invalid_argument("rw_buckets: at most 4 spans");
+    c.n_rw_buckets = (int32_t)v.size();
+    for (size_t i = 0; i < v.size(); ++i) {
+      if (v[i] < 1 || v[i] > 0x7fffffff || (i && v[i] <= v[i - 1]))
+        throw std::invalid_argument("rw_buckets: strictly ascending integers >= 1");
+      c.rw_buckets[i] = (int32_t)v[i];
+    }
+  }
+  if (d.contains("rw_pcts")) {
+    auto v = d["rw_pcts"].cast<std::vector<int64_t>>();
+    if (v.size() > 8) throw std::invalid_argument("rw_pcts: at most 8 percentiles");
+    c.n_rw_pcts = (int32_t)v.size();
+    for (size_t i = 0; i < v.size(); ++i) {
+      if (v[i] < 1 || v[i] > 100000 || (i && v[i] <= v[i - 1]))
+        throw std::invalid_argument("rw_pcts: strictly ascending integers in 1 .. 100000 (percentile * 1000)");
+      c.rw_pcts[i] = (int32_t)v[i];
+    }
+  }
   if (d.contains("tk_k") && !d["tk_k"].is_none()) {  // (the constructor checks them when the tk stream is on)
     c.tk_k = d["tk_k"].cast<int32_t>();
     if (d.contains("tk_by")) c.tk_by = d["tk_by"].cast<std::vector<int32_t>>();
@@ -626,6 +646,27 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("recents", [](Engine& e) {
+        // per series id of the last rollover's K20 value pass: None for a series without rows, else a
+        // list over the configured spans of (m, nan, sum, [sum2 per configured percentile])
+        std::vector<RecentRec> rec;
+        std::vector<uint8_t> has;
+        e.download_recents(rec, has);
+        const int ns = e.rw_nspan(), nq = e.rw_nq();
+        py::list out;
+        for (size_t s = 0; s < has.size(); ++s) {
+          if (!has[s]) { out.append(py::none()); continue; }
+          py::list spans;
+          for (int k = 0; k < ns; ++k) {
+            const RecentRec& r = rec[s * (size_t)ns + (size_t)k];
+            py::list v;
+            for (int j = 0; j < nq && r.m > 0; ++j) v.append(py::int_(r.sum2[j]));
+            spans.append(py::make_tuple(r.m, r.nan, py::int_(r.sum), v));
+          }
+          out.append(spans);
+        }
+        return out;
+      })
       .def("leaderboard", [](Engine& e) {
         // the last rollover's K18 records: (board, rank, series id, tpm, avg, p75, p95), raw doubles
         std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> rows;
@@ -684,15 +725,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[10];
-    int64_t counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::string out[11];
+    int64_t counts[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[10] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv"};
-    for (int k = 0; k < 10; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[11] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw"};
+    for (int k = 0; k < 11; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -887,6 +928,10 @@ PYBIND11_MODULE(_apm_native, m) {
   // keeps a service in its 32-lane group (tests bracket them)
   m.def("svcwin_group_max", []() { return apm_svcwin_group_max(); });
   m.def("svcwin_group_win", []() { return apm_svcwin_group_win(); });
+  // rw recent windows (recent.hip): the largest span's sample count and the window length up to
+  // which the value pass keeps a series in its 32-lane group (tests bracket them)
+  m.def("recent_group_max", []() { return apm_recent_group_max(); });
+  m.def("recent_group_win", []() { return apm_recent_group_win(); });
   m.def("apm_topk_tile", []() { return apm_topk_tile(); });
   m.def("apm_topk_final_span", []() { return apm_topk_final_span(); });
   m.def("topk_select", [](const std::vector<std::tuple<double, double, double, double, int32_t>>& win_rows,

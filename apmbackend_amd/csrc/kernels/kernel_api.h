@@ -38,7 +38,7 @@ struct WindowArgs {
   StatsState st;
   int32_t win_slots[K8_INLINE_SLOTS];  // slot index per window bucket (-1 = bucket absent), n_win <= 64
   const int32_t* win_slots_ext;        // device [n_win] when n_win > K8_INLINE_SLOTS (else null)
-  int32_t n_win;          // windowSizeInIntervals (31 in the shipped config)
+  int32_t n_win;          // window buckets: windowSizeInIntervals + 1 (31 in the shipped config)
   double tpm_div;         // windowSz * intervalLen / 60
   WinStat* out;           // [S]
   int32_t* big_list;      // series deferred to the block pass
@@ -325,6 +325,46 @@ struct SvcWinTextArgs {
   uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
   char* out;                    // at least apm_svcwin_row_bound(max name bytes, nq) * n_groups bytes
 };
+// K20 rw rows: exact stats of the newest window buckets (recent.hip, docs/RECENT.md).  A span of k
+// buckets is the window entries r >= n_win - min(k, n_win) of the window K8 just read (the same
+// WindowArgs).  The value pass writes one record per (series, span) for every series with
+// WinStat.active and WinStat.n >= 1, and none for any other; the text pass prints, per emission
+// position of such a series and per span, ascending:
+//   rw|<edge ts>|server|service|<k>|<m>|<nan>|<sum>|<p>:<v>,<p>:<v>,...
+constexpr int RW_MAX_SPAN = 4;
+struct RecentRec {
+  int32_t m, nan;               // samples of the span that are not / are ELAPSED_NAN
+  long long sum;                // of the m finite samples
+  long long sum2[WP_MAX_Q];     // per percentile: sum of the one or two ranks read (m >= 1 only)
+};
+struct RecentArgs {
+  WindowArgs w;                 // K8's arguments of this rollover (spill lists sorted; w.out = K8's result)
+  int32_t nspan;                // 1 .. RW_MAX_SPAN
+  int32_t span[RW_MAX_SPAN];    // buckets per span, strictly ascending, >= 1
+  int32_t nq;                   // 1 .. WP_MAX_Q
+  int32_t q[WP_MAX_Q];          // percentile * 1000, strictly ascending, 1 .. 100000
+  RecentRec* rec;               // [S][nspan]
+  int32_t* big_list;            // [S] series deferred to the block pass
+  int32_t* big_n;
+};
+struct RecentTextArgs {
+  const RecentRec* rec;         // [S][nspan]
+  const WinStat* win;           // [S] K8's result: which series have records
+  const int32_t* perm;          // [n / nspan] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;                    // lanes: emission positions * nspan
+  int32_t n_series;
+  int32_t nspan;
+  int32_t span[RW_MAX_SPAN];
+  int32_t nq;
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  char ptxt[WP_MAX_Q][8];       // "<p>:" per percentile (at most "99.999:")
+  int32_t plen[WP_MAX_Q];
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_recent_row_bound(max name bytes, nq) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -476,6 +516,19 @@ void apm_svcwin_values(apm::SvcWinArgs* a, hipStream_t stream);
 // length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_svcwin_plan(apm::SvcWinTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_svcwin_write(apm::SvcWinTextArgs* a, hipStream_t stream);
+// recent.hip
+// the value pass' two paths (tests bracket them): a series stays in its 32-lane group while the
+// window has at most apm_recent_group_win() buckets and its largest span holds at most
+// apm_recent_group_max() samples; every other series with a row is selected by a whole block
+int32_t apm_recent_group_max();
+int32_t apm_recent_group_win();
+size_t apm_recent_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes and nq percentiles
+size_t apm_recent_row_bound(size_t name_bytes, int32_t nq);
+void apm_recent_values(apm::RecentArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_recent_plan(apm::RecentTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_recent_write(apm::RecentTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

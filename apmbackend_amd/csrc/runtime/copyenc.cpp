@@ -267,8 +267,8 @@ void append_pct_pairs(std::string& js, std::string_view rest) {
   }
 }
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[10]*/) {
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[11]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -460,6 +460,35 @@ int encode_line(std::string_view line, std::string* out /*[10]*/) {
     copy_escape(o, js);
     o += '\n';
     return 9;
+  }
+  if (t == "rw") {  // recent window: timestamp, server, service, buckets, count, nan, elapsed_sum, pcts json
+    // (utils/records.py entry_from_csv holds the same rules, those of sv) a row whose buckets, count
+    // or nan is not 1 to 10 plain digits, or whose sum is not 1 to 18 digits after an optional '-',
+    // is dropped
+    for (int i = 4; i <= 6; ++i)
+      if (!a.has(i) || !all_digits(a.f[i], 10)) return -1;
+    if (!a.has(7)) return -1;
+    const bool sneg = !a.f[7].empty() && a.f[7][0] == '-';
+    const std::string_view sdig = sneg ? a.f[7].substr(1) : a.f[7];
+    if (!all_digits(sdig, 18)) return -1;
+    std::string& o = out[10];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    for (int i = 4; i <= 6; ++i) {
+      int64_t v = 0;
+      for (char ch : a.f[i]) v = v * 10 + (ch - '0');
+      append_i64(o, v); o += '\t';
+    }
+    int64_t sv = 0;
+    for (char ch : sdig) sv = sv * 10 + (ch - '0');
+    append_i64(o, sneg ? -sv : sv); o += '\t';
+    std::string js = "{";
+    append_pct_pairs(js, a.has(8) ? a.f[8] : std::string_view());
+    js += '}';
+    copy_escape(o, js);
+    o += '\n';
+    return 10;
   }
   if (t == "jx") {
     std::string& o = out[3];

@@ -254,6 +254,17 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       ok = cfg_.svc_pcts[j] >= 1 && cfg_.svc_pcts[j] <= 100000 && (j == 0 || cfg_.svc_pcts[j] > cfg_.svc_pcts[j - 1]);
     if (!ok) throw std::invalid_argument("sv stream: svc_pcts must hold 1 to 8 strictly ascending percentiles");
   }
+  if (want(OUT_RW)) {  // K20: the stream needs both lists (likewise before anything is allocated)
+    const int ns = cfg_.n_rw_buckets, nq = cfg_.n_rw_pcts;
+    bool ok = ns >= 1 && ns <= RW_MAX_SPAN && nq >= 1 && nq <= WP_MAX_Q;
+    for (int j = 0; ok && j < ns; ++j)
+      ok = cfg_.rw_buckets[j] >= 1 && cfg_.rw_buckets[j] <= cfg_.window && (j == 0 || cfg_.rw_buckets[j] > cfg_.rw_buckets[j - 1]);
+    for (int j = 0; ok && j < nq; ++j)
+      ok = cfg_.rw_pcts[j] >= 1 && cfg_.rw_pcts[j] <= 100000 && (j == 0 || cfg_.rw_pcts[j] > cfg_.rw_pcts[j - 1]);
+    if (!ok)
+      throw std::invalid_argument("rw stream: rw_buckets must hold 1 to 4 strictly ascending spans in 1 .. window and "
+                                  "rw_pcts 1 to 8 strictly ascending percentiles");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -470,6 +481,11 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_sv_grp_ = (int32_t*)res_.dmalloc((size_t)S * 4);
     d_sv_rec_ = (SvcRec*)res_.dmalloc((size_t)S * sizeof(SvcRec));
     text_alloc(sv_, OUT_SV, apm_svcwin_tmp_bytes(S));
+  }
+  if (want(OUT_RW)) {  // K20: nspan records and text lanes per series
+    const int ns = cfg_.n_rw_buckets;
+    d_rw_rec_ = (RecentRec*)res_.dmalloc((size_t)S * ns * sizeof(RecentRec));
+    text_alloc(rw_, OUT_RW, apm_recent_tmp_bytes(S * ns), ns);
   }
   if (want(OUT_LH)) text_alloc(lh_, OUT_LH, apm_hist_tmp_bytes(S));  // K15
   {
@@ -2415,6 +2431,10 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   // K8 writes any of them; its own tables (the service CSR) are uploaded on this stream ahead of
   // its launches, and the next append follows on this stream.
   if (want(OUT_SV)) svcwin_rollover(wa, edge_ts);
+  // K20: last, for K16's reason again (docs/PERCENTILES.md "Where it is queued"): it reads only
+  // what K16 reads -- window cells, counts, the sorted spill lists, d_win_ -- nothing queued since
+  // K8 writes any of them, and the next append follows on this stream.
+  if (want(OUT_RW)) recent_rollover(wa, edge_ts);
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2569,8 +2589,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[10];
-        int64_t counts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::string enc[11];
+        int64_t counts[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -2992,12 +3012,13 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   });
 }
 
-// ---- The text streams of a rollover (lh, wp, sl, sv): buffers and the slot protocol, once.
-void Engine::text_alloc(TextStream& t, int kind, size_t tmp_bytes) {
+// ---- The text streams of a rollover (lh, wp, sl, sv, rw): buffers and the slot protocol, once.
+// `rows`: text lanes per series (rw prints one row per span).
+void Engine::text_alloc(TextStream& t, int kind, size_t tmp_bytes, int rows) {
   const size_t S = (size_t)cfg_.max_series;
   t.kind = kind;
-  t.len = (uint32_t*)res_.dmalloc((S + 1) * 4);
-  t.off = (uint32_t*)res_.dmalloc((S + 1) * 4);
+  t.len = (uint32_t*)res_.dmalloc((S * (size_t)rows + 1) * 4);
+  t.off = (uint32_t*)res_.dmalloc((S * (size_t)rows + 1) * 4);
   t.big = (int32_t*)res_.dmalloc((S + 1) * 4);
   t.tmp_bytes = tmp_bytes;
   t.tmp = res_.dmalloc(tmp_bytes);
@@ -3356,6 +3377,61 @@ void Engine::download_svcwins(std::vector<std::string>& names, std::vector<SvcRe
     names.push_back(dict_.service_name(series_[(size_t)h_sv_mem_[(size_t)h_sv_off_[(size_t)g]]].service));
 }
 
+// ---- K20: rw rows.  Per st row whose window holds a sample, one row per configured span of the
+// newest window buckets, in st order with the st rows' timestamp: value pass over the newest
+// entries of K8's window, then count / scan / write of the text, nspan lanes per position.
+void Engine::recent_rollover(const WindowArgs& wa, int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();
+  const int ns = cfg_.n_rw_buckets, nq = cfg_.n_rw_pcts;
+  RecentArgs va{};
+  va.w = wa;
+  va.nspan = ns;
+  for (int j = 0; j < ns; ++j) va.span[j] = cfg_.rw_buckets[j];
+  va.nq = nq;
+  for (int j = 0; j < nq; ++j) va.q[j] = cfg_.rw_pcts[j];
+  va.rec = d_rw_rec_;
+  va.big_list = rw_.big;
+  va.big_n = rw_.big + cfg_.max_series;
+  apm_recent_values(&va, stream_);
+  rw_last_n_ = n;
+  RecentTextArgs ta{};
+  ta.rec = d_rw_rec_;
+  ta.win = wa.out;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n * ns;
+  ta.n_series = n;
+  ta.nspan = ns;
+  for (int j = 0; j < ns; ++j) ta.span[j] = cfg_.rw_buckets[j];
+  ta.nq = nq;
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  for (int j = 0; j < nq; ++j) ta.plen[j] = pct_label(ta.ptxt[j], cfg_.rw_pcts[j]);  // (as K16 prints them)
+  ta.len = rw_.len;
+  ta.off = rw_.off;
+  // the output bound needs no length pass: every row is at most apm_recent_row_bound bytes
+  ta.out = text_begin(rw_, (size_t)n * ns * apm_recent_row_bound(max_name_len_, nq) + 64);
+  if (apm_recent_plan(&ta, rw_.tmp, rw_.tmp_bytes, stream_) != 0) throw std::runtime_error("recent window scan failed");
+  apm_recent_write(&ta, stream_);
+  text_end(rw_, ta.n);
+}
+
+void Engine::download_recents(std::vector<RecentRec>& rec, std::vector<uint8_t>& has) {
+  rec.clear(); has.clear();
+  const int32_t n = rw_last_n_;
+  if (!want(OUT_RW) || n == 0) return;
+  const size_t ns = (size_t)cfg_.n_rw_buckets;
+  rec.resize((size_t)n * ns);
+  std::vector<WinStat> win((size_t)n);
+  HIP_OK(hipMemcpyAsync(rec.data(), d_rw_rec_, rec.size() * sizeof(RecentRec), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(win.data(), d_win_, win.size() * sizeof(WinStat), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  has.resize((size_t)n);
+  for (int32_t s = 0; s < n; ++s) has[(size_t)s] = win[(size_t)s].active && win[(size_t)s].n >= 1;
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3496,7 +3572,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw"};
   return n[k];
 }
 

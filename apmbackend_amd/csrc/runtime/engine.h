@@ -136,6 +136,13 @@ struct EngineConfig {
   // construction (OUT_SV in `outputs` without a valid list is an error)
   int32_t n_svc_pcts = 0;
   int32_t svc_pcts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // rw stream (K20): the spans in buckets, strictly ascending, 1 .. window, and the percentiles as
+  // q = p * 1000, strictly ascending, 1 .. 100000; read at construction (OUT_RW in `outputs`
+  // without valid lists is an error)
+  int32_t n_rw_buckets = 0;
+  int32_t rw_buckets[4] = {0, 0, 0, 0};
+  int32_t n_rw_pcts = 0;
+  int32_t rw_pcts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int async_stats = 1;      // overlap batch i's stats with batch i+1's parse + join
   // RCCL watchdog: a collective not complete after this long (a dead or wedged peer) aborts the
   // communicator and throws, so the supervisor restarts the rank group from its checkpoint
@@ -161,13 +168,13 @@ struct EngineConfig {
 //   FS            z -> alerts/db  fs lines (one per series per LAG)
 //   AL            alerts -> db    al lines
 //   SX            new: per-JVM rollup fused with JMX / VM gauges (K14), one line per server
-enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, OUT_SV, N_OUT };
+enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, OUT_SV, OUT_RW, N_OUT };
 // Streams whose pending text a checkpoint stores (checkpoint.cpp).  The version-9 layout holds
-// exactly these; lh, wp, sl, tk and sv rows are taken by their consumer before a checkpoint and are not persisted.
+// exactly these; lh, wp, sl, tk, sv and rw rows are taken by their consumer before a checkpoint and are not persisted.
 constexpr int N_OUT_CKPT = OUT_FB + 1;
-// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk, sv); the stats thread owns the rest
+// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk, sv, rw); the stats thread owns the rest
 constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP) |
-                                (1u << OUT_SL) | (1u << OUT_TK) | (1u << OUT_SV);
+                                (1u << OUT_SL) | (1u << OUT_TK) | (1u << OUT_SV) | (1u << OUT_RW);
 const char* out_kind_name(int k);
 int out_kind_of(const std::string& name);
 
@@ -734,7 +741,7 @@ class Engine {
   std::mutex out_pool_mu_;
   bool st_has_job_ = false, st_busy_ = false, st_stop_ = false;
   std::string st_error_;
-  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk / sv streams (kLaneKinds)
+  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk / sv / rw streams (kLaneKinds)
   std::thread out_thread_;
   std::mutex out_mu_;
   std::condition_variable out_cv_;
@@ -1202,14 +1209,14 @@ class Engine {
   PinnedBuf<uint32_t> h_fs_off_[2];
   size_t fs_rows_[2] = {0, 0};
 
-  // A rollover stream whose rows are printed on the device (lh, wp, sl, sv): the buffers of its
+  // A rollover stream whose rows are printed on the device (lh, wp, sl, sv, rw): the buffers of its
   // count / scan / write text pass and two device / pinned text slots, as for st / fs.  A rollover
   // takes the other slot than the one before it; a slot is reused only after its output-lane task
   // is done, and the lane reads a slot's total only after the slot's event.  Allocated when the
   // stream is on (text_alloc); text_begin / text_end carry the slot protocol.
   struct TextStream {
     int kind = 0;                             // the stream's OUT_* kind
-    uint32_t *len = nullptr, *off = nullptr;  // [S + 1]
+    uint32_t *len = nullptr, *off = nullptr;  // [S * rows + 1] (rows per series: text_alloc)
     int32_t* big = nullptr;                   // [S] block-pass list of the value pass, [S] its length
     void* tmp = nullptr;                      // the scan's scratch
     size_t tmp_bytes = 0;
@@ -1221,7 +1228,7 @@ class Engine {
     uint64_t task[2] = {0, 0};
     int k = 1;                                // the slot the last rollover took
   };
-  void text_alloc(TextStream& t, int kind, size_t tmp_bytes);
+  void text_alloc(TextStream& t, int kind, size_t tmp_bytes, int rows = 1);
   // the next slot, free of its previous task, and its device output of at least `bound` bytes
   char* text_begin(TextStream& t, size_t bound);
   // after the plan and write launches over n positions: t.off[n] -> the slot's pinned total, the
@@ -1307,9 +1314,24 @@ class Engine {
   int32_t svc_nq() const { return cfg_.n_svc_pcts; }
  private:
 
+  // K20 rw rows (recent.hip), allocated when the stream is on: exact stats of the newest buckets of
+  // the window K8 read, one row per series and configured span, queued last in the rollover.  No
+  // device state outlives a rollover; the text pass (nspan lanes per position) and its slots are rw_'s.
+  RecentRec* d_rw_rec_ = nullptr;                           // [S][nspan]
+  TextStream rw_;
+  int32_t rw_last_n_ = 0;                                   // series of the last rollover's value pass
+  void recent_rollover(const WindowArgs& wa, int64_t edge_ts);
+ public:
+  // (tests) the value pass' result of the last rollover: per series and span its record, and
+  // whether the series had records at all (K8's WinStat.active and n >= 1)
+  void download_recents(std::vector<RecentRec>& rec, std::vector<uint8_t>& has);
+  int32_t rw_nspan() const { return cfg_.n_rw_buckets; }
+  int32_t rw_nq() const { return cfg_.n_rw_pcts; }
+ private:
+
   // text outputs
   std::string blob_[N_OUT];
-  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   std::shared_ptr<ByteSink> byte_sink_[N_OUT];
   bool fs_copy_ = false;
   bool db_copy_ = false;
@@ -1318,7 +1340,7 @@ class Engine {
   void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
-  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // K14 server rollup + exogenous context
   std::vector<double> h_ctx_;                    // [servers][CTX_FIELDS] (stats thread)
   bool ctx_dirty_ = false;

@@ -26,9 +26,11 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import (as_bool, gpu_opt, latency_objectives, leaderboard, service_window, window_percentiles,
-                            zscore_lag_settings)
-from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, ServiceWindowEntry,
+from ..utils.config import (as_bool, check_recent_windows, gpu_opt, latency_objectives, leaderboard, recent_windows,
+                            service_window,
+                            window_percentiles, zscore_lag_settings)
+from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, RecentWindowEntry,
+                             ServiceWindowEntry,
                              StatEntry, TxEntry, WindowPctEntry, WindowSloEntry, entry_from_csv, hist_bin, hist_lower,
                              pct_ranks)
 from ..utils.timeparse import TzOffset, convert_string_date_to_ms, default_tz
@@ -673,7 +675,12 @@ class StatsOracle:
                  emit_pct: Optional[Callable[[str], None]] = None, percentiles: Iterable[int] = (),
                  emit_slo: Optional[Callable[[str], None]] = None, objectives: Optional[Dict[str, Any]] = None,
                  emit_top: Optional[Callable[[str], None]] = None, board: Optional[Dict[str, Any]] = None,
-                 emit_svc: Optional[Callable[[str], None]] = None, svc_percentiles: Iterable[int] = ()):
+                 emit_svc: Optional[Callable[[str], None]] = None, svc_percentiles: Iterable[int] = (),
+                 emit_recent: Optional[Callable[[str], None]] = None, recent_buckets: Iterable[int] = (),
+                 recent_percentiles: Iterable[int] = ()):
+        self.emit_recent = emit_recent  # rw rows (docs/RECENT.md); None = stream off
+        self.recent_buckets = [int(k) for k in recent_buckets]  # spans in buckets, ascending
+        self.recent_percentiles = [int(q) for q in recent_percentiles]  # q = p * 1000
         self.emit_svc = emit_svc    # sv rows (docs/SERVICEWINDOW.md); None = stream off
         self.svc_percentiles = [int(q) for q in svc_percentiles]  # q = p * 1000 (config.service_window)
         self.emit_top = emit_top    # tk rows (docs/LEADERBOARD.md); None = stream off
@@ -819,6 +826,30 @@ class StatsOracle:
                                            pcts).to_csv())
         return rows
 
+    def recent_rows(self, edge_ts: int, server: str, service: str, svc: Dict[int, List[int]]) -> List[str]:
+        """The rw rows of one series with an st row: per configured span of k buckets, the samples
+        of the window buckets newer than ``latest - buffer - min(k, window buckets)``: the count of
+        those that are not NaN, the NaN count, the sum and the percentiles of the former by the
+        integer rank rule (none when there is no such sample).  No row when the whole window is
+        empty."""
+        newest = self.latest - self.buffer
+        n_win = self.keep - self.buffer + 1
+        if not any(arr for b, arr in svc.items() if self.latest - self.keep <= b <= newest):
+            return []
+        rows = []
+        for k in self.recent_buckets:
+            lo = newest - min(k, n_win)
+            flat = [v for b in sorted(svc) if lo < b <= newest for v in svc[b]]
+            # the engine stores int32; anything else is its NaN sentinel (engine.cpp)
+            fin = sorted(int(v) for v in flat if v == v and -2147483647 <= v <= 2147483647)
+            pcts = []
+            for q in self.recent_percentiles if fin else ():
+                r0, r1 = pct_ranks(len(fin), q)
+                pcts.append((q, fin[r0] + fin[r1]))
+            rows.append(RecentWindowEntry(edge_ts, server, service, k, len(fin), len(flat) - len(fin), sum(fin),
+                                          pcts).to_csv())
+        return rows
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -867,6 +898,9 @@ class StatsOracle:
                     row = self.slo_row(edge_ts, server, service, win)
                     if row is not None:
                         self.emit_slo(row)
+                if self.emit_recent is not None and cnt != 0:
+                    for row in self.recent_rows(edge_ts, server, service, svc):
+                        self.emit_recent(row)
         if self.emit_top is not None:
             for row in self.top_rows(st_rows):
                 self.emit_top(row)
@@ -1104,11 +1138,15 @@ class PipelineOracle:
         self.sl: List[str] = []
         self.tk: List[str] = []
         self.sv: List[str] = []
+        self.rw: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
         self.alerts = AlertsOracle(cfg, alert_clock, cooldown_key=g.get("cooldownKey", "service"))
         sc = cfg["streamCalcStats"]
+        # (as APMEngine does: a span is at most windowSizeInIntervals at construction; reload() may
+        # shorten the window later, and the span then reads the whole window)
+        check_recent_windows(recent_windows(cfg), int(sc["windowSizeInIntervals"]))
         self.st = StatsOracle(self._on_st, self.tx_db.append, int(sc["intervalLengthInSeconds"]),
                               int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
                               emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None,
@@ -1119,7 +1157,10 @@ class PipelineOracle:
                               emit_top=self.tk.append if leaderboard(cfg) else None,
                               board=leaderboard(cfg),
                               emit_svc=self.sv.append if service_window(cfg) else None,
-                              svc_percentiles=service_window(cfg))
+                              svc_percentiles=service_window(cfg),
+                              emit_recent=self.rw.append if recent_windows(cfg) else None,
+                              recent_buckets=(recent_windows(cfg) or {}).get("buckets", ()),
+                              recent_percentiles=(recent_windows(cfg) or {}).get("percentiles", ()))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

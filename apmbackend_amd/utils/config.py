@@ -96,6 +96,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "topQueue": "leaderboard",        # amqp mode: the queue the tk records go to
     "serviceWindow": None,            # K19 "sv" stream: exact per-service window stats across servers, {"percentiles": [50, 75, 95, 99]} (docs/SERVICEWINDOW.md)
     "svcQueue": "service_window",     # amqp mode: the queue the sv records go to
+    "recentWindows": None,            # K20 "rw" stream: exact stats of the newest window buckets, {"buckets": [1, 6], "percentiles": [50, 95, 99]} (docs/RECENT.md)
+    "recentQueue": "recent_window",   # amqp mode: the queue the rw records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -285,6 +287,51 @@ def service_window(cfg: Dict[str, Any]) -> List[int]:
     return parse_service_window(gpu_opt(cfg, "serviceWindow"))
 
 
+RECENT_MAX_SPANS = 4
+
+
+def parse_recent_windows(v: Any) -> Optional[Dict[str, List[int]]]:
+    """gpu.recentWindows -> {"buckets": [k, ...], "percentiles": [q, ...]} (q = p * 1000).
+    ``buckets``: 1 to 4 JSON integers (no bool, float or string), strictly ascending, each at least
+    1; the bound against the window is the engine's (check_recent_windows).  ``percentiles``: the
+    rules of gpu.windowPercentiles, at least one entry.  None -> None (stream off); an object
+    without either list, with any other member, or a value of any other type raises ValueError."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.recentWindows: an object with 'buckets' and 'percentiles', got {v!r}")
+    extra = set(v) - {"buckets", "percentiles"}
+    if extra:
+        raise ValueError(f"gpu.recentWindows: unknown key(s) {sorted(extra, key=str)!r}")
+    b = v.get("buckets")
+    if not isinstance(b, list) or not 1 <= len(b) <= RECENT_MAX_SPANS:
+        raise ValueError(f"gpu.recentWindows: buckets must list 1 to {RECENT_MAX_SPANS} bucket counts, got {b!r}")
+    for i, k in enumerate(b):
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > 0x7fffffff:
+            raise ValueError(f"gpu.recentWindows.buckets: integers >= 1, got {k!r}")
+        if i and k <= b[i - 1]:
+            raise ValueError(f"gpu.recentWindows.buckets: strictly ascending, got {b!r}")
+    try:
+        qs = parse_window_percentiles(v.get("percentiles"))
+    except ValueError as e:
+        raise ValueError(str(e).replace("gpu.windowPercentiles", "gpu.recentWindows.percentiles", 1)) from None
+    if not qs:
+        raise ValueError("gpu.recentWindows: percentiles must list 1 to 8 percentiles")
+    return {"buckets": [int(k) for k in b], "percentiles": qs}
+
+
+def recent_windows(cfg: Dict[str, Any]) -> Optional[Dict[str, List[int]]]:
+    """The validated gpu.recentWindows object of a config (None: off)."""
+    return parse_recent_windows(gpu_opt(cfg, "recentWindows"))
+
+
+def check_recent_windows(rw: Optional[Dict[str, List[int]]], window: int) -> None:
+    """The bound an engine puts on the spans when it is constructed: at most windowSizeInIntervals."""
+    if rw and rw["buckets"][-1] > int(window):
+        raise ValueError(f"gpu.recentWindows.buckets: at most windowSizeInIntervals ({int(window)}), "
+                         f"got {rw['buckets'][-1]}")
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -324,6 +371,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         parse_leaderboard(merged["leaderboard"])  # likewise
     if "serviceWindow" in merged:
         parse_service_window(merged["serviceWindow"])  # likewise
+    if "recentWindows" in merged:
+        parse_recent_windows(merged["recentWindows"])  # likewise
     return cfg
 
 

@@ -516,6 +516,35 @@ class ServiceWindowEntry:
                 "pcts": {pct_text(q): (v // 2 if v % 2 == 0 else v / 2) for q, v in self.pcts}}
 
 
+# ---- rw: exact stats of the newest window buckets (docs/RECENT.md).  Integers only.
+@dataclass
+class RecentWindowEntry:
+    """``rw|ts|server|service|k|m|nan|sum|p:v,p:v,...`` -- at a rollover, the newest ``buckets``
+    buckets of the series' K8 window: ``count`` non-NaN samples (``nan`` counts the others), their
+    int64 ``elapsed_sum`` and their exact percentiles (no reference counterpart).  ``pcts`` holds
+    (q, sum2) integer pairs as WindowPctEntry does; it is empty when ``count`` is 0."""
+    timestamp: Num
+    server: str
+    service: str
+    buckets: int
+    count: int
+    nan: int
+    elapsed_sum: int
+    pcts: List[tuple]
+    type: str = "rw"
+
+    def to_csv(self) -> str:
+        pairs = ",".join(f"{pct_text(q)}:{half_text(v)}" for q, v in self.pcts)
+        return (f"rw|{js_str(self.timestamp)}|{self.server}|{self.service}|{int(self.buckets)}|{int(self.count)}|"
+                f"{int(self.nan)}|{int(self.elapsed_sum)}|{pairs}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "buckets": int(self.buckets), "count": int(self.count), "nan": int(self.nan),
+                "elapsed_sum": int(self.elapsed_sum),
+                "pcts": {pct_text(q): (v // 2 if v % 2 == 0 else v / 2) for q, v in self.pcts}}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -591,7 +620,20 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
             if q is not None and s2 is not None:  # (a malformed pair is dropped, likewise)
                 pcts.append((q, s2))
         return ServiceWindowEntry(parse_int(a[1]), a[2], srv, cnt, nan, tot, pcts)
+    if t == "rw":
+        a = _pad(arr, 9)
+        k, cnt, nan = _svc_int(a[4]), _svc_int(a[5]), _svc_int(a[6])
+        tot = _svc_int(a[7], 18, signed=True)
+        if k is None or cnt is None or nan is None or tot is None:  # (a malformed row is dropped, as copyenc.cpp does)
+            return None
+        pcts = []
+        for pr in (a[8] or "").split(","):
+            p, _sep, v = pr.partition(":")
+            q, s2 = _pct_from_text(p), _half_from_text(v)
+            if q is not None and s2 is not None:  # (a malformed pair is dropped, likewise)
+                pcts.append((q, s2))
+        return RecentWindowEntry(parse_int(a[1]), a[2], a[3], k, cnt, nan, tot, pcts)
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw")
