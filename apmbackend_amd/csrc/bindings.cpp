@@ -11,6 +11,7 @@
 #include <cstring>
 #include <memory>
 
+#include "kernels/burncmp.h"
 #include "kernels/kernel_api.h"
 #include "runtime/engine.h"
 #include "runtime/format.h"
@@ -168,6 +169,29 @@ EngineConfig config_from(const py::dict& d) {
       c.rw_pcts[i] = (int32_t)v[i];
     }
   }
+  if (d.contains("sb_classes")) {  // K21 (the constructor checks the tables and rules when the sb stream is on)
+    c.sb_classes = d["sb_classes"].cast<std::vector<std::vector<int64_t>>>();
+    if (d.contains("sb_services")) c.sb_services = d["sb_services"].cast<std::map<std::string, int32_t>>();
+    c.sb_default = get<int32_t>(d, "sb_default", 0);
+  }
+  if (d.contains("sb_short")) {
+    auto k = d["sb_short"].cast<std::vector<int64_t>>();
+    auto f = d.contains("sb_factor") ? d["sb_factor"].cast<std::vector<int64_t>>() : std::vector<int64_t>();
+    if (k.size() > 4 || f.size() != k.size()) throw std::invalid_argument("sb_short / sb_factor: at most 4 rules, one factor per span");
+    c.n_sb_rules = (int32_t)k.size();
+    for (size_t i = 0; i < k.size(); ++i) {
+      if (k[i] < 1 || k[i] > 0x7fffffff || (i && k[i] <= k[i - 1]))
+        throw std::invalid_argument("sb_short: strictly ascending integers >= 1");
+      if (f[i] < 1 || f[i] > 1000000) throw std::invalid_argument("sb_factor: integers in 1 .. 1000000 (factor * 1000)");
+      c.sb_short[i] = (int32_t)k[i];
+      c.sb_factor[i] = (int32_t)f[i];
+    }
+  }
+  if (d.contains("sb_min_samples")) {
+    const int64_t ms = d["sb_min_samples"].cast<int64_t>();
+    if (ms < 1 || ms > 0x7fffffff) throw std::invalid_argument("sb_min_samples: an integer >= 1");
+    c.sb_min_samples = (int32_t)ms;
+  }
   if (d.contains("tk_k") && !d["tk_k"].is_none()) {  // (the constructor checks them when the tk stream is on)
     c.tk_k = d["tk_k"].cast<int32_t>();
     if (d.contains("tk_by")) c.tk_by = d["tk_by"].cast<std::vector<int32_t>>();
@@ -222,6 +246,7 @@ py::dict metrics_dict(const EngineMetrics& m) {
   d["db_copy_rows"] = m.db_copy_rows; d["db_copy_fallbacks"] = m.db_copy_fallbacks;
   d["t_stats_tx_ms"] = m.t_stats_tx_ms; d["t_rollover_ms"] = m.t_rollover_ms;
   d["t_format_ms"] = m.t_format_ms; d["t_release_ms"] = m.t_release_ms;
+  d["sb_rows"] = m.sb_rows;
   d["formatted_bytes"] = m.formatted_bytes; d["lockstep_rollovers"] = m.lockstep_rollovers; d["format_fallbacks"] = m.format_fallbacks;
   d["t_parse_ms"] = m.t_parse_ms; d["t_join_ms"] = m.t_join_ms; d["t_stats_ms"] = m.t_stats_ms;
   d["t_total_ms"] = m.t_total_ms;
@@ -667,6 +692,23 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("burns", [](Engine& e) {
+        // per series id of the last rollover's K21 value pass: None for a series without an st row or
+        // an objective, else (m, bad, nan, [(m_k, bad_k) per configured rule], fired mask)
+        std::vector<BurnRec> rec;
+        std::vector<uint8_t> has;
+        e.download_burns(rec, has);
+        const int nr = e.sb_nrule();
+        py::list out;
+        for (size_t s = 0; s < has.size(); ++s) {
+          if (!has[s]) { out.append(py::none()); continue; }
+          const BurnRec& r = rec[s];
+          py::list rules;
+          for (int j = 0; j < nr; ++j) rules.append(py::make_tuple(r.mk[j], r.badk[j]));
+          out.append(py::make_tuple(r.m, r.bad, r.nan, rules, r.fired));
+        }
+        return out;
+      })
       .def("leaderboard", [](Engine& e) {
         // the last rollover's K18 records: (board, rank, series id, tpm, avg, p75, p95), raw doubles
         std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> rows;
@@ -725,15 +767,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[11];
-    int64_t counts[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::string out[12];
+    int64_t counts[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[11] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw"};
-    for (int k = 0; k < 11; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[12] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb"};
+    for (int k = 0; k < 12; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -932,6 +974,17 @@ PYBIND11_MODULE(_apm_native, m) {
   // which the value pass keeps a series in its 32-lane group (tests bracket them)
   m.def("recent_group_max", []() { return apm_recent_group_max(); });
   m.def("recent_group_win", []() { return apm_recent_group_win(); });
+  // sb burn rates (burn.hip): the sample count up to which the value pass keeps a series in its
+  // 32-lane group (tests bracket it), and the exact inequality the kernels decide a rule with
+  // (burncmp.h, the same routine compiled for the host): m >= min_samples and
+  // bad * 10^8 >= f * m * b
+  m.def("burn_group_max", []() { return apm_burn_group_max(); });
+  m.def("burn_fires", [](int64_t bad, int64_t mm, int64_t b, int64_t f, int64_t min_samples) {
+    if (bad < 0 || bad > 0x7fffffff || mm < 0 || mm > 0x7fffffff || b < 1 || b > 99999 || f < 1 || f > 1000000 ||
+        min_samples < 1 || min_samples > 0x7fffffff)
+      throw std::invalid_argument("burn_fires: bad, m in 0 .. 2147483647, b in 1 .. 99999, f in 1 .. 1000000, min_samples >= 1");
+    return burn_fires((uint32_t)bad, (uint32_t)mm, (uint32_t)b, (uint32_t)f, (uint32_t)min_samples);
+  }, py::arg("bad"), py::arg("m"), py::arg("b"), py::arg("f"), py::arg("min_samples"));
   m.def("apm_topk_tile", []() { return apm_topk_tile(); });
   m.def("apm_topk_final_span", []() { return apm_topk_final_span(); });
   m.def("topk_select", [](const std::vector<std::tuple<double, double, double, double, int32_t>>& win_rows,

@@ -365,6 +365,52 @@ struct RecentTextArgs {
   uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
   char* out;                    // at least apm_recent_row_bound(max name bytes, nq) * n bytes
 };
+// K21 sb rows: SLO burn-rate breaches decided on the device (burn.hip, docs/BURN.md).  A class is
+// one objective {T, q}: T the latency threshold, q = target * 1000, b = 100000 - q the error budget;
+// class 0 is "no row".  Over the window K8 just read (the same WindowArgs) and, per rule j, over
+// its newest span[j] buckets (rw's span: the entries r >= n_win - min(span[j], n_win)) the value
+// pass counts the finite samples and those above T, decides every rule with burn_fires (burncmp.h)
+// and writes one record per series; the text pass prints, per emission position of a series with a
+// rule that fired:
+//   sb|<edge ts>|server|service|<T>|<q>|<m>|<bad>|<nan>|<k>:<f>:<m_k>:<bad_k>:<0|1>,...
+constexpr int SB_MAX_RULES = 4;
+struct BurnRec {
+  int32_t m, bad, nan;          // window samples that are finite / finite and above T / ELAPSED_NAN
+  int32_t mk[SB_MAX_RULES];     // per rule: the finite samples of its span
+  int32_t badk[SB_MAX_RULES];   // ... and those of them above T
+  int32_t fired;                // bit j: rule j fired (window and span both burn at factor[j])
+};
+struct BurnArgs {
+  WindowArgs w;                 // K8's arguments of this rollover (w.out = K8's result)
+  const int32_t* cls;           // [S] class per series (0 or out of range: no row)
+  const int32_t* obj;           // [n_classes][2] {T, q} (class 0: unused)
+  int32_t n_classes;
+  int32_t nrule;                // 1 .. SB_MAX_RULES
+  int32_t span[SB_MAX_RULES];   // buckets per rule, strictly ascending, >= 1
+  int32_t factor[SB_MAX_RULES]; // f = factor * 1000, 1 .. 1000000
+  int32_t min_samples;          // >= 1
+  BurnRec* rec;                 // [S]
+  int32_t* big_list;            // [S] series deferred to the block pass
+  int32_t* big_n;
+};
+struct BurnTextArgs {
+  const BurnRec* rec;           // [S]
+  const int32_t* cls;           // [S]
+  const int32_t* obj;           // [n_classes][2]
+  int32_t n_classes;
+  const int32_t* perm;          // [n] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;
+  int32_t n_series;
+  int32_t nrule;
+  int32_t span[SB_MAX_RULES];
+  int32_t factor[SB_MAX_RULES];
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_burn_row_bound(max name bytes) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -529,6 +575,17 @@ void apm_recent_values(apm::RecentArgs* a, hipStream_t stream);
 // length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_recent_plan(apm::RecentTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_recent_write(apm::RecentTextArgs* a, hipStream_t stream);
+// burn.hip
+// the value pass' two paths (tests bracket them): a series K8 counted at most apm_burn_group_max()
+// samples for stays in its 32-lane group, every other one is counted by a block
+int32_t apm_burn_group_max();
+size_t apm_burn_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes
+size_t apm_burn_row_bound(size_t name_bytes);
+void apm_burn_values(apm::BurnArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_burn_plan(apm::BurnTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_burn_write(apm::BurnTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

@@ -267,8 +267,8 @@ void append_pct_pairs(std::string& js, std::string_view rest) {
   }
 }
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[11]*/) {
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw, 11 sb) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[12]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -489,6 +489,58 @@ int encode_line(std::string_view line, std::string* out /*[11]*/) {
     copy_escape(o, js);
     o += '\n';
     return 10;
+  }
+  if (t == "sb") {  // SLO burn: timestamp, server, service, threshold, target_q, count, bad, nan, rules json
+    // (utils/records.py entry_from_csv and burn_rules_from_text hold the same rules) a row whose T,
+    // q, m, bad or nan is not 1 to 10 plain digits, or whose last field is not 1 to 4 groups
+    // k:f:m:bad:fired of such numbers with fired 0 or 1, is dropped whole
+    for (int i = 4; i <= 8; ++i)
+      if (!a.has(i) || !all_digits(a.f[i], 10)) return -1;
+    if (!a.has(9) || a.f[9].empty()) return -1;
+    std::string js = "[";
+    {
+      static const char* key[5] = {"{\"k\":", ",\"f\":", ",\"m\":", ",\"bad\":", ",\"fired\":"};
+      std::string_view rest = a.f[9];
+      int groups = 0;
+      for (;;) {
+        const size_t e = rest.find(',');
+        std::string_view g = rest.substr(0, e);
+        if (++groups > 4) return -1;
+        if (groups > 1) js += ',';
+        for (int p = 0; p < 5; ++p) {
+          const size_t c = g.find(':');
+          if ((p < 4) == (c == std::string_view::npos)) return -1;  // (exactly five parts)
+          const std::string_view num = g.substr(0, c);
+          if (!all_digits(num, 10)) return -1;
+          js += key[p];
+          if (p == 4) {
+            if (num != "0" && num != "1") return -1;
+            js += num == "1" ? "true" : "false";
+          } else {
+            int64_t v = 0;
+            for (char ch : num) v = v * 10 + (ch - '0');
+            append_i64(js, v);
+            g = g.substr(c + 1);
+          }
+        }
+        js += '}';
+        if (e == std::string_view::npos) break;
+        rest = rest.substr(e + 1);
+      }
+    }
+    js += ']';
+    std::string& o = out[11];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    for (int i = 4; i <= 8; ++i) {
+      int64_t v = 0;
+      for (char ch : a.f[i]) v = v * 10 + (ch - '0');
+      append_i64(o, v); o += '\t';
+    }
+    copy_escape(o, js);
+    o += '\n';
+    return 11;
   }
   if (t == "jx") {
     std::string& o = out[3];

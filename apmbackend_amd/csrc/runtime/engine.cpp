@@ -265,6 +265,24 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       throw std::invalid_argument("rw stream: rw_buckets must hold 1 to 4 strictly ascending spans in 1 .. window and "
                                   "rw_pcts 1 to 8 strictly ascending percentiles");
   }
+  if (want(OUT_SB)) {  // K21: the stream needs its tables and rules (likewise before anything is allocated)
+    const auto& cl = cfg_.sb_classes;
+    bool ok = cl.size() >= 2 && cl[0].empty() && cl.size() <= (size_t)cfg_.max_series + 2;
+    for (size_t c = 1; ok && c < cl.size(); ++c)
+      ok = cl[c].size() == 2 && cl[c][0] >= 0 && cl[c][0] <= INT32_MAX && cl[c][1] >= 1 && cl[c][1] <= 99999;
+    const auto in_range = [&](int32_t c) { return c >= 0 && (size_t)c < cl.size(); };
+    ok = ok && in_range(cfg_.sb_default);
+    for (const auto& kv : cfg_.sb_services) ok = ok && in_range(kv.second);
+    const int nr = cfg_.n_sb_rules;
+    ok = ok && nr >= 1 && nr <= SB_MAX_RULES && cfg_.sb_min_samples >= 1;
+    for (int j = 0; ok && j < nr; ++j)
+      ok = cfg_.sb_short[j] >= 1 && cfg_.sb_short[j] <= cfg_.window && (j == 0 || cfg_.sb_short[j] > cfg_.sb_short[j - 1]) &&
+           cfg_.sb_factor[j] >= 1 && cfg_.sb_factor[j] <= 1000000;
+    if (!ok)
+      throw std::invalid_argument("sb stream: sb_classes must hold the empty class 0 and at least one objective {T in 0 .. "
+                                  "2147483647, q in 1 .. 99999}, every class index must name one; sb_short must hold 1 to 4 "
+                                  "strictly ascending spans in 1 .. window, sb_factor factors in 1 .. 1000000, sb_min_samples >= 1");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -486,6 +504,23 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     const int ns = cfg_.n_rw_buckets;
     d_rw_rec_ = (RecentRec*)res_.dmalloc((size_t)S * ns * sizeof(RecentRec));
     text_alloc(rw_, OUT_RW, apm_recent_tmp_bytes(S * ns), ns);
+  }
+  if (want(OUT_SB)) {  // K21
+    const int32_t C = (int32_t)cfg_.sb_classes.size();  // (checked at the top of the constructor)
+    n_sb_classes_ = C;
+    d_sb_obj_ = (int32_t*)res_.dmalloc((size_t)C * 2 * 4);
+    {
+      std::vector<int32_t> tab((size_t)C * 2, 0);
+      for (int32_t c = 1; c < C; ++c) {
+        tab[(size_t)c * 2] = (int32_t)cfg_.sb_classes[c][0];
+        tab[(size_t)c * 2 + 1] = (int32_t)cfg_.sb_classes[c][1];
+      }
+      HIP_OK(hipMemcpy(d_sb_obj_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    }
+    d_sb_cls_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    HIP_OK(hipMemset(d_sb_cls_, 0, (size_t)S * 4));  // class 0 until a series' class is uploaded
+    d_sb_rec_ = (BurnRec*)res_.dmalloc((size_t)S * sizeof(BurnRec));
+    text_alloc(sb_, OUT_SB, apm_burn_tmp_bytes(S));
   }
   if (want(OUT_LH)) text_alloc(lh_, OUT_LH, apm_hist_tmp_bytes(S));  // K15
   {
@@ -719,6 +754,7 @@ int32_t Engine::series_for(int32_t server, int32_t service) {
   h_infl_.resize((size_t)n_series_ * MAX_LAGS);
   h_hard_max_.push_back(cfg_.hard_max_ms);
   if (want(OUT_SL)) h_slo_cls_.push_back(slo_class_of(s));  // (uploaded with the hard max)
+  if (want(OUT_SB)) h_sb_cls_.push_back(burn_class_of(s));  // K21: likewise
   h_suppressed_.push_back(0);
   zscore_seen_.push_back(0);
   h_active_.push_back(0);
@@ -751,6 +787,12 @@ void Engine::apply_series_settings(int32_t s) {
 int32_t Engine::slo_class_of(int32_t s) const {
   auto it = cfg_.slo_services.find(dict_.service_name(series_[s].service));
   return it != cfg_.slo_services.end() ? it->second : cfg_.slo_default;
+}
+
+// K21: the same rule over the sb stream's own tables
+int32_t Engine::burn_class_of(int32_t s) const {
+  auto it = cfg_.sb_services.find(dict_.service_name(series_[s].service));
+  return it != cfg_.sb_services.end() ? it->second : cfg_.sb_default;
 }
 
 void Engine::refresh_series_settings() {
@@ -794,6 +836,7 @@ void Engine::upload_series_tables(int32_t lo) {
   h2d(d_suppressed_ + lo, sp, m, stream_);
   stage_done();
   if (want(OUT_SL)) upload_slo_classes(lo);
+  if (want(OUT_SB)) upload_burn_classes(lo);
 }
 
 // K17: the classes of series [lo, n) to the device, on the stats stream.  A full upload (lo == 0: a
@@ -815,6 +858,25 @@ void Engine::upload_slo_classes(int32_t lo) {
     stage_done();
   }
   slo_cls_uploaded_ = n;
+}
+
+// K21: upload_slo_classes over the sb stream's own class array
+void Engine::upload_burn_classes(int32_t lo) {
+  const int32_t n = n_series_;
+  lo = std::min(lo, sb_cls_uploaded_);  // (series no earlier upload carried go along)
+  if (lo == 0 || h_sb_cls_.size() != (size_t)n) {
+    h_sb_cls_.resize((size_t)n);
+    for (int32_t s = 0; s < n; ++s) h_sb_cls_[s] = burn_class_of(s);
+    lo = 0;
+  }
+  if (n > lo) {
+    const size_t mc = (size_t)(n - lo);
+    int32_t* cs = (int32_t*)stage(mc * 4);
+    std::memcpy(cs, h_sb_cls_.data() + lo, mc * 4);
+    h2d(d_sb_cls_ + lo, cs, mc * 4, stream_);
+    stage_done();
+  }
+  sb_cls_uploaded_ = n;
 }
 
 std::vector<uint64_t> Engine::cache_stats(bool drain) {
@@ -1495,6 +1557,8 @@ void Engine::flush() {
     t_out_ms_ = 0;
     metrics_.formatted_bytes += formatted_bytes_lane_;
     formatted_bytes_lane_ = 0;
+    metrics_.sb_rows += sb_rows_lane_;
+    sb_rows_lane_ = 0;
     if (!out_error_.empty()) { std::string e = out_error_; out_error_.clear(); throw std::runtime_error(e); }
   }
   if (!st_error_.empty()) { std::string e = st_error_; st_error_.clear(); throw std::runtime_error(e); }
@@ -2435,6 +2499,9 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   // what K16 reads -- window cells, counts, the sorted spill lists, d_win_ -- nothing queued since
   // K8 writes any of them, and the next append follows on this stream.
   if (want(OUT_RW)) recent_rollover(wa, edge_ts);
+  // K21: last of all, for the same reason: it reads what K17 reads (window cells, counts, spill
+  // lists, d_win_) and its own class array, and the next append follows on this stream.
+  if (want(OUT_SB)) burn_rollover(wa, edge_ts);
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2589,8 +2656,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[11];
-        int64_t counts[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::string enc[12];
+        int64_t counts[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3012,7 +3079,7 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   });
 }
 
-// ---- The text streams of a rollover (lh, wp, sl, sv, rw): buffers and the slot protocol, once.
+// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb): buffers and the slot protocol, once.
 // `rows`: text lanes per series (rw prints one row per span).
 void Engine::text_alloc(TextStream& t, int kind, size_t tmp_bytes, int rows) {
   const size_t S = (size_t)cfg_.max_series;
@@ -3050,6 +3117,12 @@ void Engine::text_end(TextStream& t, int32_t n) {
     res_.reserve(ts->text[k], total, total * 2 + (1 << 20));
     lane_d2h(ts->text[k], dst, total);
     lane_sync();
+    if (ts->kind == OUT_SB) {  // (metrics: the rows, under the lane's mutex as its other counters)
+      const char* p = ts->text[k];
+      const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
+      std::lock_guard<std::mutex> g(out_mu_);
+      sb_rows_lane_ += rows;
+    }
     emit_bytes(ts->kind, ts->text[k], total);
   });
 }
@@ -3432,6 +3505,68 @@ void Engine::download_recents(std::vector<RecentRec>& rec, std::vector<uint8_t>&
   for (int32_t s = 0; s < n; ++s) has[(size_t)s] = win[(size_t)s].active && win[(size_t)s].n >= 1;
 }
 
+// ---- K21: sb rows.  Per st row whose service has an objective and for which a burn-rate rule
+// fired, one row, in st order with the st rows' timestamp: value pass over K8's window (the rules
+// are decided on the device), then count / scan / write of the text -- the length pass is the
+// compaction, only the rows' bytes reach the host.
+void Engine::burn_rollover(const WindowArgs& wa, int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();
+  // (series whose settings no upload_series_tables() carried yet: as slo_rollover)
+  if (sb_cls_uploaded_ < n) upload_burn_classes(sb_cls_uploaded_);
+  const int nr = cfg_.n_sb_rules;
+  BurnArgs va{};
+  va.w = wa;
+  va.cls = d_sb_cls_;
+  va.obj = d_sb_obj_;
+  va.n_classes = n_sb_classes_;
+  va.nrule = nr;
+  for (int j = 0; j < nr; ++j) { va.span[j] = cfg_.sb_short[j]; va.factor[j] = cfg_.sb_factor[j]; }
+  va.min_samples = cfg_.sb_min_samples;
+  va.rec = d_sb_rec_;
+  va.big_list = sb_.big;
+  va.big_n = sb_.big + cfg_.max_series;
+  apm_burn_values(&va, stream_);
+  sb_last_n_ = n;
+  BurnTextArgs ta{};
+  ta.rec = d_sb_rec_;
+  ta.cls = d_sb_cls_;
+  ta.obj = d_sb_obj_;
+  ta.n_classes = n_sb_classes_;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n;
+  ta.n_series = n;
+  ta.nrule = nr;
+  for (int j = 0; j < nr; ++j) { ta.span[j] = cfg_.sb_short[j]; ta.factor[j] = cfg_.sb_factor[j]; }
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  ta.len = sb_.len;
+  ta.off = sb_.off;
+  // the output bound needs no length pass: every row is at most apm_burn_row_bound bytes
+  ta.out = text_begin(sb_, (size_t)n * apm_burn_row_bound(max_name_len_) + 64);
+  if (apm_burn_plan(&ta, sb_.tmp, sb_.tmp_bytes, stream_) != 0) throw std::runtime_error("burn scan failed");
+  apm_burn_write(&ta, stream_);
+  text_end(sb_, n);
+}
+
+void Engine::download_burns(std::vector<BurnRec>& rec, std::vector<uint8_t>& has) {
+  rec.clear(); has.clear();
+  const int32_t n = sb_last_n_;
+  if (!want(OUT_SB) || n == 0) return;
+  rec.resize((size_t)n);
+  std::vector<WinStat> win((size_t)n);
+  std::vector<int32_t> cls((size_t)n);
+  HIP_OK(hipMemcpyAsync(rec.data(), d_sb_rec_, rec.size() * sizeof(BurnRec), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(win.data(), d_win_, win.size() * sizeof(WinStat), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(cls.data(), d_sb_cls_, cls.size() * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  has.resize((size_t)n);
+  for (int32_t s = 0; s < n; ++s)
+    has[(size_t)s] = win[(size_t)s].active && cls[(size_t)s] > 0 && cls[(size_t)s] < n_sb_classes_;
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3572,7 +3707,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb"};
   return n[k];
 }
 

@@ -26,11 +26,11 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import (as_bool, check_recent_windows, gpu_opt, latency_objectives, leaderboard, recent_windows,
+from ..utils.config import (as_bool, check_recent_windows, check_slo_burn, gpu_opt, slo_burn, latency_objectives, leaderboard, recent_windows,
                             service_window,
                             window_percentiles, zscore_lag_settings)
 from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, RecentWindowEntry,
-                             ServiceWindowEntry,
+                             ServiceWindowEntry, SloBurnEntry,
                              StatEntry, TxEntry, WindowPctEntry, WindowSloEntry, entry_from_csv, hist_bin, hist_lower,
                              pct_ranks)
 from ..utils.timeparse import TzOffset, convert_string_date_to_ms, default_tz
@@ -677,7 +677,10 @@ class StatsOracle:
                  emit_top: Optional[Callable[[str], None]] = None, board: Optional[Dict[str, Any]] = None,
                  emit_svc: Optional[Callable[[str], None]] = None, svc_percentiles: Iterable[int] = (),
                  emit_recent: Optional[Callable[[str], None]] = None, recent_buckets: Iterable[int] = (),
-                 recent_percentiles: Iterable[int] = ()):
+                 recent_percentiles: Iterable[int] = (),
+                 emit_burn: Optional[Callable[[str], None]] = None, burn: Optional[Dict[str, Any]] = None):
+        self.emit_burn = emit_burn  # sb rows (docs/BURN.md); None = stream off
+        self.burn = burn            # config.parse_slo_burn's result
         self.emit_recent = emit_recent  # rw rows (docs/RECENT.md); None = stream off
         self.recent_buckets = [int(k) for k in recent_buckets]  # spans in buckets, ascending
         self.recent_percentiles = [int(q) for q in recent_percentiles]  # q = p * 1000
@@ -850,6 +853,42 @@ class StatsOracle:
                                           pcts).to_csv())
         return rows
 
+    @staticmethod
+    def _burn_counts(flat: List[Any], T: int) -> Tuple[int, int, int]:
+        """(m, bad, nan) of a list of samples: the finite ones, those of them above T, the others."""
+        # the engine stores int32; anything else is its NaN sentinel (engine.cpp)
+        fin = [int(v) for v in flat if v == v and -2147483647 <= v <= 2147483647]
+        return len(fin), sum(1 for v in fin if v > T), len(flat) - len(fin)
+
+    def burn_row(self, edge_ts: int, server: str, service: str, svc: Dict[int, List[int]]) -> Optional[str]:
+        """The sb row of one series with an st row: None unless its service has an objective and, for
+        at least one rule (k, f), both the whole window and its newest min(k, window buckets)
+        buckets hold at least minSamples finite samples and satisfy bad * 10^8 >= f * m * b
+        (b = 100000 - q), in integers."""
+        named = self.burn["services"]
+        obj = named[service] if service in named else self.burn["default"]  # (a service named with null: no row)
+        if obj is None:
+            return None
+        T, q = obj
+        b = 100000 - q
+        ms = self.burn["minSamples"]
+        newest = self.latest - self.buffer
+        n_win = self.keep - self.buffer + 1
+
+        def burns(m: int, bad: int, f: int) -> bool:
+            return m >= ms and bad * 10 ** 8 >= f * m * b
+
+        m, bad, nan = self._burn_counts([v for k in sorted(svc) if self.latest - self.keep <= k <= newest
+                                         for v in svc[k]], T)
+        rules = []
+        for k, f in self.burn["rules"]:
+            lo = newest - min(k, n_win)
+            mk, badk, _ = self._burn_counts([v for bk in sorted(svc) if lo < bk <= newest for v in svc[bk]], T)
+            rules.append((k, f, mk, badk, burns(m, bad, f) and burns(mk, badk, f)))
+        if not any(r[4] for r in rules):
+            return None
+        return SloBurnEntry(edge_ts, server, service, T, q, m, bad, nan, rules).to_csv()
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -901,6 +940,10 @@ class StatsOracle:
                 if self.emit_recent is not None and cnt != 0:
                     for row in self.recent_rows(edge_ts, server, service, svc):
                         self.emit_recent(row)
+                if self.emit_burn is not None:
+                    row = self.burn_row(edge_ts, server, service, svc)
+                    if row is not None:
+                        self.emit_burn(row)
         if self.emit_top is not None:
             for row in self.top_rows(st_rows):
                 self.emit_top(row)
@@ -1139,6 +1182,7 @@ class PipelineOracle:
         self.tk: List[str] = []
         self.sv: List[str] = []
         self.rw: List[str] = []
+        self.sb: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1147,6 +1191,7 @@ class PipelineOracle:
         # (as APMEngine does: a span is at most windowSizeInIntervals at construction; reload() may
         # shorten the window later, and the span then reads the whole window)
         check_recent_windows(recent_windows(cfg), int(sc["windowSizeInIntervals"]))
+        check_slo_burn(slo_burn(cfg), int(sc["windowSizeInIntervals"]))  # (likewise)
         self.st = StatsOracle(self._on_st, self.tx_db.append, int(sc["intervalLengthInSeconds"]),
                               int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
                               emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None,
@@ -1160,7 +1205,8 @@ class PipelineOracle:
                               svc_percentiles=service_window(cfg),
                               emit_recent=self.rw.append if recent_windows(cfg) else None,
                               recent_buckets=(recent_windows(cfg) or {}).get("buckets", ()),
-                              recent_percentiles=(recent_windows(cfg) or {}).get("percentiles", ()))
+                              recent_percentiles=(recent_windows(cfg) or {}).get("percentiles", ()),
+                              emit_burn=self.emit_burn if slo_burn(cfg) else None, burn=slo_burn(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 
@@ -1189,6 +1235,10 @@ class PipelineOracle:
             if len(self.st.servers) != n:  # a server's first series: its node-wide order key
                 for srv in list(self.st.servers)[n:]:
                     self._first_batch.setdefault(srv, self._batch_no)
+
+    def emit_burn(self, line):
+        """One sb row (docs/BURN.md) of the stats stage: kept in ``self.sb``."""
+        self.sb.append(line)
 
     def _on_st(self, line):
         self.stats.append(line)

@@ -22,8 +22,8 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 from .. import _native
 from ..models.oracle import file_kind, server_of
 from ..ops.parse_ref import tz_table
-from ..utils.config import (LEADERBOARD_KEYS, check_recent_windows, latency_objectives, leaderboard, recent_windows,
-                            service_window, slo_tables, window_percentiles)
+from ..utils.config import (LEADERBOARD_KEYS, burn_tables, check_recent_windows, check_slo_burn, latency_objectives,
+                            leaderboard, recent_windows, service_window, slo_burn, slo_tables, window_percentiles)
 from ..utils.timeparse import TzOffset
 
 log = logging.getLogger("apm.pipeline")
@@ -45,11 +45,14 @@ NATIVE_OUT_KINDS = ENGINE_OUT_KINDS + ("tk",)
 # to sv.
 DEVICE_OUT_KINDS = NATIVE_OUT_KINDS + ("sv",)
 # ... and tests/test_svcwin_model.py pins DEVICE_OUT_KINDS and its last element; STREAM_OUT_KINDS is
-# engine.h's OutKind in full and the tuple a stream's bit index comes from.
+# engine.h's OutKind up to rw.
 STREAM_OUT_KINDS = DEVICE_OUT_KINDS + ("rw",)
+# ... and tests/test_recent_*.py pin STREAM_OUT_KINDS; FULL_OUT_KINDS is engine.h's OutKind in full and
+# the tuple a stream's bit index comes from.
+FULL_OUT_KINDS = STREAM_OUT_KINDS + ("sb",)
 # keep_text=True materialises these; lh (K15 latency histograms), wp (K16 window percentiles),
-# sl (K17 threshold counts), tk (K18 leaderboards), sv (K19 per-service window stats) and rw (K20
-# stats of the newest window buckets) are opt-in through `outputs` only
+# sl (K17 threshold counts), tk (K18 leaderboards), sv (K19 per-service window stats), rw (K20
+# stats of the newest window buckets) and sb (K21 SLO burn-rate breaches) are opt-in through `outputs` only
 KEEP_TEXT_KINDS = tuple(k for k in OUT_KINDS if k != "lh")
 # What the reference persists (db_insert queue): released + audit tx, fs, al.  `transactions`
 # and `st` are internal hand-offs that only the AMQP bridge needs.
@@ -60,21 +63,22 @@ MAX_LAGS = 16  # apm_types.h MAX_LAGS: LAG capacity per engine (each LAG is an H
 def output_mask(kinds) -> int:
     m = 0
     for k in kinds:
-        m |= 1 << STREAM_OUT_KINDS.index(k)
+        m |= 1 << FULL_OUT_KINDS.index(k)
     return m
 
 
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
                   tz: Optional[TzOffset] = None, tz_centre_ms: Optional[int] = None, **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
-    materialises every stream but the opt-in lh / wp / sl / tk / sv / rw; `outputs` (iterable of STREAM_OUT_KINDS) selects explicitly.
+    materialises every stream but the opt-in lh / wp / sl / tk / sv / rw / sb; `outputs` (iterable of FULL_OUT_KINDS) selects explicitly.
     The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
     existed, `outputs` was ignored under keep_text).  "wp" takes its percentiles from
     gpu.windowPercentiles (ValueError when the list is missing or malformed), "sl" its thresholds
     from gpu.latencyObjectives (likewise), "tk" its boards from gpu.leaderboard (likewise), "sv" its percentiles
     from gpu.serviceWindow (likewise), "rw" its spans and percentiles from gpu.recentWindows (likewise; the
     bound of a span against windowSizeInIntervals is checked where an engine is constructed, not here: a
-    reload reads the settings through this function too).  `tz` (a TzOffset) stands in for gpu.timezone; the zone's
+    reload reads the settings through this function too), "sb" its objectives and rules from gpu.sloBurn
+    (likewise, the bound of a rule's span included).  `tz` (a TzOffset) stands in for gpu.timezone; the zone's
     transition table is centred on `tz_centre_ms` (default: the wall clock now, see
     ops.parse_ref.tz_table)."""
     g = cfg.get("gpu", {})
@@ -93,6 +97,10 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
     recent = recent_windows(cfg)
     if "rw" in (outputs or ()) and not recent:
         raise ValueError('outputs names "rw" but gpu.recentWindows is not set')
+    burn = slo_burn(cfg)
+    if "sb" in (outputs or ()) and not burn:
+        raise ValueError('outputs names "sb" but gpu.sloBurn is not set')
+    sb_classes, sb_services, sb_default = burn_tables(burn)
     # (the spans' bound against the window holds at construction only -- APMEngine.__init__ and the
     # native constructor: a reload may shorten the window below a span, which then reads all of it)
     zc = cfg["streamCalcZScore"]
@@ -178,6 +186,14 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         # K20: the spans (buckets) and percentiles (q = p * 1000) of the rw stream, likewise
         "rw_buckets": recent["buckets"] if recent else [],
         "rw_pcts": recent["percentiles"] if recent else [],
+        # K21: the class tables of the sb stream ([T, q] per class), its rules (span in buckets and
+        # f = factor * 1000) and minSamples, likewise
+        "sb_classes": sb_classes,
+        "sb_services": sb_services,
+        "sb_default": sb_default,
+        "sb_short": [k for k, _f in burn["rules"]] if burn else [],
+        "sb_factor": [f for _k, f in burn["rules"]] if burn else [],
+        "sb_min_samples": burn["minSamples"] if burn else 1,
     }
     # intervalLengthInSeconds only scales the TPM divisor: the bucket label is endTs without its
     # last 4 digits whatever the interval (stream_calc_stats.js:89-96, :186), as here
@@ -240,6 +256,7 @@ class APMEngine:
         # K20: a span is at most windowSizeInIntervals when the engine is constructed (a later reload
         # may shorten the window: the span then reads the whole window)
         check_recent_windows(recent_windows(cfg), int(cfg["streamCalcStats"]["windowSizeInIntervals"]))
+        check_slo_burn(slo_burn(cfg), int(cfg["streamCalcStats"]["windowSizeInIntervals"]))  # K21: likewise
         self.N = _native.load()
         # the engine's zone (tz, else gpu.timezone as read now) and the time its transition table is
         # centred on (the wall clock at construction).  Both are kept: the zone is not applied live,
@@ -263,7 +280,7 @@ class APMEngine:
     @classmethod
     def restart_required(cls, old: Dict[str, Any], new: Dict[str, Any]) -> List[str]:
         """The engine settings that differ between two engine_config results and are not applied
-        live (win_pcts, the slo_* tables, the tk_* settings, svc_pcts, rw_buckets, rw_pcts, ...)."""
+        live (win_pcts, the slo_* tables, the tk_* settings, svc_pcts, rw_buckets, rw_pcts, the sb_* settings, ...)."""
         return sorted(k for k in new if k not in cls.LIVE_KEYS and k not in ("outputs", "tz_table")
                       and new[k] != old.get(k))
 

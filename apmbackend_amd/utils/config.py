@@ -98,6 +98,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "svcQueue": "service_window",     # amqp mode: the queue the sv records go to
     "recentWindows": None,            # K20 "rw" stream: exact stats of the newest window buckets, {"buckets": [1, 6], "percentiles": [50, 95, 99]} (docs/RECENT.md)
     "recentQueue": "recent_window",   # amqp mode: the queue the rw records go to
+    "sloBurn": None,                  # K21 "sb" stream: multi-window SLO burn-rate breaches, {"default": {"threshold": 2000, "target": 99}, "services": {...}, "rules": [{"short": 1, "factor": 14.4}], "minSamples": 20} (docs/BURN.md)
+    "burnQueue": "slo_burn",          # amqp mode: the queue the sb records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -332,6 +334,138 @@ def check_recent_windows(rw: Optional[Dict[str, List[int]]], window: int) -> Non
                          f"got {rw['buckets'][-1]}")
 
 
+BURN_MAX_RULES = 4          # kernel_api.h SB_MAX_RULES
+BURN_Q_SCALE = 100000       # target_q = target * 1000; the error budget is b = 100000 - q
+BURN_F_MAX = 1000000        # factor * 1000
+
+
+def _burn_decimal(where: str, p: Any, lo: int, hi: int) -> int:
+    """A decimal with at most three places as the integer ``p * 1000`` in lo .. hi, read from its
+    text the way parse_window_percentiles reads a percentile (never through float arithmetic)."""
+    if isinstance(p, bool) or not isinstance(p, (int, float, str, decimal.Decimal)):
+        raise ValueError(f"gpu.sloBurn: {where}: {p!r} is not a number")
+    try:
+        d = decimal.Decimal(repr(p) if isinstance(p, float) else str(p).strip())
+    except decimal.InvalidOperation:
+        raise ValueError(f"gpu.sloBurn: {where}: {p!r} is not a number") from None
+    if not d.is_finite():
+        raise ValueError(f"gpu.sloBurn: {where}: {p!r} is not finite")
+    q = d * 1000
+    if q != q.to_integral_value():
+        raise ValueError(f"gpu.sloBurn: {where}: {p!r} has more than three decimals")
+    q = int(q)
+    if not lo <= q <= hi:
+        raise ValueError(f"gpu.sloBurn: {where}: {p!r} is outside {lo / 1000:g} .. {hi / 1000:g}")
+    return q
+
+
+def _parse_burn_objective(where: str, v: Any) -> Optional[Tuple[int, int]]:
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.sloBurn: {where} must be an object with 'threshold' and 'target' (or null), got {v!r}")
+    extra = set(v) - {"threshold", "target"}
+    if extra:
+        raise ValueError(f"gpu.sloBurn: {where}: unknown key(s) {sorted(extra, key=str)!r}")
+    if "threshold" not in v or "target" not in v:
+        raise ValueError(f"gpu.sloBurn: {where} needs both 'threshold' and 'target', got {v!r}")
+    t = v["threshold"]
+    if isinstance(t, bool) or not isinstance(t, int):
+        raise ValueError(f"gpu.sloBurn: {where}: threshold {t!r} is not an integer")
+    if not 0 <= t <= SLO_T_MAX:
+        raise ValueError(f"gpu.sloBurn: {where}: threshold {t!r} is outside 0 .. {SLO_T_MAX}")
+    return int(t), _burn_decimal(f"{where}: target", v["target"], 1, BURN_Q_SCALE - 1)
+
+
+def parse_slo_burn(v: Any) -> Optional[Dict[str, Any]]:
+    """gpu.sloBurn -> {"default": (T, q) | None, "services": {name: (T, q) | None},
+    "rules": [(short, f), ...], "minSamples": n}.  An objective is a JSON integer ``threshold`` in
+    0 .. 2147483647 (bool, float and str are rejected) and a ``target`` percentage with at most three
+    decimals, q = target * 1000 in 1 .. 99999; ``default`` may be absent or null, a service named
+    with null gets no rows.  ``rules``: 1 to 4 objects {"short": k, "factor": x}, ``short`` a JSON
+    integer >= 1, strictly ascending (its bound against the window is the engine's,
+    check_slo_burn), ``factor`` a decimal with at most three places, f = factor * 1000 in
+    1 .. 1000000.  ``minSamples``: a JSON integer >= 1 (default 1).  None, or an object in which no
+    service has an objective -> None (stream off); anything else raises ValueError."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.sloBurn: an object with 'default' and / or 'services', and 'rules', got {v!r}")
+    extra = set(v) - {"default", "services", "rules", "minSamples"}
+    if extra:
+        raise ValueError(f"gpu.sloBurn: unknown key(s) {sorted(extra, key=str)!r}")
+    default = _parse_burn_objective("default", v.get("default"))
+    services = v.get("services")
+    if services is None:
+        services = {}
+    if not isinstance(services, dict):
+        raise ValueError(f"gpu.sloBurn: services must be an object, got {services!r}")
+    named: Dict[str, Optional[Tuple[int, int]]] = {}
+    for name, o in services.items():
+        if not isinstance(name, str):
+            raise ValueError(f"gpu.sloBurn: service name {name!r} is not a string")
+        named[name] = _parse_burn_objective(f"services[{name!r}]", o)
+    rules = v.get("rules")
+    if not isinstance(rules, list) or not 1 <= len(rules) <= BURN_MAX_RULES:
+        raise ValueError(f"gpu.sloBurn: rules must list 1 to {BURN_MAX_RULES} rules, got {rules!r}")
+    out_rules: List[Tuple[int, int]] = []
+    for i, r in enumerate(rules):
+        if not isinstance(r, dict):
+            raise ValueError(f"gpu.sloBurn: rules[{i}] must be an object with 'short' and 'factor', got {r!r}")
+        extra = set(r) - {"short", "factor"}
+        if extra:
+            raise ValueError(f"gpu.sloBurn: rules[{i}]: unknown key(s) {sorted(extra, key=str)!r}")
+        if "short" not in r or "factor" not in r:
+            raise ValueError(f"gpu.sloBurn: rules[{i}] needs both 'short' and 'factor', got {r!r}")
+        k = r["short"]
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1 or k > 0x7fffffff:
+            raise ValueError(f"gpu.sloBurn: rules[{i}]: short must be an integer >= 1, got {k!r}")
+        if out_rules and k <= out_rules[-1][0]:
+            raise ValueError(f"gpu.sloBurn: rules[{i}]: short {k!r} does not ascend strictly")
+        out_rules.append((int(k), _burn_decimal(f"rules[{i}]: factor", r["factor"], 1, BURN_F_MAX)))
+    ms = v.get("minSamples", 1)
+    if isinstance(ms, bool) or not isinstance(ms, int) or ms < 1 or ms > 0x7fffffff:
+        raise ValueError(f"gpu.sloBurn: minSamples must be an integer >= 1, got {ms!r}")
+    if default is None and not any(o is not None for o in named.values()):
+        return None
+    return {"default": default, "services": named, "rules": out_rules, "minSamples": int(ms)}
+
+
+def slo_burn(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """The validated gpu.sloBurn object of a config (None: off)."""
+    return parse_slo_burn(gpu_opt(cfg, "sloBurn"))
+
+
+def check_slo_burn(sb: Optional[Dict[str, Any]], window: int) -> None:
+    """The bound an engine puts on the rules' spans when it is constructed: at most
+    windowSizeInIntervals (as check_recent_windows)."""
+    if sb and sb["rules"][-1][0] > int(window):
+        raise ValueError(f"gpu.sloBurn.rules: short at most windowSizeInIntervals ({int(window)}), "
+                         f"got {sb['rules'][-1][0]}")
+
+
+def burn_tables(sb: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[str, int], int]:
+    """(classes, service -> class, default class) as the engine takes them, by sl's scheme
+    (slo_tables): class 0 is "no row" (an empty list), class 1 the default objective [T, q] when
+    there is one, then one class per named service with an objective, in config order; a service
+    named with null maps to class 0."""
+    if not sb:
+        return [], {}, 0
+    classes: List[List[int]] = [[]]
+    default_class = 0
+    if sb["default"] is not None:
+        classes.append(list(sb["default"]))
+        default_class = 1
+    services: Dict[str, int] = {}
+    for name, o in sb["services"].items():
+        if o is not None:
+            classes.append(list(o))
+            services[name] = len(classes) - 1
+        else:
+            services[name] = 0
+    return classes, services, default_class
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -373,6 +507,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         parse_service_window(merged["serviceWindow"])  # likewise
     if "recentWindows" in merged:
         parse_recent_windows(merged["recentWindows"])  # likewise
+    if "sloBurn" in merged:
+        parse_slo_burn(merged["sloBurn"])  # likewise
     return cfg
 
 

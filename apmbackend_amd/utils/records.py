@@ -545,6 +545,60 @@ class RecentWindowEntry:
                 "pcts": {pct_text(q): (v // 2 if v % 2 == 0 else v / 2) for q, v in self.pcts}}
 
 
+# ---- sb: SLO burn-rate breaches (docs/BURN.md).  Integers only.
+BURN_MAX_RULES = 4
+
+
+def burn_rules_from_text(text: Optional[str]) -> Optional[List[tuple]]:
+    """``k:f:m:bad:fired,...`` -> [(k, f, m, bad, fired)], 1 to 4 groups of five plain decimals of 1
+    to 10 digits, the last 0 or 1; None: malformed (copyenc.cpp holds the same rules)."""
+    groups = (text or "").split(",")
+    if not text or len(groups) > BURN_MAX_RULES:
+        return None
+    out = []
+    for g in groups:
+        parts = g.split(":")
+        if len(parts) != 5:
+            return None
+        vals = [_svc_int(p) for p in parts]
+        if any(v is None for v in vals) or parts[4] not in ("0", "1"):
+            return None
+        out.append(tuple(vals))
+    return out
+
+
+@dataclass
+class SloBurnEntry:
+    """``sb|ts|server|service|T|q|m|bad|nan|k:f:m_k:bad_k:fired,...`` -- at a rollover, a series
+    whose K8 window and whose newest ``k`` buckets both burn the error budget of its objective
+    (``threshold`` T, ``target_q`` = target * 1000) at least ``f`` / 1000 times as fast as the
+    objective allows, for at least one rule: ``count`` non-NaN window samples, ``bad`` of them above
+    T, ``nan`` others; ``rules`` holds (k, f, m_k, bad_k, fired) per configured rule (no reference
+    counterpart)."""
+    timestamp: Num
+    server: str
+    service: str
+    threshold: int
+    target_q: int
+    count: int
+    bad: int
+    nan: int
+    rules: List[tuple]
+    type: str = "sb"
+
+    def to_csv(self) -> str:
+        groups = ",".join(f"{int(k)}:{int(f)}:{int(m)}:{int(b)}:{1 if fired else 0}" for k, f, m, b, fired in self.rules)
+        return (f"sb|{js_str(self.timestamp)}|{self.server}|{self.service}|{int(self.threshold)}|{int(self.target_q)}|"
+                f"{int(self.count)}|{int(self.bad)}|{int(self.nan)}|{groups}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "threshold": int(self.threshold), "target_q": int(self.target_q), "count": int(self.count),
+                "bad": int(self.bad), "nan": int(self.nan),
+                "rules": [{"k": int(k), "f": int(f), "m": int(m), "bad": int(b), "fired": bool(fired)}
+                          for k, f, m, b, fired in self.rules]}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -633,7 +687,14 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
             if q is not None and s2 is not None:  # (a malformed pair is dropped, likewise)
                 pcts.append((q, s2))
         return RecentWindowEntry(parse_int(a[1]), a[2], a[3], k, cnt, nan, tot, pcts)
+    if t == "sb":
+        a = _pad(arr, 10)
+        nums = [_svc_int(x) for x in a[4:9]]
+        rules = burn_rules_from_text(a[9])
+        if any(v is None for v in nums) or rules is None:  # (a malformed row is dropped, as copyenc.cpp does)
+            return None
+        return SloBurnEntry(parse_int(a[1]), a[2], a[3], *nums, rules)
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb")
