@@ -13,6 +13,7 @@
 
 #include "kernels/burncmp.h"
 #include "kernels/kernel_api.h"
+#include "kernels/trafficcmp.h"
 #include "runtime/engine.h"
 #include "runtime/format.h"
 #include "runtime/jsutil.h"
@@ -192,6 +193,38 @@ EngineConfig config_from(const py::dict& d) {
     if (ms < 1 || ms > 0x7fffffff) throw std::invalid_argument("sb_min_samples: an integer >= 1");
     c.sb_min_samples = (int32_t)ms;
   }
+  if (d.contains("tf_classes")) {  // K22 (the constructor checks the tables and rules when the tf stream is on)
+    c.tf_classes = d["tf_classes"].cast<std::vector<std::vector<int64_t>>>();
+    if (d.contains("tf_services")) c.tf_services = d["tf_services"].cast<std::map<std::string, int32_t>>();
+    c.tf_default = get<int32_t>(d, "tf_default", 0);
+  }
+  if (d.contains("tf_short")) {
+    const auto list = [&](const char* key) {
+      return d.contains(key) ? d[key].cast<std::vector<int64_t>>() : std::vector<int64_t>();
+    };
+    const auto k = list("tf_short"), dr = list("tf_drop"), su = list("tf_surge"), z = list("tf_z");
+    if (k.size() > 4 || dr.size() != k.size() || su.size() != k.size() || z.size() != k.size())
+      throw std::invalid_argument("tf_short / tf_drop / tf_surge / tf_z: at most 4 rules, one value of each per span");
+    c.n_tf_rules = (int32_t)k.size();
+    for (size_t i = 0; i < k.size(); ++i) {
+      if (k[i] < 1 || k[i] > 64 || (i && k[i] <= k[i - 1]))
+        throw std::invalid_argument("tf_short: strictly ascending integers in 1 .. 64");
+      if (dr[i] < 0 || dr[i] > 999) throw std::invalid_argument("tf_drop: integers in 1 .. 999 (drop * 1000), 0 for none");
+      if (su[i] != 0 && (su[i] < 1001 || su[i] > 1000000))
+        throw std::invalid_argument("tf_surge: integers in 1001 .. 1000000 (surge * 1000), 0 for none");
+      if (dr[i] == 0 && su[i] == 0) throw std::invalid_argument("tf_drop / tf_surge: a rule needs at least one of them");
+      if (z[i] < 0 || z[i] > 100000) throw std::invalid_argument("tf_z: integers in 0 .. 100000 (z * 1000)");
+      c.tf_short[i] = (int32_t)k[i];
+      c.tf_drop[i] = (int32_t)dr[i];
+      c.tf_surge[i] = (int32_t)su[i];
+      c.tf_z[i] = (int32_t)z[i];
+    }
+  }
+  if (d.contains("tf_min_buckets")) {
+    const int64_t mb = d["tf_min_buckets"].cast<int64_t>();
+    if (mb < 3 || mb > 0x7fffffff) throw std::invalid_argument("tf_min_buckets: an integer >= 3");
+    c.tf_min_buckets = (int32_t)mb;
+  }
   if (d.contains("tk_k") && !d["tk_k"].is_none()) {  // (the constructor checks them when the tk stream is on)
     c.tk_k = d["tk_k"].cast<int32_t>();
     if (d.contains("tk_by")) c.tk_by = d["tk_by"].cast<std::vector<int32_t>>();
@@ -247,6 +280,7 @@ py::dict metrics_dict(const EngineMetrics& m) {
   d["t_stats_tx_ms"] = m.t_stats_tx_ms; d["t_rollover_ms"] = m.t_rollover_ms;
   d["t_format_ms"] = m.t_format_ms; d["t_release_ms"] = m.t_release_ms;
   d["sb_rows"] = m.sb_rows;
+  d["tf_rows"] = m.tf_rows;
   d["formatted_bytes"] = m.formatted_bytes; d["lockstep_rollovers"] = m.lockstep_rollovers; d["format_fallbacks"] = m.format_fallbacks;
   d["t_parse_ms"] = m.t_parse_ms; d["t_join_ms"] = m.t_join_ms; d["t_stats_ms"] = m.t_stats_ms;
   d["t_total_ms"] = m.t_total_ms;
@@ -709,6 +743,26 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("traffic", [](Engine& e) {
+        // per series id of the last rollover's K22 value pass: None for a series without an st row or
+        // a class, else (n, [(B, R, med2, mad4, verdict "D" / "S" / "N") per configured rule])
+        std::vector<TrafficRec> rec;
+        std::vector<uint8_t> has;
+        e.download_traffic(rec, has);
+        const int nr = e.tf_nrule();
+        py::list out;
+        for (size_t s = 0; s < has.size(); ++s) {
+          if (!has[s]) { out.append(py::none()); continue; }
+          const TrafficRec& r = rec[s];
+          py::list rules;
+          for (int j = 0; j < nr; ++j) {
+            const int v = (r.verdict >> (2 * j)) & 3;
+            rules.append(py::make_tuple(r.B[j], r.R[j], r.med2[j], r.mad4[j], v == TF_D ? "D" : v == TF_S ? "S" : "N"));
+          }
+          out.append(py::make_tuple(r.n, rules));
+        }
+        return out;
+      })
       .def("leaderboard", [](Engine& e) {
         // the last rollover's K18 records: (board, rank, series id, tpm, avg, p75, p95), raw doubles
         std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> rows;
@@ -767,15 +821,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[12];
-    int64_t counts[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::string out[13];
+    int64_t counts[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[12] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb"};
-    for (int k = 0; k < 12; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[13] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf"};
+    for (int k = 0; k < 13; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -985,6 +1039,28 @@ PYBIND11_MODULE(_apm_native, m) {
       throw std::invalid_argument("burn_fires: bad, m in 0 .. 2147483647, b in 1 .. 99999, f in 1 .. 1000000, min_samples >= 1");
     return burn_fires((uint32_t)bad, (uint32_t)mm, (uint32_t)b, (uint32_t)f, (uint32_t)min_samples);
   }, py::arg("bad"), py::arg("m"), py::arg("b"), py::arg("f"), py::arg("min_samples"));
+  // tf traffic (traffic.hip): the window length up to which the value pass sorts in registers and the
+  // longest it takes at all, the series per block of that path (tests bracket them), and the exact
+  // verdict the kernels decide a rule with (trafficcmp.h, the same routine compiled for the host):
+  // "D", "S" or "N" from the recent samples R, twice the median, four times the MAD, the baseline
+  // buckets B and the clipped span kk
+  m.def("traffic_group_win", []() { return apm_traffic_group_win(); });
+  m.def("traffic_max_win", []() { return apm_traffic_max_win(); });
+  m.def("traffic_tile", []() { return apm_traffic_tile(); });
+  m.def("traffic_verdict", [](int64_t R, int64_t med2, int64_t mad4, int64_t B, int64_t kk, int64_t r_d, int64_t r_s,
+                              int64_t z, int64_t min_rate, int64_t min_buckets) {
+    // (the bounds trafficcmp.h's width argument rests on: R < 2^37, med2 < 2^32, mad4 <= 2^33)
+    if (R < 0 || R > 64 * (int64_t)0x7fffffff || med2 < 0 || med2 > 2 * (int64_t)0x7fffffff || mad4 < 0 ||
+        mad4 > ((int64_t)1 << 33) || B < 0 || B > 0x7fffffff || kk < 1 || kk > 64 || r_d < 0 || r_d > 999 ||
+        (r_s != 0 && (r_s < 1001 || r_s > 1000000)) || z < 0 || z > 100000 || min_rate < 1 || min_rate > 0x7fffffff ||
+        min_buckets < 0 || min_buckets > 0x7fffffff)
+      throw std::invalid_argument("traffic_verdict: R in 0 .. 64 (2^31 - 1), med2 in 0 .. 2^32 - 2, mad4 in 0 .. 2^33, kk in "
+                                  "1 .. 64, r_d in 0 .. 999, r_s 0 or in 1001 .. 1000000, z in 0 .. 100000, min_rate >= 1");
+    const int v = traffic_verdict(R, med2, mad4, (int32_t)B, (int32_t)kk, (int32_t)r_d, (int32_t)r_s, (int32_t)z,
+                                  (int32_t)min_rate, (int32_t)min_buckets);
+    return std::string(v == TF_D ? "D" : v == TF_S ? "S" : "N");
+  }, py::arg("R"), py::arg("med2"), py::arg("mad4"), py::arg("B"), py::arg("kk"), py::arg("r_d"), py::arg("r_s"),
+     py::arg("z"), py::arg("min_rate"), py::arg("min_buckets"));
   m.def("apm_topk_tile", []() { return apm_topk_tile(); });
   m.def("apm_topk_final_span", []() { return apm_topk_final_span(); });
   m.def("topk_select", [](const std::vector<std::tuple<double, double, double, double, int32_t>>& win_rows,

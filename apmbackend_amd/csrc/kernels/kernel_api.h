@@ -411,6 +411,53 @@ struct BurnTextArgs {
   uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
   char* out;                    // at least apm_burn_row_bound(max name bytes) * n bytes
 };
+// K22 tf rows: traffic drops and surges decided on the device (traffic.hip, docs/TRAFFIC.md).  A
+// class is one gate minRate (samples per bucket); class 0 is "no row".  Over the per-bucket counts
+// of the window K8 just read (the same WindowArgs; counts[slot][s] only, an absent bucket counts 0)
+// the value pass finds, per rule j, the samples R of the newest k' = min(span[j], n_win) buckets and
+// twice the median / four times the MAD of the other B = n_win - k' buckets' counts, decides the
+// rule with traffic_verdict (trafficcmp.h) and writes one record per series; the text pass prints,
+// per emission position of a series with a verdict other than N:
+//   tf|<edge ts>|server|service|<n>|<minRate>|<k>:<B>:<R>:<med2>:<mad4>:<D|S|N>,...
+constexpr int TF_MAX_RULES = 4;
+struct TrafficRec {
+  int32_t n;                    // WinStat.n of the series (= the sum of its window's counts)
+  uint32_t R[TF_MAX_RULES];     // per rule: samples of the recent span (at most n, so 32 bits hold it)
+  uint32_t med2[TF_MAX_RULES];  // ... twice the median of the baseline buckets' counts
+  int32_t B[TF_MAX_RULES];      // ... the baseline buckets
+  int32_t verdict;              // bits 2j, 2j + 1: rule j's verdict (TF_N / TF_D / TF_S)
+  uint64_t mad4[TF_MAX_RULES];  // ... four times the median absolute deviation (below 2^34)
+};
+struct TrafficArgs {
+  WindowArgs w;                 // K8's arguments of this rollover (w.out = K8's result)
+  const int32_t* cls;           // [S] class per series (0 or out of range: no row)
+  const int32_t* rate;          // [n_classes] minRate (class 0: unused)
+  int32_t n_classes;
+  int32_t nrule;                // 1 .. TF_MAX_RULES
+  int32_t span[TF_MAX_RULES];   // buckets per rule, strictly ascending, 1 .. 64
+  int32_t drop[TF_MAX_RULES];   // r_d = drop * 1000, 1 .. 999 (0: no drop test)
+  int32_t surge[TF_MAX_RULES];  // r_s = surge * 1000, 1001 .. 1000000 (0: no surge test)
+  int32_t z[TF_MAX_RULES];      // z * 1000, 0 .. 100000
+  int32_t min_buckets;          // >= 3
+  TrafficRec* rec;              // [S]
+};
+struct TrafficTextArgs {
+  const TrafficRec* rec;        // [S]
+  const int32_t* cls;           // [S]
+  const int32_t* rate;          // [n_classes]
+  int32_t n_classes;
+  const int32_t* perm;          // [n] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;
+  int32_t n_series;
+  int32_t nrule;
+  int32_t span[TF_MAX_RULES];
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_traffic_row_bound(max name bytes) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -586,6 +633,21 @@ void apm_burn_values(apm::BurnArgs* a, hipStream_t stream);
 // length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_burn_plan(apm::BurnTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_burn_write(apm::BurnTextArgs* a, hipStream_t stream);
+// traffic.hip
+// the value pass' two paths (tests bracket them): a window of at most apm_traffic_group_win()
+// buckets is sorted in registers, 64 series (apm_traffic_tile()) a block; a longer one, up to
+// apm_traffic_max_win() buckets, is ranked by counting
+int32_t apm_traffic_group_win();
+int32_t apm_traffic_max_win();
+int32_t apm_traffic_tile();
+size_t apm_traffic_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes
+size_t apm_traffic_row_bound(size_t name_bytes);
+// 0, or -1 when the window is longer than apm_traffic_max_win() (nothing launched)
+int apm_traffic_values(apm::TrafficArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_traffic_plan(apm::TrafficTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_traffic_write(apm::TrafficTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

@@ -267,8 +267,8 @@ void append_pct_pairs(std::string& js, std::string_view rest) {
   }
 }
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw, 11 sb) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[12]*/) {
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw, 11 sb, 12 tf) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[13]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -541,6 +541,60 @@ int encode_line(std::string_view line, std::string* out /*[12]*/) {
     copy_escape(o, js);
     o += '\n';
     return 11;
+  }
+  if (t == "tf") {  // traffic: timestamp, server, service, count, min_rate, rules json
+    // (utils/records.py entry_from_csv and traffic_rules_from_text hold the same rules) a row whose n
+    // or minRate is not 1 to 10 plain digits, or whose last field is not 1 to 4 groups
+    // k:B:R:med2:mad4:V of such numbers with V one of D, S, N, is dropped whole
+    for (int i = 4; i <= 5; ++i)
+      if (!a.has(i) || !all_digits(a.f[i], 10)) return -1;
+    if (!a.has(6) || a.f[6].empty()) return -1;
+    std::string js = "[";
+    {
+      static const char* key[6] = {"{\"k\":", ",\"buckets\":", ",\"recent\":", ",\"med2\":", ",\"mad4\":", ",\"verdict\":"};
+      std::string_view rest = a.f[6];
+      int groups = 0;
+      for (;;) {
+        const size_t e = rest.find(',');
+        std::string_view g = rest.substr(0, e);
+        if (++groups > 4) return -1;
+        if (groups > 1) js += ',';
+        for (int p = 0; p < 6; ++p) {
+          const size_t c = g.find(':');
+          if ((p < 5) == (c == std::string_view::npos)) return -1;  // (exactly six parts)
+          const std::string_view part = g.substr(0, c);
+          js += key[p];
+          if (p == 5) {
+            if (part != "D" && part != "S" && part != "N") return -1;
+            js += '"';
+            js += part;
+            js += '"';
+          } else {
+            if (!all_digits(part, 10)) return -1;
+            int64_t v = 0;
+            for (char ch : part) v = v * 10 + (ch - '0');
+            append_i64(js, v);
+            g = g.substr(c + 1);
+          }
+        }
+        js += '}';
+        if (e == std::string_view::npos) break;
+        rest = rest.substr(e + 1);
+      }
+    }
+    js += ']';
+    std::string& o = out[12];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    for (int i = 4; i <= 5; ++i) {
+      int64_t v = 0;
+      for (char ch : a.f[i]) v = v * 10 + (ch - '0');
+      append_i64(o, v); o += '\t';
+    }
+    copy_escape(o, js);
+    o += '\n';
+    return 12;
   }
   if (t == "jx") {
     std::string& o = out[3];

@@ -283,6 +283,30 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
                                   "2147483647, q in 1 .. 99999}, every class index must name one; sb_short must hold 1 to 4 "
                                   "strictly ascending spans in 1 .. window, sb_factor factors in 1 .. 1000000, sb_min_samples >= 1");
   }
+  if (want(OUT_TF)) {  // K22: likewise
+    const auto& cl = cfg_.tf_classes;
+    bool ok = cl.size() >= 2 && cl[0].empty() && cl.size() <= (size_t)cfg_.max_series + 2;
+    for (size_t c = 1; ok && c < cl.size(); ++c) ok = cl[c].size() == 1 && cl[c][0] >= 1 && cl[c][0] <= INT32_MAX;
+    const auto in_range = [&](int32_t c) { return c >= 0 && (size_t)c < cl.size(); };
+    ok = ok && in_range(cfg_.tf_default);
+    for (const auto& kv : cfg_.tf_services) ok = ok && in_range(kv.second);
+    const int nr = cfg_.n_tf_rules;
+    ok = ok && nr >= 1 && nr <= TF_MAX_RULES && cfg_.tf_min_buckets >= 3;
+    for (int j = 0; ok && j < nr; ++j) {
+      const int32_t d = cfg_.tf_drop[j], u = cfg_.tf_surge[j];
+      ok = cfg_.tf_short[j] >= 1 && cfg_.tf_short[j] <= std::min(64, cfg_.window) &&
+           (j == 0 || cfg_.tf_short[j] > cfg_.tf_short[j - 1]) && (d == 0 || (d >= 1 && d <= 999)) &&
+           (u == 0 || (u >= 1001 && u <= 1000000)) && (d != 0 || u != 0) && cfg_.tf_z[j] >= 0 && cfg_.tf_z[j] <= 100000;
+    }
+    if (!ok)
+      throw std::invalid_argument("tf stream: tf_classes must hold the empty class 0 and at least one gate {minRate in 1 .. "
+                                  "2147483647}, every class index must name one; tf_short must hold 1 to 4 strictly ascending "
+                                  "spans in 1 .. min(64, window), tf_drop 0 or 1 .. 999, tf_surge 0 or 1001 .. 1000000 (not "
+                                  "both 0), tf_z 0 .. 100000, tf_min_buckets >= 3");
+    if (cfg_.window + 1 > apm_traffic_max_win())
+      throw std::invalid_argument("tf stream: a window of more than " + std::to_string(apm_traffic_max_win() - 1) +
+                                  " intervals is not supported");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -522,6 +546,20 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_sb_rec_ = (BurnRec*)res_.dmalloc((size_t)S * sizeof(BurnRec));
     text_alloc(sb_, OUT_SB, apm_burn_tmp_bytes(S));
   }
+  if (want(OUT_TF)) {  // K22
+    const int32_t C = (int32_t)cfg_.tf_classes.size();  // (checked at the top of the constructor)
+    n_tf_classes_ = C;
+    d_tf_rate_ = (int32_t*)res_.dmalloc((size_t)C * 4);
+    {
+      std::vector<int32_t> tab((size_t)C, 0);
+      for (int32_t c = 1; c < C; ++c) tab[(size_t)c] = (int32_t)cfg_.tf_classes[c][0];
+      HIP_OK(hipMemcpy(d_tf_rate_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    }
+    d_tf_cls_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    HIP_OK(hipMemset(d_tf_cls_, 0, (size_t)S * 4));  // class 0 until a series' class is uploaded
+    d_tf_rec_ = (TrafficRec*)res_.dmalloc((size_t)S * sizeof(TrafficRec));
+    text_alloc(tf_, OUT_TF, apm_traffic_tmp_bytes(S));
+  }
   if (want(OUT_LH)) text_alloc(lh_, OUT_LH, apm_hist_tmp_bytes(S));  // K15
   {
     const char* f = std::getenv("APM_TXCOPY_FORCE_FALLBACK");
@@ -755,6 +793,7 @@ int32_t Engine::series_for(int32_t server, int32_t service) {
   h_hard_max_.push_back(cfg_.hard_max_ms);
   if (want(OUT_SL)) h_slo_cls_.push_back(slo_class_of(s));  // (uploaded with the hard max)
   if (want(OUT_SB)) h_sb_cls_.push_back(burn_class_of(s));  // K21: likewise
+  if (want(OUT_TF)) h_tf_cls_.push_back(traffic_class_of(s));  // K22: likewise
   h_suppressed_.push_back(0);
   zscore_seen_.push_back(0);
   h_active_.push_back(0);
@@ -793,6 +832,12 @@ int32_t Engine::slo_class_of(int32_t s) const {
 int32_t Engine::burn_class_of(int32_t s) const {
   auto it = cfg_.sb_services.find(dict_.service_name(series_[s].service));
   return it != cfg_.sb_services.end() ? it->second : cfg_.sb_default;
+}
+
+// K22: the same rule over the tf stream's own tables
+int32_t Engine::traffic_class_of(int32_t s) const {
+  auto it = cfg_.tf_services.find(dict_.service_name(series_[s].service));
+  return it != cfg_.tf_services.end() ? it->second : cfg_.tf_default;
 }
 
 void Engine::refresh_series_settings() {
@@ -837,6 +882,7 @@ void Engine::upload_series_tables(int32_t lo) {
   stage_done();
   if (want(OUT_SL)) upload_slo_classes(lo);
   if (want(OUT_SB)) upload_burn_classes(lo);
+  if (want(OUT_TF)) upload_traffic_classes(lo);
 }
 
 // K17: the classes of series [lo, n) to the device, on the stats stream.  A full upload (lo == 0: a
@@ -877,6 +923,25 @@ void Engine::upload_burn_classes(int32_t lo) {
     stage_done();
   }
   sb_cls_uploaded_ = n;
+}
+
+// K22: upload_slo_classes over the tf stream's own class array
+void Engine::upload_traffic_classes(int32_t lo) {
+  const int32_t n = n_series_;
+  lo = std::min(lo, tf_cls_uploaded_);  // (series no earlier upload carried go along)
+  if (lo == 0 || h_tf_cls_.size() != (size_t)n) {
+    h_tf_cls_.resize((size_t)n);
+    for (int32_t s = 0; s < n; ++s) h_tf_cls_[s] = traffic_class_of(s);
+    lo = 0;
+  }
+  if (n > lo) {
+    const size_t mc = (size_t)(n - lo);
+    int32_t* cs = (int32_t*)stage(mc * 4);
+    std::memcpy(cs, h_tf_cls_.data() + lo, mc * 4);
+    h2d(d_tf_cls_ + lo, cs, mc * 4, stream_);
+    stage_done();
+  }
+  tf_cls_uploaded_ = n;
 }
 
 std::vector<uint64_t> Engine::cache_stats(bool drain) {
@@ -1559,6 +1624,8 @@ void Engine::flush() {
     formatted_bytes_lane_ = 0;
     metrics_.sb_rows += sb_rows_lane_;
     sb_rows_lane_ = 0;
+    metrics_.tf_rows += tf_rows_lane_;
+    tf_rows_lane_ = 0;
     if (!out_error_.empty()) { std::string e = out_error_; out_error_.clear(); throw std::runtime_error(e); }
   }
   if (!st_error_.empty()) { std::string e = st_error_; st_error_.clear(); throw std::runtime_error(e); }
@@ -2502,6 +2569,8 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   // K21: last of all, for the same reason: it reads what K17 reads (window cells, counts, spill
   // lists, d_win_) and its own class array, and the next append follows on this stream.
   if (want(OUT_SB)) burn_rollover(wa, edge_ts);
+  // K22: after it, for the same reason: it reads the window's counts, d_win_ and its own class array.
+  if (want(OUT_TF)) traffic_rollover(wa, edge_ts);
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2656,8 +2725,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[12];
-        int64_t counts[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::string enc[13];
+        int64_t counts[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3079,7 +3148,7 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   });
 }
 
-// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb): buffers and the slot protocol, once.
+// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb, tf): buffers and the slot protocol, once.
 // `rows`: text lanes per series (rw prints one row per span).
 void Engine::text_alloc(TextStream& t, int kind, size_t tmp_bytes, int rows) {
   const size_t S = (size_t)cfg_.max_series;
@@ -3122,6 +3191,12 @@ void Engine::text_end(TextStream& t, int32_t n) {
       const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
       std::lock_guard<std::mutex> g(out_mu_);
       sb_rows_lane_ += rows;
+    }
+    if (ts->kind == OUT_TF) {  // (likewise)
+      const char* p = ts->text[k];
+      const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
+      std::lock_guard<std::mutex> g(out_mu_);
+      tf_rows_lane_ += rows;
     }
     emit_bytes(ts->kind, ts->text[k], total);
   });
@@ -3567,6 +3642,72 @@ void Engine::download_burns(std::vector<BurnRec>& rec, std::vector<uint8_t>& has
     has[(size_t)s] = win[(size_t)s].active && cls[(size_t)s] > 0 && cls[(size_t)s] < n_sb_classes_;
 }
 
+// ---- K22: tf rows.  Per st row whose service has a minRate and for which a traffic rule says drop
+// or surge, one row, in st order with the st rows' timestamp: value pass over the counts of K8's
+// window (the rules are decided on the device), then count / scan / write of the text -- the
+// length pass is the compaction, only the rows' bytes reach the host.
+void Engine::traffic_rollover(const WindowArgs& wa, int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();
+  // (series whose settings no upload_series_tables() carried yet: as slo_rollover)
+  if (tf_cls_uploaded_ < n) upload_traffic_classes(tf_cls_uploaded_);
+  const int nr = cfg_.n_tf_rules;
+  TrafficArgs va{};
+  va.w = wa;
+  va.cls = d_tf_cls_;
+  va.rate = d_tf_rate_;
+  va.n_classes = n_tf_classes_;
+  va.nrule = nr;
+  for (int j = 0; j < nr; ++j) {
+    va.span[j] = cfg_.tf_short[j];
+    va.drop[j] = cfg_.tf_drop[j];
+    va.surge[j] = cfg_.tf_surge[j];
+    va.z[j] = cfg_.tf_z[j];
+  }
+  va.min_buckets = cfg_.tf_min_buckets;
+  va.rec = d_tf_rec_;
+  // (the constructor and stage_reconfig keep the window inside the value pass' bound)
+  if (apm_traffic_values(&va, stream_) != 0) throw std::runtime_error("tf stream: window too long");
+  tf_last_n_ = n;
+  TrafficTextArgs ta{};
+  ta.rec = d_tf_rec_;
+  ta.cls = d_tf_cls_;
+  ta.rate = d_tf_rate_;
+  ta.n_classes = n_tf_classes_;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n;
+  ta.n_series = n;
+  ta.nrule = nr;
+  for (int j = 0; j < nr; ++j) ta.span[j] = cfg_.tf_short[j];
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  ta.len = tf_.len;
+  ta.off = tf_.off;
+  // the output bound needs no length pass: every row is at most apm_traffic_row_bound bytes
+  ta.out = text_begin(tf_, (size_t)n * apm_traffic_row_bound(max_name_len_) + 64);
+  if (apm_traffic_plan(&ta, tf_.tmp, tf_.tmp_bytes, stream_) != 0) throw std::runtime_error("traffic scan failed");
+  apm_traffic_write(&ta, stream_);
+  text_end(tf_, n);
+}
+
+void Engine::download_traffic(std::vector<TrafficRec>& rec, std::vector<uint8_t>& has) {
+  rec.clear(); has.clear();
+  const int32_t n = tf_last_n_;
+  if (!want(OUT_TF) || n == 0) return;
+  rec.resize((size_t)n);
+  std::vector<WinStat> win((size_t)n);
+  std::vector<int32_t> cls((size_t)n);
+  HIP_OK(hipMemcpyAsync(rec.data(), d_tf_rec_, rec.size() * sizeof(TrafficRec), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(win.data(), d_win_, win.size() * sizeof(WinStat), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(cls.data(), d_tf_cls_, cls.size() * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  has.resize((size_t)n);
+  for (int32_t s = 0; s < n; ++s)
+    has[(size_t)s] = win[(size_t)s].active && cls[(size_t)s] > 0 && cls[(size_t)s] < n_tf_classes_;
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3707,7 +3848,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf"};
   return n[k];
 }
 

@@ -45,6 +45,12 @@ void Engine::stage_reconfig(const ReconfigSpec& spec) {
   if (spec.n_lags < 1 || spec.n_lags > MAX_LAGS)
     throw std::runtime_error("reconfigure: 1.." + std::to_string(MAX_LAGS) + " LAG settings");
   check_window(spec.window, spec.buffer, spec.interval_len);
+  // K22: the tf value pass takes windows up to apm_traffic_max_win() buckets (the constructor's
+  // bound): a reload past it is refused here, whole, and not found at the next rollover
+  if (want(OUT_TF) && spec.window + 1 > apm_traffic_max_win())
+    throw std::invalid_argument("reconfigure: the tf stream takes a window of at most " +
+                                std::to_string(apm_traffic_max_win() - 1) + " intervals (got " +
+                                std::to_string(spec.window) + "); not applied");
   for (int l = 0; l < spec.n_lags; ++l)
     if (spec.lags[l] < 1) throw std::runtime_error("reconfigure: LAG must be >= 1");
   std::lock_guard<std::mutex> g(rc_mu_);

@@ -22,15 +22,16 @@ from __future__ import annotations
 
 import math
 import re
+import statistics
 from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import (as_bool, check_recent_windows, check_slo_burn, gpu_opt, slo_burn, latency_objectives, leaderboard, recent_windows,
-                            service_window,
+from ..utils.config import (as_bool, check_recent_windows, check_slo_burn, check_traffic_watch, gpu_opt, slo_burn,
+                            latency_objectives, leaderboard, recent_windows, service_window, traffic_watch,
                             window_percentiles, zscore_lag_settings)
 from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, RecentWindowEntry,
-                             ServiceWindowEntry, SloBurnEntry,
+                             ServiceWindowEntry, SloBurnEntry, TrafficEntry,
                              StatEntry, TxEntry, WindowPctEntry, WindowSloEntry, entry_from_csv, hist_bin, hist_lower,
                              pct_ranks)
 from ..utils.timeparse import TzOffset, convert_string_date_to_ms, default_tz
@@ -678,7 +679,10 @@ class StatsOracle:
                  emit_svc: Optional[Callable[[str], None]] = None, svc_percentiles: Iterable[int] = (),
                  emit_recent: Optional[Callable[[str], None]] = None, recent_buckets: Iterable[int] = (),
                  recent_percentiles: Iterable[int] = (),
-                 emit_burn: Optional[Callable[[str], None]] = None, burn: Optional[Dict[str, Any]] = None):
+                 emit_burn: Optional[Callable[[str], None]] = None, burn: Optional[Dict[str, Any]] = None,
+                 emit_traffic: Optional[Callable[[str], None]] = None, traffic: Optional[Dict[str, Any]] = None):
+        self.emit_traffic = emit_traffic  # tf rows (docs/TRAFFIC.md); None = stream off
+        self.traffic = traffic            # config.parse_traffic_watch's result
         self.emit_burn = emit_burn  # sb rows (docs/BURN.md); None = stream off
         self.burn = burn            # config.parse_slo_burn's result
         self.emit_recent = emit_recent  # rw rows (docs/RECENT.md); None = stream off
@@ -889,6 +893,45 @@ class StatsOracle:
             return None
         return SloBurnEntry(edge_ts, server, service, T, q, m, bad, nan, rules).to_csv()
 
+    @staticmethod
+    def traffic_rule(counts: List[int], k: int, r_d: int, r_s: int, z: int, min_rate: int,
+                     min_buckets: int) -> Tuple[int, int, int, int, str]:
+        """(B, R, med2, mad4, verdict) of one rule over the per-bucket counts of a window, oldest
+        first: the newest min(k, len) buckets against the median / MAD of the others, in integers
+        (docs/TRAFFIC.md)."""
+        kk = min(k, len(counts))
+        base = counts[:len(counts) - kk]
+        B = len(base)
+        R = sum(counts[B:])
+        med2 = mad4 = 0
+        if B:
+            med2 = statistics.median_low(base) + statistics.median_high(base)
+            dev = [abs(2 * c - med2) for c in base]
+            mad4 = statistics.median_low(dev) + statistics.median_high(dev)
+        verdict = "N"
+        if B >= min_buckets and med2 >= 2 * min_rate:
+            if r_d and 2000 * R <= r_d * kk * med2 and 4000 * R <= kk * (2000 * med2 - z * mad4):
+                verdict = "D"
+            elif r_s and 2000 * R >= r_s * kk * med2 and 4000 * R >= kk * (2000 * med2 + z * mad4):
+                verdict = "S"
+        return B, R, med2, mad4, verdict
+
+    def traffic_row(self, edge_ts: int, server: str, service: str, svc: Dict[int, List[int]]) -> Optional[str]:
+        """The tf row of one series with an st row: None unless its service has a minRate and at least
+        one rule says D or S.  A bucket's count is its stored samples, NaN ones included; an absent
+        bucket counts 0."""
+        named = self.traffic["services"]
+        min_rate = named[service] if service in named else self.traffic["default"]  # (named with null: no row)
+        if min_rate is None:
+            return None
+        newest = self.latest - self.buffer
+        counts = [len(svc.get(b, ())) for b in range(self.latest - self.keep, newest + 1)]
+        rules = [(k,) + self.traffic_rule(counts, k, r_d, r_s, z, min_rate, self.traffic["minBuckets"])
+                 for k, r_d, r_s, z in self.traffic["rules"]]
+        if all(r[5] == "N" for r in rules):
+            return None
+        return TrafficEntry(edge_ts, server, service, sum(counts), min_rate, rules).to_csv()
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -944,6 +987,10 @@ class StatsOracle:
                     row = self.burn_row(edge_ts, server, service, svc)
                     if row is not None:
                         self.emit_burn(row)
+                if self.emit_traffic is not None:
+                    row = self.traffic_row(edge_ts, server, service, svc)
+                    if row is not None:
+                        self.emit_traffic(row)
         if self.emit_top is not None:
             for row in self.top_rows(st_rows):
                 self.emit_top(row)
@@ -1183,6 +1230,7 @@ class PipelineOracle:
         self.sv: List[str] = []
         self.rw: List[str] = []
         self.sb: List[str] = []
+        self.tf: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1192,6 +1240,7 @@ class PipelineOracle:
         # shorten the window later, and the span then reads the whole window)
         check_recent_windows(recent_windows(cfg), int(sc["windowSizeInIntervals"]))
         check_slo_burn(slo_burn(cfg), int(sc["windowSizeInIntervals"]))  # (likewise)
+        check_traffic_watch(traffic_watch(cfg), int(sc["windowSizeInIntervals"]))  # (likewise)
         self.st = StatsOracle(self._on_st, self.tx_db.append, int(sc["intervalLengthInSeconds"]),
                               int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
                               emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None,
@@ -1206,7 +1255,8 @@ class PipelineOracle:
                               emit_recent=self.rw.append if recent_windows(cfg) else None,
                               recent_buckets=(recent_windows(cfg) or {}).get("buckets", ()),
                               recent_percentiles=(recent_windows(cfg) or {}).get("percentiles", ()),
-                              emit_burn=self.emit_burn if slo_burn(cfg) else None, burn=slo_burn(cfg))
+                              emit_burn=self.emit_burn if slo_burn(cfg) else None, burn=slo_burn(cfg),
+                              emit_traffic=self.tf.append if traffic_watch(cfg) else None, traffic=traffic_watch(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

@@ -22,8 +22,9 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 from .. import _native
 from ..models.oracle import file_kind, server_of
 from ..ops.parse_ref import tz_table
-from ..utils.config import (LEADERBOARD_KEYS, burn_tables, check_recent_windows, check_slo_burn, latency_objectives,
-                            leaderboard, recent_windows, service_window, slo_burn, slo_tables, window_percentiles)
+from ..utils.config import (LEADERBOARD_KEYS, burn_tables, check_recent_windows, check_slo_burn, check_traffic_watch,
+                            latency_objectives, leaderboard, recent_windows, service_window, slo_burn, slo_tables,
+                            traffic_tables, traffic_watch, window_percentiles)
 from ..utils.timeparse import TzOffset
 
 log = logging.getLogger("apm.pipeline")
@@ -47,12 +48,15 @@ DEVICE_OUT_KINDS = NATIVE_OUT_KINDS + ("sv",)
 # ... and tests/test_svcwin_model.py pins DEVICE_OUT_KINDS and its last element; STREAM_OUT_KINDS is
 # engine.h's OutKind up to rw.
 STREAM_OUT_KINDS = DEVICE_OUT_KINDS + ("rw",)
-# ... and tests/test_recent_*.py pin STREAM_OUT_KINDS; FULL_OUT_KINDS is engine.h's OutKind in full and
-# the tuple a stream's bit index comes from.
+# ... and tests/test_recent_*.py pin STREAM_OUT_KINDS; FULL_OUT_KINDS is engine.h's OutKind up to sb.
 FULL_OUT_KINDS = STREAM_OUT_KINDS + ("sb",)
+# ... and tests/test_burn_*.py pin FULL_OUT_KINDS; EVERY_OUT_KINDS is engine.h's OutKind in full and
+# the tuple a stream's bit index comes from.
+EVERY_OUT_KINDS = FULL_OUT_KINDS + ("tf",)
 # keep_text=True materialises these; lh (K15 latency histograms), wp (K16 window percentiles),
 # sl (K17 threshold counts), tk (K18 leaderboards), sv (K19 per-service window stats), rw (K20
-# stats of the newest window buckets) and sb (K21 SLO burn-rate breaches) are opt-in through `outputs` only
+# stats of the newest window buckets), sb (K21 SLO burn-rate breaches) and tf (K22 traffic drops and
+# surges) are opt-in through `outputs` only
 KEEP_TEXT_KINDS = tuple(k for k in OUT_KINDS if k != "lh")
 # What the reference persists (db_insert queue): released + audit tx, fs, al.  `transactions`
 # and `st` are internal hand-offs that only the AMQP bridge needs.
@@ -63,14 +67,14 @@ MAX_LAGS = 16  # apm_types.h MAX_LAGS: LAG capacity per engine (each LAG is an H
 def output_mask(kinds) -> int:
     m = 0
     for k in kinds:
-        m |= 1 << FULL_OUT_KINDS.index(k)
+        m |= 1 << EVERY_OUT_KINDS.index(k)
     return m
 
 
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
                   tz: Optional[TzOffset] = None, tz_centre_ms: Optional[int] = None, **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
-    materialises every stream but the opt-in lh / wp / sl / tk / sv / rw / sb; `outputs` (iterable of FULL_OUT_KINDS) selects explicitly.
+    materialises every stream but the opt-in lh / wp / sl / tk / sv / rw / sb / tf; `outputs` (iterable of EVERY_OUT_KINDS) selects explicitly.
     The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
     existed, `outputs` was ignored under keep_text).  "wp" takes its percentiles from
     gpu.windowPercentiles (ValueError when the list is missing or malformed), "sl" its thresholds
@@ -78,7 +82,8 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
     from gpu.serviceWindow (likewise), "rw" its spans and percentiles from gpu.recentWindows (likewise; the
     bound of a span against windowSizeInIntervals is checked where an engine is constructed, not here: a
     reload reads the settings through this function too), "sb" its objectives and rules from gpu.sloBurn
-    (likewise, the bound of a rule's span included).  `tz` (a TzOffset) stands in for gpu.timezone; the zone's
+    (likewise, the bound of a rule's span included), "tf" its classes and rules from gpu.trafficWatch
+    (likewise).  `tz` (a TzOffset) stands in for gpu.timezone; the zone's
     transition table is centred on `tz_centre_ms` (default: the wall clock now, see
     ops.parse_ref.tz_table)."""
     g = cfg.get("gpu", {})
@@ -101,6 +106,10 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
     if "sb" in (outputs or ()) and not burn:
         raise ValueError('outputs names "sb" but gpu.sloBurn is not set')
     sb_classes, sb_services, sb_default = burn_tables(burn)
+    traffic = traffic_watch(cfg)
+    if "tf" in (outputs or ()) and not traffic:
+        raise ValueError('outputs names "tf" but gpu.trafficWatch is not set')
+    tf_classes, tf_services, tf_default = traffic_tables(traffic)
     # (the spans' bound against the window holds at construction only -- APMEngine.__init__ and the
     # native constructor: a reload may shorten the window below a span, which then reads all of it)
     zc = cfg["streamCalcZScore"]
@@ -194,6 +203,16 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         "sb_short": [k for k, _f in burn["rules"]] if burn else [],
         "sb_factor": [f for _k, f in burn["rules"]] if burn else [],
         "sb_min_samples": burn["minSamples"] if burn else 1,
+        # K22: the class tables of the tf stream ([minRate] per class), its rules (span in buckets,
+        # r_d = drop * 1000 or 0, r_s = surge * 1000 or 0, z * 1000) and minBuckets, likewise
+        "tf_classes": tf_classes,
+        "tf_services": tf_services,
+        "tf_default": tf_default,
+        "tf_short": [r[0] for r in traffic["rules"]] if traffic else [],
+        "tf_drop": [r[1] for r in traffic["rules"]] if traffic else [],
+        "tf_surge": [r[2] for r in traffic["rules"]] if traffic else [],
+        "tf_z": [r[3] for r in traffic["rules"]] if traffic else [],
+        "tf_min_buckets": traffic["minBuckets"] if traffic else 8,
     }
     # intervalLengthInSeconds only scales the TPM divisor: the bucket label is endTs without its
     # last 4 digits whatever the interval (stream_calc_stats.js:89-96, :186), as here
@@ -257,6 +276,7 @@ class APMEngine:
         # may shorten the window: the span then reads the whole window)
         check_recent_windows(recent_windows(cfg), int(cfg["streamCalcStats"]["windowSizeInIntervals"]))
         check_slo_burn(slo_burn(cfg), int(cfg["streamCalcStats"]["windowSizeInIntervals"]))  # K21: likewise
+        check_traffic_watch(traffic_watch(cfg), int(cfg["streamCalcStats"]["windowSizeInIntervals"]))  # K22: likewise
         self.N = _native.load()
         # the engine's zone (tz, else gpu.timezone as read now) and the time its transition table is
         # centred on (the wall clock at construction).  Both are kept: the zone is not applied live,
@@ -280,7 +300,7 @@ class APMEngine:
     @classmethod
     def restart_required(cls, old: Dict[str, Any], new: Dict[str, Any]) -> List[str]:
         """The engine settings that differ between two engine_config results and are not applied
-        live (win_pcts, the slo_* tables, the tk_* settings, svc_pcts, rw_buckets, rw_pcts, the sb_* settings, ...)."""
+        live (win_pcts, the slo_* tables, the tk_* settings, svc_pcts, rw_buckets, rw_pcts, the sb_* and tf_* settings, ...)."""
         return sorted(k for k in new if k not in cls.LIVE_KEYS and k not in ("outputs", "tz_table")
                       and new[k] != old.get(k))
 

@@ -68,12 +68,14 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
     "rw": ("dbRecentTable", ["timestamp", "server", "service", "buckets", "count", "nan", "elapsed_sum", "pcts"]),
     # SLO burn-rate breaches (sb records, gpu.sloBurn): likewise
     "sb": ("dbBurnTable", ["timestamp", "server", "service", "threshold", "target_q", "count", "bad", "nan", "rules"]),
+    # traffic drops and surges (tf records, gpu.trafficWatch): likewise
+    "tf": ("dbTrafficTable", ["timestamp", "server", "service", "count", "min_rate", "rules"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf")
 # tables of the record types the reference does not know (its config has no key for them)
 DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct", "sl": "apm_window_slo",
                   "tk": "apm_leaderboard", "sv": "apm_service_window", "rw": "apm_recent_window",
-                  "sb": "apm_slo_burn"}
+                  "sb": "apm_slo_burn", "tf": "apm_traffic"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -161,7 +163,7 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
         elif c in ("stats", "entry", "bins", "pcts", "le", "rules"):
             out[c] = json.loads(v)
-        elif c in ("servers", "buckets", "elapsed_sum", "threshold", "target_q", "bad"):  # (sv, rw, sb: plain integers; the sum may pass 2^53)
+        elif c in ("servers", "buckets", "elapsed_sum", "threshold", "target_q", "bad", "min_rate"):  # (sv, rw, sb: plain integers; the sum may pass 2^53)
             out[c] = int(v)
         elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan", "rank", "average", "per75", "per95") or rtype == "jx" and c not in ("server",):
             f = float(v)

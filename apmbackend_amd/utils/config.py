@@ -100,6 +100,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "recentQueue": "recent_window",   # amqp mode: the queue the rw records go to
     "sloBurn": None,                  # K21 "sb" stream: multi-window SLO burn-rate breaches, {"default": {"threshold": 2000, "target": 99}, "services": {...}, "rules": [{"short": 1, "factor": 14.4}], "minSamples": 20} (docs/BURN.md)
     "burnQueue": "slo_burn",          # amqp mode: the queue the sb records go to
+    "trafficWatch": None,             # K22 "tf" stream: traffic drops and surges against the window's median / MAD baseline, {"default": {"minRate": 5}, "services": {...}, "rules": [{"short": 1, "drop": 0.1, "z": 4}], "minBuckets": 8} (docs/TRAFFIC.md)
+    "trafficQueue": "traffic",        # amqp mode: the queue the tf records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -466,6 +468,142 @@ def burn_tables(sb: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[str
     return classes, services, default_class
 
 
+TRAFFIC_MAX_RULES = 4       # kernel_api.h TF_MAX_RULES
+TRAFFIC_SHORT_MAX = 64      # buckets of a rule's recent span (the bound the 64-bit products rest on)
+TRAFFIC_Z_DEFAULT = 3000    # z * 1000
+
+
+def _traffic_decimal(where: str, p: Any, lo: int, hi: int) -> int:
+    """A decimal with at most three places as the integer ``p * 1000`` in lo .. hi, read from its
+    text (never through float arithmetic), as _burn_decimal."""
+    if isinstance(p, bool) or not isinstance(p, (int, float, str, decimal.Decimal)):
+        raise ValueError(f"gpu.trafficWatch: {where}: {p!r} is not a number")
+    try:
+        d = decimal.Decimal(repr(p) if isinstance(p, float) else str(p).strip())
+    except decimal.InvalidOperation:
+        raise ValueError(f"gpu.trafficWatch: {where}: {p!r} is not a number") from None
+    if not d.is_finite():
+        raise ValueError(f"gpu.trafficWatch: {where}: {p!r} is not finite")
+    q = d * 1000
+    if q != q.to_integral_value():
+        raise ValueError(f"gpu.trafficWatch: {where}: {p!r} has more than three decimals")
+    q = int(q)
+    if not lo <= q <= hi:
+        raise ValueError(f"gpu.trafficWatch: {where}: {p!r} is outside {lo / 1000:g} .. {hi / 1000:g}")
+    return q
+
+
+def _parse_traffic_class(where: str, v: Any) -> Optional[int]:
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.trafficWatch: {where} must be an object with 'minRate' (or null), got {v!r}")
+    extra = set(v) - {"minRate"}
+    if extra:
+        raise ValueError(f"gpu.trafficWatch: {where}: unknown key(s) {sorted(extra, key=str)!r}")
+    if "minRate" not in v:
+        raise ValueError(f"gpu.trafficWatch: {where} needs 'minRate', got {v!r}")
+    r = v["minRate"]
+    if isinstance(r, bool) or not isinstance(r, int):
+        raise ValueError(f"gpu.trafficWatch: {where}: minRate {r!r} is not an integer")
+    if not 1 <= r <= SLO_T_MAX:
+        raise ValueError(f"gpu.trafficWatch: {where}: minRate {r!r} is outside 1 .. {SLO_T_MAX}")
+    return int(r)
+
+
+def parse_traffic_watch(v: Any) -> Optional[Dict[str, Any]]:
+    """gpu.trafficWatch -> {"default": minRate | None, "services": {name: minRate | None},
+    "rules": [(short, r_d, r_s, z), ...], "minBuckets": n}.  ``minRate`` is a JSON integer in
+    1 .. 2147483647 (bool, float and str are rejected); ``default`` may be absent or null, a service
+    named with null gets no rows.  ``rules``: 1 to 4 objects {"short": k, "drop": x, "surge": y,
+    "z": w}, ``short`` a JSON integer in 1 .. 64, strictly ascending (its bound against the window is
+    the engine's, check_traffic_watch); ``drop`` a decimal with at most three places, r_d = drop *
+    1000 in 1 .. 999; ``surge`` likewise, r_s = surge * 1000 in 1001 .. 1000000; at least one of the
+    two (the missing one is 0 in the result); ``z`` likewise, z * 1000 in 0 .. 100000, default 3.
+    ``minBuckets``: a JSON integer >= 3 (default 8).  None, or an object in which no service has a
+    minRate -> None (stream off); anything else raises ValueError."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.trafficWatch: an object with 'default' and / or 'services', and 'rules', got {v!r}")
+    extra = set(v) - {"default", "services", "rules", "minBuckets"}
+    if extra:
+        raise ValueError(f"gpu.trafficWatch: unknown key(s) {sorted(extra, key=str)!r}")
+    default = _parse_traffic_class("default", v.get("default"))
+    services = v.get("services")
+    if services is None:
+        services = {}
+    if not isinstance(services, dict):
+        raise ValueError(f"gpu.trafficWatch: services must be an object, got {services!r}")
+    named: Dict[str, Optional[int]] = {}
+    for name, o in services.items():
+        if not isinstance(name, str):
+            raise ValueError(f"gpu.trafficWatch: service name {name!r} is not a string")
+        named[name] = _parse_traffic_class(f"services[{name!r}]", o)
+    rules = v.get("rules")
+    if not isinstance(rules, list) or not 1 <= len(rules) <= TRAFFIC_MAX_RULES:
+        raise ValueError(f"gpu.trafficWatch: rules must list 1 to {TRAFFIC_MAX_RULES} rules, got {rules!r}")
+    out_rules: List[Tuple[int, int, int, int]] = []
+    for i, r in enumerate(rules):
+        if not isinstance(r, dict):
+            raise ValueError(f"gpu.trafficWatch: rules[{i}] must be an object with 'short' and 'drop' and / or 'surge', got {r!r}")
+        extra = set(r) - {"short", "drop", "surge", "z"}
+        if extra:
+            raise ValueError(f"gpu.trafficWatch: rules[{i}]: unknown key(s) {sorted(extra, key=str)!r}")
+        if "short" not in r or ("drop" not in r and "surge" not in r):
+            raise ValueError(f"gpu.trafficWatch: rules[{i}] needs 'short' and at least one of 'drop' and 'surge', got {r!r}")
+        k = r["short"]
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= TRAFFIC_SHORT_MAX:
+            raise ValueError(f"gpu.trafficWatch: rules[{i}]: short must be an integer in 1 .. {TRAFFIC_SHORT_MAX}, got {k!r}")
+        if out_rules and k <= out_rules[-1][0]:
+            raise ValueError(f"gpu.trafficWatch: rules[{i}]: short {k!r} does not ascend strictly")
+        rd = _traffic_decimal(f"rules[{i}]: drop", r["drop"], 1, 999) if "drop" in r else 0
+        rs = _traffic_decimal(f"rules[{i}]: surge", r["surge"], 1001, 1000000) if "surge" in r else 0
+        z = _traffic_decimal(f"rules[{i}]: z", r["z"], 0, 100000) if "z" in r else TRAFFIC_Z_DEFAULT
+        out_rules.append((int(k), rd, rs, z))
+    mb = v.get("minBuckets", 8)
+    if isinstance(mb, bool) or not isinstance(mb, int) or mb < 3 or mb > 0x7fffffff:
+        raise ValueError(f"gpu.trafficWatch: minBuckets must be an integer >= 3, got {mb!r}")
+    if default is None and not any(o is not None for o in named.values()):
+        return None
+    return {"default": default, "services": named, "rules": out_rules, "minBuckets": int(mb)}
+
+
+def traffic_watch(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """The validated gpu.trafficWatch object of a config (None: off)."""
+    return parse_traffic_watch(gpu_opt(cfg, "trafficWatch"))
+
+
+def check_traffic_watch(tf: Optional[Dict[str, Any]], window: int) -> None:
+    """The bound an engine puts on the rules' spans when it is constructed: at most
+    windowSizeInIntervals (as check_slo_burn)."""
+    if tf and tf["rules"][-1][0] > int(window):
+        raise ValueError(f"gpu.trafficWatch.rules: short at most windowSizeInIntervals ({int(window)}), "
+                         f"got {tf['rules'][-1][0]}")
+
+
+def traffic_tables(tf: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[str, int], int]:
+    """(classes, service -> class, default class) as the engine takes them, by sl's scheme
+    (burn_tables): class 0 is "no row" (an empty list), class 1 the default [minRate] when there is
+    one, then one class per named service with a minRate, in config order; a service named with
+    null maps to class 0."""
+    if not tf:
+        return [], {}, 0
+    classes: List[List[int]] = [[]]
+    default_class = 0
+    if tf["default"] is not None:
+        classes.append([tf["default"]])
+        default_class = 1
+    services: Dict[str, int] = {}
+    for name, o in tf["services"].items():
+        if o is not None:
+            classes.append([o])
+            services[name] = len(classes) - 1
+        else:
+            services[name] = 0
+    return classes, services, default_class
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -509,6 +647,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         parse_recent_windows(merged["recentWindows"])  # likewise
     if "sloBurn" in merged:
         parse_slo_burn(merged["sloBurn"])  # likewise
+    if "trafficWatch" in merged:
+        parse_traffic_watch(merged["trafficWatch"])  # likewise
     return cfg
 
 

@@ -599,6 +599,56 @@ class SloBurnEntry:
                           for k, f, m, b, fired in self.rules]}
 
 
+# ---- tf: traffic drops and surges (docs/TRAFFIC.md).  Integers only.
+TRAFFIC_MAX_RULES = 4
+
+
+def traffic_rules_from_text(text: Optional[str]) -> Optional[List[tuple]]:
+    """``k:B:R:med2:mad4:V,...`` -> [(k, B, R, med2, mad4, V)], 1 to 4 groups of five plain decimals
+    of 1 to 10 digits and a verdict D, S or N; None: malformed (copyenc.cpp holds the same rules)."""
+    groups = (text or "").split(",")
+    if not text or len(groups) > TRAFFIC_MAX_RULES:
+        return None
+    out = []
+    for g in groups:
+        parts = g.split(":")
+        if len(parts) != 6 or parts[5] not in ("D", "S", "N"):
+            return None
+        vals = [_svc_int(p) for p in parts[:5]]
+        if any(v is None for v in vals):
+            return None
+        out.append(tuple(vals) + (parts[5],))
+    return out
+
+
+@dataclass
+class TrafficEntry:
+    """``tf|ts|server|service|n|minRate|k:B:R:med2:mad4:V,...`` -- at a rollover, a series whose
+    newest ``k`` window buckets hold far fewer (``D``) or far more (``S``) samples than the other
+    ``B`` buckets of its K8 window, for at least one rule: ``count`` is the window's samples,
+    ``min_rate`` the class' gate; ``rules`` holds (k, B, R, med2, mad4, verdict) per configured rule,
+    R the samples of the newest buckets, med2 twice the median and mad4 four times the median absolute
+    deviation of the baseline buckets' counts (no reference counterpart)."""
+    timestamp: Num
+    server: str
+    service: str
+    count: int
+    min_rate: int
+    rules: List[tuple]
+    type: str = "tf"
+
+    def to_csv(self) -> str:
+        groups = ",".join(f"{int(k)}:{int(b)}:{int(r)}:{int(m2)}:{int(m4)}:{v}" for k, b, r, m2, m4, v in self.rules)
+        return (f"tf|{js_str(self.timestamp)}|{self.server}|{self.service}|{int(self.count)}|{int(self.min_rate)}|"
+                f"{groups}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "count": int(self.count), "min_rate": int(self.min_rate),
+                "rules": [{"k": int(k), "buckets": int(b), "recent": int(r), "med2": int(m2), "mad4": int(m4),
+                           "verdict": v} for k, b, r, m2, m4, v in self.rules]}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -694,7 +744,14 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
         if any(v is None for v in nums) or rules is None:  # (a malformed row is dropped, as copyenc.cpp does)
             return None
         return SloBurnEntry(parse_int(a[1]), a[2], a[3], *nums, rules)
+    if t == "tf":
+        a = _pad(arr, 7)
+        nums = [_svc_int(x) for x in a[4:6]]
+        rules = traffic_rules_from_text(a[6])
+        if any(v is None for v in nums) or rules is None:  # (a malformed row is dropped, as copyenc.cpp does)
+            return None
+        return TrafficEntry(parse_int(a[1]), a[2], a[3], *nums, rules)
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf")
