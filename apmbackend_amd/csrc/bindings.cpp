@@ -13,6 +13,7 @@
 
 #include "kernels/burncmp.h"
 #include "kernels/kernel_api.h"
+#include "kernels/peercmp.h"
 #include "kernels/trafficcmp.h"
 #include "runtime/engine.h"
 #include "runtime/format.h"
@@ -225,6 +226,26 @@ EngineConfig config_from(const py::dict& d) {
     if (mb < 3 || mb > 0x7fffffff) throw std::invalid_argument("tf_min_buckets: an integer >= 3");
     c.tf_min_buckets = (int32_t)mb;
   }
+  if (d.contains("po_classes")) {  // K23 (the constructor checks the tables and settings when the po stream is on)
+    c.po_classes = d["po_classes"].cast<std::vector<std::vector<int64_t>>>();
+    if (d.contains("po_services")) c.po_services = d["po_services"].cast<std::map<std::string, int32_t>>();
+    c.po_default = get<int32_t>(d, "po_default", 0);
+  }
+  {
+    const auto num = [&](const char* key, int64_t lo, int64_t hi, int64_t also, int32_t& dst, const char* what) {
+      if (!d.contains(key)) return;
+      const int64_t v = d[key].cast<int64_t>();
+      if (v != also && (v < lo || v > hi)) throw std::invalid_argument(std::string(key) + ": " + what);
+      dst = (int32_t)v;
+    };
+    num("po_pct", 1, 100000, 0, c.po_pct, "a percentile * 1000 in 1 .. 100000");
+    num("po_high", 1001, 1000000, 0, c.po_high, "an integer in 1001 .. 1000000 (high * 1000), 0 for none");
+    num("po_low", 1, 999, 0, c.po_low, "an integer in 1 .. 999 (low * 1000), 0 for none");
+    num("po_z", 0, 100000, 0, c.po_z, "an integer in 0 .. 100000 (z * 1000)");
+    num("po_min_delta", 0, 0x7fffffff, 0, c.po_min_delta, "an integer in 0 .. 2147483647");
+    num("po_min_peers", 3, 0x7fffffff, 3, c.po_min_peers, "an integer >= 3");
+    num("po_min_samples", 1, 0x7fffffff, 1, c.po_min_samples, "an integer in 1 .. 2147483647");
+  }
   if (d.contains("tk_k") && !d["tk_k"].is_none()) {  // (the constructor checks them when the tk stream is on)
     c.tk_k = d["tk_k"].cast<int32_t>();
     if (d.contains("tk_by")) c.tk_by = d["tk_by"].cast<std::vector<int32_t>>();
@@ -281,6 +302,7 @@ py::dict metrics_dict(const EngineMetrics& m) {
   d["t_format_ms"] = m.t_format_ms; d["t_release_ms"] = m.t_release_ms;
   d["sb_rows"] = m.sb_rows;
   d["tf_rows"] = m.tf_rows;
+  d["po_rows"] = m.po_rows;
   d["formatted_bytes"] = m.formatted_bytes; d["lockstep_rollovers"] = m.lockstep_rollovers; d["format_fallbacks"] = m.format_fallbacks;
   d["t_parse_ms"] = m.t_parse_ms; d["t_join_ms"] = m.t_join_ms; d["t_stats_ms"] = m.t_stats_ms;
   d["t_total_ms"] = m.t_total_ms;
@@ -763,6 +785,19 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("peers", [](Engine& e) {
+        // per series id of the last rollover's K23 value pass: None for a series without an st row,
+        // with class 0 or below minSamples, else (m, x, E, X2, D4, verdict "H" / "L" / "N")
+        std::vector<PeerRec> rec;
+        e.download_peers(rec);
+        py::list out;
+        for (const PeerRec& r : rec) {
+          if (r.m == 0) { out.append(py::none()); continue; }
+          out.append(py::make_tuple(r.m, (int64_t)r.x, r.E, (int64_t)r.X2, (int64_t)r.D4,
+                                    r.verdict == PO_H ? "H" : r.verdict == PO_L ? "L" : "N"));
+        }
+        return out;
+      })
       .def("leaderboard", [](Engine& e) {
         // the last rollover's K18 records: (board, rank, series id, tpm, avg, p75, p95), raw doubles
         std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> rows;
@@ -821,15 +856,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[13];
-    int64_t counts[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::string out[14];
+    int64_t counts[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[13] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf"};
-    for (int k = 0; k < 13; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[14] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po"};
+    for (int k = 0; k < 14; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -1061,6 +1096,24 @@ PYBIND11_MODULE(_apm_native, m) {
     return std::string(v == TF_D ? "D" : v == TF_S ? "S" : "N");
   }, py::arg("R"), py::arg("med2"), py::arg("mad4"), py::arg("B"), py::arg("kk"), py::arg("r_d"), py::arg("r_s"),
      py::arg("z"), py::arg("min_rate"), py::arg("min_buckets"));
+  // po peers (peers.hip): the members up to which a group is ranked by 32 lanes in registers (tests
+  // bracket it; larger groups take the block pass), and the exact verdict the kernels decide a
+  // member with (peercmp.h, the same routine compiled for the host): "H", "L" or "N"
+  m.def("peer_group_max", []() { return apm_peer_group_max(); });
+  m.def("peer_verdict", [](int64_t x, int64_t X2, int64_t D4, int64_t E, int64_t r_h, int64_t r_l, int64_t z,
+                           int64_t min_value, int64_t min_delta, int64_t min_peers) {
+    // (the bounds peercmp.h's width argument rests on: |x| < 2^32, |X2| < 2^33, D4 < 2^36)
+    const int64_t b32 = (int64_t)1 << 32;
+    if (x <= -b32 || x >= b32 || X2 <= -2 * b32 || X2 >= 2 * b32 || D4 < 0 || D4 >= 16 * b32 || E < 0 || E > 0x7fffffff ||
+        (r_h != 0 && (r_h < 1001 || r_h > 1000000)) || r_l < 0 || r_l > 999 || z < 0 || z > 100000 || min_value < 1 ||
+        min_value > 0x7fffffff || min_delta < 0 || min_delta > 0x7fffffff || min_peers < 0 || min_peers > 0x7fffffff)
+      throw std::invalid_argument("peer_verdict: |x| < 2^32, |X2| < 2^33, D4 in 0 .. 2^36 - 1, r_h 0 or in 1001 .. 1000000, "
+                                  "r_l in 0 .. 999, z in 0 .. 100000, min_value >= 1, min_delta >= 0");
+    const int v = peer_verdict(x, X2, D4, (int32_t)E, (int32_t)r_h, (int32_t)r_l, (int32_t)z, (int32_t)min_value,
+                               (int32_t)min_delta, (int32_t)min_peers);
+    return std::string(v == PO_H ? "H" : v == PO_L ? "L" : "N");
+  }, py::arg("x"), py::arg("X2"), py::arg("D4"), py::arg("E"), py::arg("r_h"), py::arg("r_l"), py::arg("z"),
+     py::arg("min_value"), py::arg("min_delta"), py::arg("min_peers"));
   m.def("apm_topk_tile", []() { return apm_topk_tile(); });
   m.def("apm_topk_final_span", []() { return apm_topk_final_span(); });
   m.def("topk_select", [](const std::vector<std::tuple<double, double, double, double, int32_t>>& win_rows,

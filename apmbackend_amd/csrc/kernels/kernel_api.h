@@ -458,6 +458,59 @@ struct TrafficTextArgs {
   uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
   char* out;                    // at least apm_traffic_row_bound(max name bytes) * n bytes
 };
+// K23 po rows: peer-outlier servers per service, decided on the device (peers.hip, docs/PEERS.md).
+// The unit of work is K19's group: the series of one service (the same CSR).  A class is one gate
+// minValue (ms); class 0 is "no row".  Stage A is K16's value pass with one percentile into po's own
+// buffers (sum2 = x, m).  A member is eligible when it is active, has a class and m >= min_samples;
+// over the E eligible members' x the value pass finds X2 = x_lo + x_hi and D4 = d_lo + d_hi of
+// d_i = |2 x_i - X2| by counting ranks, decides every eligible member with peer_verdict
+// (peercmp.h) and writes one record per series; the text pass prints, per emission position of a
+// series with a verdict other than N:
+//   po|<edge ts>|server|service|<m>|<p>:<x>|<E>|<X2>|<D4>|<H|L>
+struct PeerRec {
+  int32_t m;                    // finite samples of the series' window (0: no record)
+  int32_t verdict;              // PO_N / PO_H / PO_L
+  int32_t E;                    // eligible members of the series' group
+  int32_t pad;
+  long long x;                  // |x| < 2^32
+  long long X2;                 // |X2| < 2^33
+  long long D4;                 // 0 <= D4 < 2^36
+};
+struct PeerArgs {
+  const uint8_t* active;        // [S] the series has an st row at this rollover
+  const long long* sum2;        // [S] stage A: x per series (defined where m >= 1)
+  const int32_t* m;             // [S] stage A: finite samples
+  const int32_t* cls;           // [S] class per series (0 or out of range: no row)
+  const int32_t* val;           // [n_classes] minValue (class 0: unused)
+  int32_t n_classes;
+  int32_t n_series;
+  int32_t n_groups;
+  const int32_t* grp_off;       // [n_groups + 1]
+  const int32_t* grp_mem;       // [n_series] member series, group by group, each in emission order
+  int32_t r_h;                  // high * 1000, 1001 .. 1000000 (0: no H test)
+  int32_t r_l;                  // low * 1000, 1 .. 999 (0: no L test)
+  int32_t z;                    // z * 1000, 0 .. 100000
+  int32_t min_delta;            // ms, >= 0
+  int32_t min_peers;            // >= 3
+  int32_t min_samples;          // >= 1
+  PeerRec* rec;                 // [S]
+  int32_t* big_list;            // [n_groups] groups deferred to the block pass
+  int32_t* big_n;
+};
+struct PeerTextArgs {
+  const PeerRec* rec;           // [S]
+  const int32_t* perm;          // [n] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;
+  int32_t n_series;
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  char ptxt[8];                 // "<p>:" (at most "99.999:")
+  int32_t plen;
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_peer_row_bound(max name bytes) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -648,6 +701,17 @@ int apm_traffic_values(apm::TrafficArgs* a, hipStream_t stream);
 // length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_traffic_plan(apm::TrafficTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_traffic_write(apm::TrafficTextArgs* a, hipStream_t stream);
+// peers.hip
+// the value pass' two paths (tests bracket them): a group of at most apm_peer_group_max() members
+// is ranked by 32 lanes in registers; a larger one by a whole block, without a bound
+int32_t apm_peer_group_max();
+size_t apm_peer_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes
+size_t apm_peer_row_bound(size_t name_bytes);
+void apm_peer_values(apm::PeerArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_peer_plan(apm::PeerTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_peer_write(apm::PeerTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

@@ -267,8 +267,9 @@ void append_pct_pairs(std::string& js, std::string_view rest) {
   }
 }
 
-// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw, 11 sb, 12 tf) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[13]*/) {
+// Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw, 11 sb, 12 tf,
+// 13 po) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[14]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -595,6 +596,52 @@ int encode_line(std::string_view line, std::string* out /*[13]*/) {
     copy_escape(o, js);
     o += '\n';
     return 12;
+  }
+  if (t == "po") {  // peer outlier: timestamp, server, service, count, pct, value2, peers, median2x2, mad4, verdict
+    // (utils/records.py entry_from_csv holds the same rules) a row is dropped whole unless it has
+    // exactly ten fields, m and E are 1 to 10 plain digits, the pair is <p>:<x> with p a percentile
+    // of at most three decimals and x 1 to 10 digits after an optional '-', X2 1 to 11 digits after
+    // an optional '-', D4 1 to 11 plain digits and the verdict H or L
+    if (a.n != 10) return -1;
+    if (!all_digits(a.f[4], 10) || !all_digits(a.f[6], 10) || !all_digits(a.f[8], 11)) return -1;
+    if (a.f[9] != "H" && a.f[9] != "L") return -1;
+    const size_t c = a.f[5].find(':');
+    if (c == std::string_view::npos) return -1;
+    const int64_t q = pct_from_text(a.f[5].substr(0, c));
+    if (q < 0) return -1;
+    const auto sint = [](std::string_view s, size_t max_len, int64_t& v) {
+      const bool neg = !s.empty() && s[0] == '-';
+      if (neg) s.remove_prefix(1);
+      if (!all_digits(s, max_len)) return false;
+      v = 0;
+      for (char ch : s) v = v * 10 + (ch - '0');
+      if (neg) v = -v;
+      return true;
+    };
+    int64_t x = 0, X2 = 0, m = 0, E = 0, D4 = 0;
+    if (!sint(a.f[5].substr(c + 1), 10, x) || !sint(a.f[7], 11, X2)) return -1;
+    sint(a.f[4], 10, m); sint(a.f[6], 10, E); sint(a.f[8], 11, D4);
+    std::string& o = out[13];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    append_i64(o, m); o += '\t';
+    append_i64(o, q / 1000);  // (the canonical text again: q / 1000 without trailing zeros)
+    if (q % 1000) {
+      char fr[4] = {(char)('0' + q % 1000 / 100), (char)('0' + q % 100 / 10), (char)('0' + q % 10), 0};
+      int n = 3;
+      while (fr[n - 1] == '0') --n;
+      o += '.';
+      o.append(fr, (size_t)n);
+    }
+    o += '\t';
+    append_i64(o, x); o += '\t';
+    append_i64(o, E); o += '\t';
+    append_i64(o, X2); o += '\t';
+    append_i64(o, D4); o += '\t';
+    o += a.f[9];
+    o += '\n';
+    return 13;
   }
   if (t == "jx") {
     std::string& o = out[3];

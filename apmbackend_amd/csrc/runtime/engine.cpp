@@ -307,6 +307,23 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       throw std::invalid_argument("tf stream: a window of more than " + std::to_string(apm_traffic_max_win() - 1) +
                                   " intervals is not supported");
   }
+  if (want(OUT_PO)) {  // K23: likewise
+    const auto& cl = cfg_.po_classes;
+    bool ok = cl.size() >= 2 && cl[0].empty() && cl.size() <= (size_t)cfg_.max_series + 2;
+    for (size_t c = 1; ok && c < cl.size(); ++c) ok = cl[c].size() == 1 && cl[c][0] >= 1 && cl[c][0] <= INT32_MAX;
+    const auto in_range = [&](int32_t c) { return c >= 0 && (size_t)c < cl.size(); };
+    ok = ok && in_range(cfg_.po_default);
+    for (const auto& kv : cfg_.po_services) ok = ok && in_range(kv.second);
+    const int32_t h = cfg_.po_high, l = cfg_.po_low;
+    ok = ok && cfg_.po_pct >= 1 && cfg_.po_pct <= 100000 && (h == 0 || (h >= 1001 && h <= 1000000)) &&
+         (l == 0 || (l >= 1 && l <= 999)) && (h != 0 || l != 0) && cfg_.po_z >= 0 && cfg_.po_z <= 100000 &&
+         cfg_.po_min_delta >= 0 && cfg_.po_min_peers >= 3 && cfg_.po_min_samples >= 1;
+    if (!ok)
+      throw std::invalid_argument("po stream: po_pct must be a percentile in 1 .. 100000 (p * 1000); po_classes must hold the "
+                                  "empty class 0 and at least one gate {minValue in 1 .. 2147483647}, every class index must "
+                                  "name one; po_high 0 or 1001 .. 1000000, po_low 0 or 1 .. 999 (not both 0), po_z 0 .. 100000, "
+                                  "po_min_delta >= 0, po_min_peers >= 3, po_min_samples >= 1");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -516,11 +533,13 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
       ev_tk_[k] = res_.new_event();
     }
   }
-  if (want(OUT_SV)) {  // K19
+  if (want(OUT_SV) || want(OUT_PO)) {  // K19's service groups, which K23 judges too
     d_sv_off_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
     d_sv_mem_ = (int32_t*)res_.dmalloc((size_t)S * 4);
     d_sv_pos_ = (int32_t*)res_.dmalloc((size_t)S * 4);
     d_sv_grp_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+  }
+  if (want(OUT_SV)) {  // K19
     d_sv_rec_ = (SvcRec*)res_.dmalloc((size_t)S * sizeof(SvcRec));
     text_alloc(sv_, OUT_SV, apm_svcwin_tmp_bytes(S));
   }
@@ -559,6 +578,24 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     HIP_OK(hipMemset(d_tf_cls_, 0, (size_t)S * 4));  // class 0 until a series' class is uploaded
     d_tf_rec_ = (TrafficRec*)res_.dmalloc((size_t)S * sizeof(TrafficRec));
     text_alloc(tf_, OUT_TF, apm_traffic_tmp_bytes(S));
+  }
+  if (want(OUT_PO)) {  // K23
+    const int32_t C = (int32_t)cfg_.po_classes.size();  // (checked at the top of the constructor)
+    n_po_classes_ = C;
+    d_po_val_ = (int32_t*)res_.dmalloc((size_t)C * 4);
+    {
+      std::vector<int32_t> tab((size_t)C, 0);
+      for (int32_t c = 1; c < C; ++c) tab[(size_t)c] = (int32_t)cfg_.po_classes[c][0];
+      HIP_OK(hipMemcpy(d_po_val_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    }
+    d_po_cls_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    HIP_OK(hipMemset(d_po_cls_, 0, (size_t)S * 4));  // class 0 until a series' class is uploaded
+    d_po_sum2_ = (long long*)res_.dmalloc((size_t)S * 8);
+    d_po_m_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    d_po_nan_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    d_po_big_ = (int32_t*)res_.dmalloc((size_t)(S + 1) * 4);
+    d_po_rec_ = (PeerRec*)res_.dmalloc((size_t)S * sizeof(PeerRec));
+    text_alloc(po_, OUT_PO, apm_peer_tmp_bytes(S));
   }
   if (want(OUT_LH)) text_alloc(lh_, OUT_LH, apm_hist_tmp_bytes(S));  // K15
   {
@@ -794,6 +831,7 @@ int32_t Engine::series_for(int32_t server, int32_t service) {
   if (want(OUT_SL)) h_slo_cls_.push_back(slo_class_of(s));  // (uploaded with the hard max)
   if (want(OUT_SB)) h_sb_cls_.push_back(burn_class_of(s));  // K21: likewise
   if (want(OUT_TF)) h_tf_cls_.push_back(traffic_class_of(s));  // K22: likewise
+  if (want(OUT_PO)) h_po_cls_.push_back(peer_class_of(s));  // K23: likewise
   h_suppressed_.push_back(0);
   zscore_seen_.push_back(0);
   h_active_.push_back(0);
@@ -840,6 +878,12 @@ int32_t Engine::traffic_class_of(int32_t s) const {
   return it != cfg_.tf_services.end() ? it->second : cfg_.tf_default;
 }
 
+// K23: the same rule over the po stream's own tables
+int32_t Engine::peer_class_of(int32_t s) const {
+  auto it = cfg_.po_services.find(dict_.service_name(series_[s].service));
+  return it != cfg_.po_services.end() ? it->second : cfg_.po_default;
+}
+
 void Engine::refresh_series_settings() {
   flush();
   // config hot reload (updateAllServiceSettings, stream_calc_z_score.js:152-167)
@@ -883,6 +927,7 @@ void Engine::upload_series_tables(int32_t lo) {
   if (want(OUT_SL)) upload_slo_classes(lo);
   if (want(OUT_SB)) upload_burn_classes(lo);
   if (want(OUT_TF)) upload_traffic_classes(lo);
+  if (want(OUT_PO)) upload_peer_classes(lo);
 }
 
 // K17: the classes of series [lo, n) to the device, on the stats stream.  A full upload (lo == 0: a
@@ -942,6 +987,25 @@ void Engine::upload_traffic_classes(int32_t lo) {
     stage_done();
   }
   tf_cls_uploaded_ = n;
+}
+
+// K23: upload_slo_classes over the po stream's own class array
+void Engine::upload_peer_classes(int32_t lo) {
+  const int32_t n = n_series_;
+  lo = std::min(lo, po_cls_uploaded_);  // (series no earlier upload carried go along)
+  if (lo == 0 || h_po_cls_.size() != (size_t)n) {
+    h_po_cls_.resize((size_t)n);
+    for (int32_t s = 0; s < n; ++s) h_po_cls_[s] = peer_class_of(s);
+    lo = 0;
+  }
+  if (n > lo) {
+    const size_t mc = (size_t)(n - lo);
+    int32_t* cs = (int32_t*)stage(mc * 4);
+    std::memcpy(cs, h_po_cls_.data() + lo, mc * 4);
+    h2d(d_po_cls_ + lo, cs, mc * 4, stream_);
+    stage_done();
+  }
+  po_cls_uploaded_ = n;
 }
 
 std::vector<uint64_t> Engine::cache_stats(bool drain) {
@@ -1626,6 +1690,8 @@ void Engine::flush() {
     sb_rows_lane_ = 0;
     metrics_.tf_rows += tf_rows_lane_;
     tf_rows_lane_ = 0;
+    metrics_.po_rows += po_rows_lane_;
+    po_rows_lane_ = 0;
     if (!out_error_.empty()) { std::string e = out_error_; out_error_.clear(); throw std::runtime_error(e); }
   }
   if (!st_error_.empty()) { std::string e = st_error_; st_error_.clear(); throw std::runtime_error(e); }
@@ -2571,6 +2637,9 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   if (want(OUT_SB)) burn_rollover(wa, edge_ts);
   // K22: after it, for the same reason: it reads the window's counts, d_win_ and its own class array.
   if (want(OUT_TF)) traffic_rollover(wa, edge_ts);
+  // K23: after it, for the same reason: it reads what K16 reads (window cells, counts, spill lists,
+  // d_win_), the service groups and its own class array, and writes buffers of its own.
+  if (want(OUT_PO)) peer_rollover(wa, edge_ts);
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2725,8 +2794,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[13];
-        int64_t counts[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::string enc[14];
+        int64_t counts[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3148,7 +3217,7 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   });
 }
 
-// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb, tf): buffers and the slot protocol, once.
+// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb, tf, po): buffers and the slot protocol, once.
 // `rows`: text lanes per series (rw prints one row per span).
 void Engine::text_alloc(TextStream& t, int kind, size_t tmp_bytes, int rows) {
   const size_t S = (size_t)cfg_.max_series;
@@ -3197,6 +3266,12 @@ void Engine::text_end(TextStream& t, int32_t n) {
       const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
       std::lock_guard<std::mutex> g(out_mu_);
       tf_rows_lane_ += rows;
+    }
+    if (ts->kind == OUT_PO) {  // (likewise)
+      const char* p = ts->text[k];
+      const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
+      std::lock_guard<std::mutex> g(out_mu_);
+      po_rows_lane_ += rows;
     }
     emit_bytes(ts->kind, ts->text[k], total);
   });
@@ -3708,6 +3783,77 @@ void Engine::download_traffic(std::vector<TrafficRec>& rec, std::vector<uint8_t>
     has[(size_t)s] = win[(size_t)s].active && cls[(size_t)s] > 0 && cls[(size_t)s] < n_tf_classes_;
 }
 
+// ---- K23: po rows.  Per st row whose service has a minValue and whose window percentile lies far
+// from the median of the same percentile over the eligible series of its service, one row, in st
+// order with the st rows' timestamp: K16's value pass with the one percentile into po's buffers,
+// the group pass over K19's service lists (the verdicts are decided on the device), then count /
+// scan / write of the text -- the length pass is the compaction.
+void Engine::peer_rollover(const WindowArgs& wa, int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();   // h_perm_ / d_perm_ and the names cover every series
+  sync_service_groups();
+  // (series whose settings no upload_series_tables() carried yet: as slo_rollover)
+  if (po_cls_uploaded_ < n) upload_peer_classes(po_cls_uploaded_);
+  WinPctArgs pa{};
+  pa.w = wa;
+  pa.nq = 1;
+  pa.q[0] = cfg_.po_pct;
+  pa.sum2 = d_po_sum2_;
+  pa.m = d_po_m_;
+  pa.nan = d_po_nan_;
+  pa.big_list = po_.big;
+  pa.big_n = po_.big + cfg_.max_series;
+  apm_winpct_values(&pa, stream_);
+  PeerArgs va{};
+  va.active = wa.st.active;
+  va.sum2 = d_po_sum2_;
+  va.m = d_po_m_;
+  va.cls = d_po_cls_;
+  va.val = d_po_val_;
+  va.n_classes = n_po_classes_;
+  va.n_series = n;
+  va.n_groups = sv_groups_;
+  va.grp_off = d_sv_off_;
+  va.grp_mem = d_sv_mem_;
+  va.r_h = cfg_.po_high;
+  va.r_l = cfg_.po_low;
+  va.z = cfg_.po_z;
+  va.min_delta = cfg_.po_min_delta;
+  va.min_peers = cfg_.po_min_peers;
+  va.min_samples = cfg_.po_min_samples;
+  va.rec = d_po_rec_;
+  va.big_list = d_po_big_;
+  va.big_n = d_po_big_ + cfg_.max_series;
+  apm_peer_values(&va, stream_);
+  po_last_n_ = n;
+  PeerTextArgs ta{};
+  ta.rec = d_po_rec_;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n;
+  ta.n_series = n;
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  ta.plen = pct_label(ta.ptxt, cfg_.po_pct);  // (as K16 prints it)
+  ta.len = po_.len;
+  ta.off = po_.off;
+  // the output bound needs no length pass: every row is at most apm_peer_row_bound bytes
+  ta.out = text_begin(po_, (size_t)n * apm_peer_row_bound(max_name_len_) + 64);
+  if (apm_peer_plan(&ta, po_.tmp, po_.tmp_bytes, stream_) != 0) throw std::runtime_error("peer scan failed");
+  apm_peer_write(&ta, stream_);
+  text_end(po_, n);
+}
+
+void Engine::download_peers(std::vector<PeerRec>& rec) {
+  rec.clear();
+  const int32_t n = po_last_n_;
+  if (!want(OUT_PO) || n == 0) return;
+  rec.resize((size_t)n);
+  HIP_OK(hipMemcpyAsync(rec.data(), d_po_rec_, rec.size() * sizeof(PeerRec), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3848,7 +3994,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po"};
   return n[k];
 }
 

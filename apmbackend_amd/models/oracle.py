@@ -27,10 +27,11 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import (as_bool, check_recent_windows, check_slo_burn, check_traffic_watch, gpu_opt, slo_burn,
+from ..utils.config import (as_bool, check_peer_outliers, check_recent_windows, check_slo_burn, check_traffic_watch,
+                            gpu_opt, peer_outliers, slo_burn,
                             latency_objectives, leaderboard, recent_windows, service_window, traffic_watch,
                             window_percentiles, zscore_lag_settings)
-from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, RecentWindowEntry,
+from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, PeerEntry, RecentWindowEntry,
                              ServiceWindowEntry, SloBurnEntry, TrafficEntry,
                              StatEntry, TxEntry, WindowPctEntry, WindowSloEntry, entry_from_csv, hist_bin, hist_lower,
                              pct_ranks)
@@ -680,7 +681,10 @@ class StatsOracle:
                  emit_recent: Optional[Callable[[str], None]] = None, recent_buckets: Iterable[int] = (),
                  recent_percentiles: Iterable[int] = (),
                  emit_burn: Optional[Callable[[str], None]] = None, burn: Optional[Dict[str, Any]] = None,
-                 emit_traffic: Optional[Callable[[str], None]] = None, traffic: Optional[Dict[str, Any]] = None):
+                 emit_traffic: Optional[Callable[[str], None]] = None, traffic: Optional[Dict[str, Any]] = None,
+                 emit_peer: Optional[Callable[[str], None]] = None, peer: Optional[Dict[str, Any]] = None):
+        self.emit_peer = emit_peer  # po rows (docs/PEERS.md); None = stream off
+        self.peer = peer            # config.parse_peer_outliers's result
         self.emit_traffic = emit_traffic  # tf rows (docs/TRAFFIC.md); None = stream off
         self.traffic = traffic            # config.parse_traffic_watch's result
         self.emit_burn = emit_burn  # sb rows (docs/BURN.md); None = stream off
@@ -932,6 +936,53 @@ class StatsOracle:
             return None
         return TrafficEntry(edge_ts, server, service, sum(counts), min_rate, rules).to_csv()
 
+    @staticmethod
+    def peer_verdict(x: int, X2: int, D4: int, E: int, po: Dict[str, Any], min_value: int) -> str:
+        """H, L or N of one eligible member (docs/PEERS.md), in integers."""
+        if E < po["minPeers"] or X2 < 4 * min_value:
+            return "N"
+        r_h, r_l, z, floor4 = po["high"], po["low"], po["z"], 4 * po["minDelta"]
+        if r_h and 2000 * x >= r_h * X2 and 4000 * x >= 2000 * X2 + z * D4 and 2 * x - X2 >= floor4:
+            return "H"
+        if r_l and 2000 * x <= r_l * X2 and 4000 * x <= 2000 * X2 - z * D4 and X2 - 2 * x >= floor4:
+            return "L"
+        return "N"
+
+    def peer_member(self, win: List[List[int]]) -> Tuple[int, int]:
+        """(m, x) of one window: its finite samples and the sum of the one or two ranks the integer
+        rank rule reads for the configured percentile (twice the percentile; 0 without a sample)."""
+        fin = sorted(int(v) for arr in win for v in arr if v == v and -2147483647 <= v <= 2147483647)
+        if not fin:
+            return 0, 0
+        lo, hi = pct_ranks(len(fin), self.peer["percentile"])
+        return len(fin), fin[lo] + fin[hi]
+
+    def peer_rows(self, edge_ts: int, members: List[Tuple[str, str, int, int]]) -> List[str]:
+        """The po rows of one rollover.  ``members``: (server, service, m, x) per st row, in st order.
+        Per service the eligible members (a minValue, m >= minSamples) give X2 = x_lo + x_hi and
+        D4 = d_lo + d_hi, d = |2 x - X2|; a row per eligible member with verdict H or L, in st order."""
+        po = self.peer
+        groups: Dict[str, List[int]] = {}
+        for server, service, m, x in members:
+            min_value = po["services"][service] if service in po["services"] else po["default"]
+            if min_value is not None and m >= po["minSamples"]:
+                groups.setdefault(service, []).append(x)
+        base: Dict[str, Tuple[int, int, int]] = {}
+        for service, xs in groups.items():
+            X2 = statistics.median_low(xs) + statistics.median_high(xs)
+            dev = [abs(2 * x - X2) for x in xs]
+            base[service] = (len(xs), X2, statistics.median_low(dev) + statistics.median_high(dev))
+        rows = []
+        for server, service, m, x in members:
+            min_value = po["services"][service] if service in po["services"] else po["default"]
+            if min_value is None or m < po["minSamples"]:
+                continue
+            E, X2, D4 = base[service]
+            v = self.peer_verdict(x, X2, D4, E, po, min_value)
+            if v != "N":
+                rows.append(PeerEntry(edge_ts, server, service, m, po["percentile"], x, E, X2, D4, v).to_csv())
+        return rows
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -946,6 +997,7 @@ class StatsOracle:
                 self.emit_hist(row)
         st_rows: List[str] = []
         svc_wins: "OrderedDict[str, List[List[int]]]" = OrderedDict()
+        peer_members: List[Tuple[str, str, int, int]] = []
         for server, srv in self.servers.items():
             for service, svc in srv.items():
                 win: List[List[int]] = []
@@ -991,12 +1043,17 @@ class StatsOracle:
                     row = self.traffic_row(edge_ts, server, service, svc)
                     if row is not None:
                         self.emit_traffic(row)
+                if self.emit_peer is not None:
+                    peer_members.append((server, service) + self.peer_member(win))
         if self.emit_top is not None:
             for row in self.top_rows(st_rows):
                 self.emit_top(row)
         if self.emit_svc is not None:
             for row in self.svc_rows(edge_ts, svc_wins):
                 self.emit_svc(row)
+        if self.emit_peer is not None:
+            for row in self.peer_rows(edge_ts, peer_members):
+                self.emit_peer(row)
 
 
 # ----------------------------------------------------------------------------- z-score oracle
@@ -1231,6 +1288,7 @@ class PipelineOracle:
         self.rw: List[str] = []
         self.sb: List[str] = []
         self.tf: List[str] = []
+        self.po: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1241,6 +1299,7 @@ class PipelineOracle:
         check_recent_windows(recent_windows(cfg), int(sc["windowSizeInIntervals"]))
         check_slo_burn(slo_burn(cfg), int(sc["windowSizeInIntervals"]))  # (likewise)
         check_traffic_watch(traffic_watch(cfg), int(sc["windowSizeInIntervals"]))  # (likewise)
+        check_peer_outliers(peer_outliers(cfg))
         self.st = StatsOracle(self._on_st, self.tx_db.append, int(sc["intervalLengthInSeconds"]),
                               int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
                               emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None,
@@ -1256,7 +1315,8 @@ class PipelineOracle:
                               recent_buckets=(recent_windows(cfg) or {}).get("buckets", ()),
                               recent_percentiles=(recent_windows(cfg) or {}).get("percentiles", ()),
                               emit_burn=self.emit_burn if slo_burn(cfg) else None, burn=slo_burn(cfg),
-                              emit_traffic=self.tf.append if traffic_watch(cfg) else None, traffic=traffic_watch(cfg))
+                              emit_traffic=self.tf.append if traffic_watch(cfg) else None, traffic=traffic_watch(cfg),
+                              emit_peer=self.po.append if peer_outliers(cfg) else None, peer=peer_outliers(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

@@ -38,9 +38,10 @@ import time
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 from ..models.oracle import file_kind, server_of
-from ..models.pipeline import DB_OUTPUTS, EVERY_OUT_KINDS, KIND_CODE, APMEngine
+from ..models.pipeline import WHOLE_OUT_KINDS, DB_OUTPUTS, KIND_CODE, APMEngine
 from ..parallel.dist import dist_env, shard_servers
-from ..utils.config import (ConfigWatcher, as_bool, gpu_opt, latency_objectives, leaderboard, read_apm_config,
+from ..utils.config import (ConfigWatcher, as_bool, gpu_opt, latency_objectives, leaderboard, peer_outliers,
+                            read_apm_config,
                             recent_windows, service_window, slo_burn, traffic_watch, window_percentiles)
 from . import logger as apmlog
 from .notifier import AlertNotifier
@@ -164,16 +165,18 @@ class IngestService:
             outs.add("sb")
         if traffic_watch(self.cfg):  # K22 traffic drops and surges (ValueError on a malformed object)
             outs.add("tf")
+        if peer_outliers(self.cfg):  # K23 peer-outlier servers per service (ValueError on a malformed object)
+            outs.add("po")
         if self.world > 1 and engine == "native" and as_bool(g.get("fleetBaseline", True)) \
                 and as_bool(g.get("fleetBaselineRows", True)):
             outs.add("fb")  # fleet-merged per-service baselines (rank 0 emits them)
         if self.mode == "amqp":
             outs |= {"transactions" if "transactions" in self.bridge else "", "st" if "stats" in self.bridge else ""}
             outs.discard("")
-        self.outputs = [k for k in EVERY_OUT_KINDS if k in outs]
+        self.outputs = [k for k in WHOLE_OUT_KINDS if k in outs]
         self.outs_set = set(self.outputs)
         if self.mode == "amqp" and "z_score" in self.bridge:
-            self.outputs = [k for k in EVERY_OUT_KINDS if k in set(self.outputs) | {"fs"}]
+            self.outputs = [k for k in WHOLE_OUT_KINDS if k in set(self.outputs) | {"fs"}]
         if engine == "native":
             self.eng = APMEngine(self.cfg, device=self.local_rank, outputs=self.outputs)
             self.native = self.eng.eng
@@ -300,6 +303,8 @@ class IngestService:
                 self.producers["burn"] = self.qm.get_queue(gpu_opt(self.cfg, "burnQueue"), "p")
             if "tf" in self.outs_set:
                 self.producers["traffic"] = self.qm.get_queue(gpu_opt(self.cfg, "trafficQueue"), "p")
+            if "po" in self.outs_set:
+                self.producers["peers"] = self.qm.get_queue(gpu_opt(self.cfg, "peerQueue"), "p")
             self.qm.on("pause", lambda: log.info("queue backpressure: pausing ingest"))
         elif self.mode != "none":
             raise ValueError(f"unknown gpu.outputMode {self.mode!r}")
@@ -853,7 +858,7 @@ class IngestService:
             counts[k] = blob.count(b"\n")
             if k == "al" and self.notifier:
                 self.notifier.add_lines(blob.decode("utf-8").split("\n"))
-            if self.inserter is not None and (k in DB_OUTPUTS or k in ("fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf")):
+            if self.inserter is not None and (k in DB_OUTPUTS or k in ("fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po")):
                 self.inserter.consume_bytes(blob)
             elif self.qm is not None:
                 if k == "fb":
@@ -874,6 +879,8 @@ class IngestService:
                     prod = self.producers.get("burn")
                 elif k == "tf":
                     prod = self.producers.get("traffic")
+                elif k == "po":
+                    prod = self.producers.get("peers")
                 elif k in DB_OUTPUTS:
                     prod = self.producers["db"]
                 elif k == "transactions":

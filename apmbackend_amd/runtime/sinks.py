@@ -70,12 +70,15 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
     "sb": ("dbBurnTable", ["timestamp", "server", "service", "threshold", "target_q", "count", "bad", "nan", "rules"]),
     # traffic drops and surges (tf records, gpu.trafficWatch): likewise
     "tf": ("dbTrafficTable", ["timestamp", "server", "service", "count", "min_rate", "rules"]),
+    # peer-outlier servers per service (po records, gpu.peerOutliers): likewise
+    "po": ("dbPeerTable", ["timestamp", "server", "service", "count", "pct", "value2", "peers", "median2x2", "mad4",
+                           "verdict"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po")
 # tables of the record types the reference does not know (its config has no key for them)
 DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct", "sl": "apm_window_slo",
                   "tk": "apm_leaderboard", "sv": "apm_service_window", "rw": "apm_recent_window",
-                  "sb": "apm_slo_burn", "tf": "apm_traffic"}
+                  "sb": "apm_slo_burn", "tf": "apm_traffic", "po": "apm_peer_outlier"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -163,7 +166,7 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
         elif c in ("stats", "entry", "bins", "pcts", "le", "rules"):
             out[c] = json.loads(v)
-        elif c in ("servers", "buckets", "elapsed_sum", "threshold", "target_q", "bad", "min_rate"):  # (sv, rw, sb: plain integers; the sum may pass 2^53)
+        elif c in ("servers", "buckets", "elapsed_sum", "threshold", "target_q", "bad", "min_rate", "value2", "peers", "median2x2", "mad4"):  # (sv, rw, sb: plain integers; the sum may pass 2^53)
             out[c] = int(v)
         elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan", "rank", "average", "per75", "per95") or rtype == "jx" and c not in ("server",):
             f = float(v)

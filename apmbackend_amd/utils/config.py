@@ -102,6 +102,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "burnQueue": "slo_burn",          # amqp mode: the queue the sb records go to
     "trafficWatch": None,             # K22 "tf" stream: traffic drops and surges against the window's median / MAD baseline, {"default": {"minRate": 5}, "services": {...}, "rules": [{"short": 1, "drop": 0.1, "z": 4}], "minBuckets": 8} (docs/TRAFFIC.md)
     "trafficQueue": "traffic",        # amqp mode: the queue the tf records go to
+    "peerOutliers": None,             # K23 "po" stream: servers whose window percentile lies far from the median over the servers of the same service, {"percentile": 95, "default": {"minValue": 20}, "services": {...}, "high": 2, "low": 0.25, "z": 3, "minDelta": 10, "minPeers": 5, "minSamples": 20} (docs/PEERS.md)
+    "peerQueue": "peer_outliers",     # amqp mode: the queue the po records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -604,6 +606,145 @@ def traffic_tables(tf: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[
     return classes, services, default_class
 
 
+PEER_PCT_DEFAULT = 95000    # percentile * 1000
+PEER_Z_DEFAULT = 3000       # z * 1000
+PEER_KEYS = ("percentile", "default", "services", "high", "low", "z", "minDelta", "minPeers", "minSamples")
+
+
+def _peer_decimal(where: str, p: Any, lo: int, hi: int) -> int:
+    """A decimal with at most three places as the integer ``p * 1000`` in lo .. hi, read from its
+    text (never through float arithmetic), as _traffic_decimal."""
+    if isinstance(p, bool) or not isinstance(p, (int, float, str, decimal.Decimal)):
+        raise ValueError(f"gpu.peerOutliers: {where}: {p!r} is not a number")
+    try:
+        d = decimal.Decimal(repr(p) if isinstance(p, float) else str(p).strip())
+    except decimal.InvalidOperation:
+        raise ValueError(f"gpu.peerOutliers: {where}: {p!r} is not a number") from None
+    if not d.is_finite():
+        raise ValueError(f"gpu.peerOutliers: {where}: {p!r} is not finite")
+    q = d * 1000
+    if q != q.to_integral_value():
+        raise ValueError(f"gpu.peerOutliers: {where}: {p!r} has more than three decimals")
+    q = int(q)
+    if not lo <= q <= hi:
+        raise ValueError(f"gpu.peerOutliers: {where}: {p!r} is outside {lo / 1000:g} .. {hi / 1000:g}")
+    return q
+
+
+def _peer_int(where: str, v: Any, lo: int, hi: int = SLO_T_MAX) -> int:
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError(f"gpu.peerOutliers: {where} {v!r} is not an integer")
+    if not lo <= v <= hi:
+        raise ValueError(f"gpu.peerOutliers: {where} {v!r} is outside {lo} .. {hi}")
+    return int(v)
+
+
+def _parse_peer_class(where: str, v: Any) -> Optional[int]:
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.peerOutliers: {where} must be an object with 'minValue' (or null), got {v!r}")
+    extra = set(v) - {"minValue"}
+    if extra:
+        raise ValueError(f"gpu.peerOutliers: {where}: unknown key(s) {sorted(extra, key=str)!r}")
+    if "minValue" not in v:
+        raise ValueError(f"gpu.peerOutliers: {where} needs 'minValue', got {v!r}")
+    return _peer_int(f"{where}: minValue", v["minValue"], 1)
+
+
+def parse_peer_outliers(v: Any) -> Optional[Dict[str, Any]]:
+    """gpu.peerOutliers -> {"percentile": q, "default": minValue | None, "services": {name: minValue
+    | None}, "high": r_h, "low": r_l, "z": z, "minDelta": n, "minPeers": n, "minSamples": n}.
+    ``percentile``: one value under gpu.windowPercentiles' rules, q = p * 1000 (default 95).
+    ``minValue`` is a JSON integer in 1 .. 2147483647 (bool, float and str are rejected); ``default``
+    may be absent or null, a service named with null gets no rows.  ``high``: a decimal with at most
+    three places, r_h = high * 1000 in 1001 .. 1000000; ``low`` likewise, r_l = low * 1000 in
+    1 .. 999; at least one of the two (the missing one is 0 in the result); ``z`` likewise, z * 1000
+    in 0 .. 100000, default 3.  ``minDelta``: a JSON integer in 0 .. 2147483647 (default 0);
+    ``minPeers``: a JSON integer >= 3 (default 5); ``minSamples``: a JSON integer in
+    1 .. 2147483647 (default 20).  None, or an object in which no service has a minValue -> None
+    (stream off); anything else raises ValueError."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.peerOutliers: an object with 'default' and / or 'services', and 'high' and / or 'low', got {v!r}")
+    extra = set(v) - set(PEER_KEYS)
+    if extra:
+        raise ValueError(f"gpu.peerOutliers: unknown key(s) {sorted(extra, key=str)!r}")
+    q = PEER_PCT_DEFAULT
+    if "percentile" in v:
+        try:
+            qs = parse_window_percentiles([v["percentile"]])
+        except ValueError as e:
+            raise ValueError(str(e).replace("gpu.windowPercentiles", "gpu.peerOutliers: percentile")) from None
+        if len(qs) != 1:
+            raise ValueError(f"gpu.peerOutliers: percentile: one percentile, got {v['percentile']!r}")
+        q = qs[0]
+    default = _parse_peer_class("default", v.get("default"))
+    services = v.get("services")
+    if services is None:
+        services = {}
+    if not isinstance(services, dict):
+        raise ValueError(f"gpu.peerOutliers: services must be an object, got {services!r}")
+    named: Dict[str, Optional[int]] = {}
+    for name, o in services.items():
+        if not isinstance(name, str):
+            raise ValueError(f"gpu.peerOutliers: service name {name!r} is not a string")
+        named[name] = _parse_peer_class(f"services[{name!r}]", o)
+    if "high" not in v and "low" not in v:
+        raise ValueError("gpu.peerOutliers: needs at least one of 'high' and 'low'")
+    r_h = _peer_decimal("high", v["high"], 1001, 1000000) if "high" in v else 0
+    r_l = _peer_decimal("low", v["low"], 1, 999) if "low" in v else 0
+    z = _peer_decimal("z", v["z"], 0, 100000) if "z" in v else PEER_Z_DEFAULT
+    min_delta = _peer_int("minDelta", v.get("minDelta", 0), 0)
+    min_peers = _peer_int("minPeers", v.get("minPeers", 5), 3)
+    min_samples = _peer_int("minSamples", v.get("minSamples", 20), 1)
+    if default is None and not any(o is not None for o in named.values()):
+        return None
+    return {"percentile": q, "default": default, "services": named, "high": r_h, "low": r_l, "z": z,
+            "minDelta": min_delta, "minPeers": min_peers, "minSamples": min_samples}
+
+
+def peer_outliers(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """The validated gpu.peerOutliers object of a config (None: off)."""
+    return parse_peer_outliers(gpu_opt(cfg, "peerOutliers"))
+
+
+def check_peer_outliers(po: Optional[Dict[str, Any]]) -> None:
+    """What an engine checks of the parsed object when it is constructed (as check_traffic_watch;
+    no setting depends on the window): the ranges parse_peer_outliers guarantees, for a caller
+    that built the object itself."""
+    if not po:
+        return
+    ok = (1 <= po["percentile"] <= PCT_SCALE and (po["high"] == 0 or 1001 <= po["high"] <= 1000000)
+          and (po["low"] == 0 or 1 <= po["low"] <= 999) and (po["high"] or po["low"]) and 0 <= po["z"] <= 100000
+          and 0 <= po["minDelta"] <= SLO_T_MAX and 3 <= po["minPeers"] <= SLO_T_MAX and 1 <= po["minSamples"] <= SLO_T_MAX)
+    if not ok:
+        raise ValueError(f"gpu.peerOutliers: settings out of range: {po!r}")
+
+
+def peer_tables(po: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[str, int], int]:
+    """(classes, service -> class, default class) as the engine takes them, by sl's scheme
+    (traffic_tables): class 0 is "no row" (an empty list), class 1 the default [minValue] when there
+    is one, then one class per named service with a minValue, in config order; a service named with
+    null maps to class 0."""
+    if not po:
+        return [], {}, 0
+    classes: List[List[int]] = [[]]
+    default_class = 0
+    if po["default"] is not None:
+        classes.append([po["default"]])
+        default_class = 1
+    services: Dict[str, int] = {}
+    for name, o in po["services"].items():
+        if o is not None:
+            classes.append([o])
+            services[name] = len(classes) - 1
+        else:
+            services[name] = 0
+    return classes, services, default_class
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -649,6 +790,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         parse_slo_burn(merged["sloBurn"])  # likewise
     if "trafficWatch" in merged:
         parse_traffic_watch(merged["trafficWatch"])  # likewise
+    if "peerOutliers" in merged:
+        parse_peer_outliers(merged["peerOutliers"])  # likewise
     return cfg
 
 

@@ -649,6 +649,43 @@ class TrafficEntry:
                            "verdict": v} for k, b, r, m2, m4, v in self.rules]}
 
 
+# ---- po: peer-outlier servers per service (docs/PEERS.md).  Integers only.
+def pct_text(q: int) -> str:
+    """q = p * 1000 as the canonical text of p: trailing zeros and a trailing point dropped."""
+    q = int(q)
+    return f"{q // 1000}.{q % 1000:03d}".rstrip("0").rstrip(".") if q % 1000 else str(q // 1000)
+
+
+@dataclass
+class PeerEntry:
+    """``po|ts|server|service|m|p:x|E|X2|D4|V`` -- at a rollover, a series whose window percentile
+    ``p`` lies far above (``H``) or below (``L``) the median of the same percentile over the ``peers``
+    eligible series of its service: ``count`` is the window's finite samples, ``q`` = p * 1000,
+    ``value2`` twice the series' percentile, ``median2x2`` x_lo + x_hi of the peers' sorted value2
+    (four times the median percentile), ``mad4`` d_lo + d_hi of the sorted abs(2 value2 - median2x2)
+    (no reference counterpart)."""
+    timestamp: Num
+    server: str
+    service: str
+    count: int
+    q: int
+    value2: int
+    peers: int
+    median2x2: int
+    mad4: int
+    verdict: str
+    type: str = "po"
+
+    def to_csv(self) -> str:
+        return (f"po|{js_str(self.timestamp)}|{self.server}|{self.service}|{int(self.count)}|{pct_text(self.q)}:"
+                f"{int(self.value2)}|{int(self.peers)}|{int(self.median2x2)}|{int(self.mad4)}|{self.verdict}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "count": int(self.count), "pct": pct_text(self.q), "value2": int(self.value2), "peers": int(self.peers),
+                "median2x2": int(self.median2x2), "mad4": int(self.mad4), "verdict": self.verdict}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -751,7 +788,19 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
         if any(v is None for v in nums) or rules is None:  # (a malformed row is dropped, as copyenc.cpp does)
             return None
         return TrafficEntry(parse_int(a[1]), a[2], a[3], *nums, rules)
+    if t == "po":
+        # (copyenc.cpp holds the same rules) exactly ten fields; m and E 1 to 10 digits; <p>:<x> with x
+        # 1 to 10 digits after an optional '-'; X2 1 to 11 digits after an optional '-'; D4 1 to 11
+        # digits; the verdict H or L; anything else is dropped
+        if len(arr) != 10 or arr[9] not in ("H", "L"):
+            return None
+        p, sep, x = arr[5].partition(":")
+        q = _pct_from_text(p) if sep else None
+        nums = [_svc_int(arr[4]), _svc_int(x, 10, True), _svc_int(arr[6]), _svc_int(arr[7], 11, True), _svc_int(arr[8], 11)]
+        if q is None or any(v is None for v in nums):
+            return None
+        return PeerEntry(parse_int(arr[1]), arr[2], arr[3], nums[0], q, nums[1], nums[2], nums[3], nums[4], arr[9])
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po")
