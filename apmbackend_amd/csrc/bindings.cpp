@@ -14,6 +14,7 @@
 #include "kernels/burncmp.h"
 #include "kernels/kernel_api.h"
 #include "kernels/peercmp.h"
+#include "kernels/shiftcmp.h"
 #include "kernels/trafficcmp.h"
 #include "runtime/engine.h"
 #include "runtime/format.h"
@@ -246,6 +247,48 @@ EngineConfig config_from(const py::dict& d) {
     num("po_min_peers", 3, 0x7fffffff, 3, c.po_min_peers, "an integer >= 3");
     num("po_min_samples", 1, 0x7fffffff, 1, c.po_min_samples, "an integer in 1 .. 2147483647");
   }
+  if (d.contains("ls_classes")) {  // K24 (the constructor checks the tables and rules when the ls stream is on)
+    c.ls_classes = d["ls_classes"].cast<std::vector<std::vector<int64_t>>>();
+    if (d.contains("ls_services")) c.ls_services = d["ls_services"].cast<std::map<std::string, int32_t>>();
+    c.ls_default = get<int32_t>(d, "ls_default", 0);
+  }
+  if (d.contains("ls_short")) {
+    const auto list = [&](const char* key) {
+      return d.contains(key) ? d[key].cast<std::vector<int64_t>>() : std::vector<int64_t>();
+    };
+    const auto k = list("ls_short"), q = list("ls_pct"), up = list("ls_up"), dn = list("ls_down"), z = list("ls_z");
+    if (k.size() > 4 || q.size() != k.size() || up.size() != k.size() || dn.size() != k.size() || z.size() != k.size())
+      throw std::invalid_argument("ls_short / ls_pct / ls_up / ls_down / ls_z: at most 4 rules, one value of each per rule");
+    c.n_ls_rules = (int32_t)k.size();
+    for (size_t i = 0; i < k.size(); ++i) {
+      if (k[i] < 1 || k[i] > 64) throw std::invalid_argument("ls_short: integers in 1 .. 64");
+      if (q[i] < 1 || q[i] > 99999) throw std::invalid_argument("ls_pct: integers in 1 .. 99999 (percentile * 1000)");
+      if (i && k[i] < k[i - 1]) throw std::invalid_argument("ls_short: ascending");
+      for (size_t o = 0; o < i; ++o)
+        if (k[o] == k[i] && q[o] == q[i]) throw std::invalid_argument("ls_short / ls_pct: a (short, percentile) pair stands twice");
+      if (up[i] != 0 && (up[i] < 1001 || up[i] > 1000000))
+        throw std::invalid_argument("ls_up: integers in 1001 .. 1000000 (up * 1000), 0 for none");
+      if (dn[i] != 0 && (dn[i] < 1001 || dn[i] > 1000000))
+        throw std::invalid_argument("ls_down: integers in 1001 .. 1000000 (down * 1000), 0 for none");
+      if (up[i] == 0 && dn[i] == 0) throw std::invalid_argument("ls_up / ls_down: a rule needs at least one of them");
+      if (z[i] < 0 || z[i] > 100000) throw std::invalid_argument("ls_z: integers in 0 .. 100000 (z * 1000)");
+      c.ls_short[i] = (int32_t)k[i];
+      c.ls_pct[i] = (int32_t)q[i];
+      c.ls_up[i] = (int32_t)up[i];
+      c.ls_down[i] = (int32_t)dn[i];
+      c.ls_z[i] = (int32_t)z[i];
+    }
+  }
+  if (d.contains("ls_min_recent")) {
+    const int64_t v = d["ls_min_recent"].cast<int64_t>();
+    if (v < 1 || v > 0x7fffffff) throw std::invalid_argument("ls_min_recent: an integer >= 1");
+    c.ls_min_recent = (int32_t)v;
+  }
+  if (d.contains("ls_min_baseline")) {
+    const int64_t v = d["ls_min_baseline"].cast<int64_t>();
+    if (v < 2 || v > 0x7fffffff) throw std::invalid_argument("ls_min_baseline: an integer >= 2");
+    c.ls_min_baseline = (int32_t)v;
+  }
   if (d.contains("tk_k") && !d["tk_k"].is_none()) {  // (the constructor checks them when the tk stream is on)
     c.tk_k = d["tk_k"].cast<int32_t>();
     if (d.contains("tk_by")) c.tk_by = d["tk_by"].cast<std::vector<int32_t>>();
@@ -303,6 +346,7 @@ py::dict metrics_dict(const EngineMetrics& m) {
   d["sb_rows"] = m.sb_rows;
   d["tf_rows"] = m.tf_rows;
   d["po_rows"] = m.po_rows;
+  d["ls_rows"] = m.ls_rows;
   d["formatted_bytes"] = m.formatted_bytes; d["lockstep_rollovers"] = m.lockstep_rollovers; d["format_fallbacks"] = m.format_fallbacks;
   d["t_parse_ms"] = m.t_parse_ms; d["t_join_ms"] = m.t_join_ms; d["t_stats_ms"] = m.t_stats_ms;
   d["t_total_ms"] = m.t_total_ms;
@@ -798,6 +842,27 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("shifts", [](Engine& e) {
+        // per series id of the last rollover's K24 value pass: None for a series without an st row or
+        // a class, else (n, [(mB, nanB, mR, nanR, a, b, T2, X2, verdict "U" / "D" / "N") per configured rule])
+        std::vector<ShiftRec> rec;
+        std::vector<uint8_t> has;
+        e.download_shifts(rec, has);
+        const int nr = e.ls_nrule();
+        py::list out;
+        for (size_t s = 0; s < has.size(); ++s) {
+          if (!has[s]) { out.append(py::none()); continue; }
+          const ShiftRec& r = rec[s];
+          py::list rules;
+          for (int j = 0; j < nr; ++j) {
+            const int v = (r.verdict >> (2 * j)) & 3;
+            rules.append(py::make_tuple(r.mB[j], r.nanB[j], r.mR[j], r.nanR[j], r.a[j], r.b[j], (int64_t)r.T2[j],
+                                        (int64_t)r.X2[j], v == LS_U ? "U" : v == LS_D ? "D" : "N"));
+          }
+          out.append(py::make_tuple(r.n, rules));
+        }
+        return out;
+      })
       .def("leaderboard", [](Engine& e) {
         // the last rollover's K18 records: (board, rank, series id, tpm, avg, p75, p95), raw doubles
         std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> rows;
@@ -856,15 +921,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[14];
-    int64_t counts[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::string out[15];
+    int64_t counts[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[14] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po"};
-    for (int k = 0; k < 14; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[15] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls"};
+    for (int k = 0; k < 15; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -1114,6 +1179,27 @@ PYBIND11_MODULE(_apm_native, m) {
     return std::string(v == PO_H ? "H" : v == PO_L ? "L" : "N");
   }, py::arg("x"), py::arg("X2"), py::arg("D4"), py::arg("E"), py::arg("r_h"), py::arg("r_l"), py::arg("z"),
      py::arg("min_value"), py::arg("min_delta"), py::arg("min_peers"));
+  // ls shifts (shift.hip): the window length and the sample count up to which the value pass keeps a
+  // series in its 32-lane group (tests bracket them), and the exact verdict the kernels decide a rule
+  // with (shiftcmp.h, the same routine compiled for the host): "U", "D" or "N"
+  m.def("shift_group_max", []() { return apm_shift_group_max(); });
+  m.def("shift_group_win", []() { return apm_shift_group_win(); });
+  m.def("shift_verdict", [](int64_t a, int64_t b, int64_t mR, int64_t mB, int64_t T2, int64_t X2, int64_t q, int64_t r_u,
+                            int64_t r_d, int64_t z, int64_t min_delta, int64_t min_recent, int64_t min_baseline) {
+    // (the bounds shiftcmp.h's width argument rests on)
+    const int64_t b32 = (int64_t)1 << 32;
+    if (mR < 0 || mR > 0x7fffffff || mB < 0 || mB > 0x7fffffff || a < 0 || b < 0 || a + b > mR || T2 <= -b32 || T2 >= b32 ||
+        X2 <= -b32 || X2 >= b32 || q < 1 || q > 99999 || (r_u != 0 && (r_u < 1001 || r_u > 1000000)) ||
+        (r_d != 0 && (r_d < 1001 || r_d > 1000000)) || z < 0 || z > 100000 || min_delta < 1 || min_delta > 1073741823 ||
+        min_recent < 1 || min_recent > 0x7fffffff || min_baseline < 1 || min_baseline > 0x7fffffff)
+      throw std::invalid_argument("shift_verdict: mR, mB in 0 .. 2147483647, a + b <= mR, |T2|, |X2| < 2^32, q in 1 .. 99999, "
+                                  "r_u, r_d 0 or in 1001 .. 1000000, z in 0 .. 100000, min_delta in 1 .. 1073741823, "
+                                  "min_recent, min_baseline >= 1");
+    const int v = shift_verdict((int32_t)a, (int32_t)b, (int32_t)mR, (int32_t)mB, T2, X2, (int32_t)q, (int32_t)r_u, (int32_t)r_d,
+                                (int32_t)z, (int32_t)min_delta, (int32_t)min_recent, (int32_t)min_baseline);
+    return std::string(v == LS_U ? "U" : v == LS_D ? "D" : "N");
+  }, py::arg("a"), py::arg("b"), py::arg("mR"), py::arg("mB"), py::arg("T2"), py::arg("X2"), py::arg("q"), py::arg("r_u"),
+     py::arg("r_d"), py::arg("z"), py::arg("min_delta"), py::arg("min_recent"), py::arg("min_baseline"));
   m.def("apm_topk_tile", []() { return apm_topk_tile(); });
   m.def("apm_topk_final_span", []() { return apm_topk_final_span(); });
   m.def("topk_select", [](const std::vector<std::tuple<double, double, double, double, int32_t>>& win_rows,

@@ -511,6 +511,61 @@ struct PeerTextArgs {
   uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
   char* out;                    // at least apm_peer_row_bound(max name bytes) * n bytes
 };
+// K24 ls rows: latency shifts of a series' newest buckets against the rest of its own window,
+// decided on the device (shift.hip, docs/SHIFT.md).  A class is one gate minDelta (ms); class 0 is
+// "no row".  Over the window K8 just read (the same WindowArgs) the value pass splits the entries,
+// per rule j, into the recent span (rw's span: the entries r >= n_win - min(span[j], n_win)) and the
+// baseline (the others), finds twice the percentile q[j] of each side's finite samples (K16's rank
+// rule) and the recent finite samples strictly above / below the baseline's, decides the rule with
+// shift_verdict (shiftcmp.h) and writes one record per series; the text pass prints, per emission
+// position of a series with a verdict other than N:
+//   ls|<edge ts>|server|service|<n>|<minDelta>|<k>:<p>:<mB>:<T2>:<mR>:<X2>:<a>:<b>:<U|D|N>,...
+constexpr int LS_MAX_RULES = 4;
+struct ShiftRec {
+  int32_t n;                    // WinStat.n of the series
+  int32_t verdict;              // bits 2j, 2j + 1: rule j's verdict (LS_N / LS_U / LS_D)
+  int32_t mB[LS_MAX_RULES], nanB[LS_MAX_RULES];  // per rule: finite / ELAPSED_NAN samples of the baseline
+  int32_t mR[LS_MAX_RULES], nanR[LS_MAX_RULES];  // ... of the recent span
+  int32_t a[LS_MAX_RULES], b[LS_MAX_RULES];      // ... recent finite samples v with 2 v > T2 / 2 v < T2
+  long long T2[LS_MAX_RULES];   // ... twice the baseline's percentile (0: no finite sample), |T2| < 2^32
+  long long X2[LS_MAX_RULES];   // ... twice the recent span's
+};
+struct ShiftArgs {
+  WindowArgs w;                 // K8's arguments of this rollover (w.out = K8's result)
+  const int32_t* cls;           // [S] class per series (0 or out of range: no row)
+  const int32_t* delta;         // [n_classes] minDelta (class 0: unused)
+  int32_t n_classes;
+  int32_t nrule;                // 1 .. LS_MAX_RULES
+  int32_t span[LS_MAX_RULES];   // buckets per rule, ascending (not strictly), 1 .. 64
+  int32_t q[LS_MAX_RULES];      // percentile * 1000, 1 .. 99999
+  int32_t up[LS_MAX_RULES];     // r_u = up * 1000, 1001 .. 1000000 (0: no up test)
+  int32_t down[LS_MAX_RULES];   // r_d = down * 1000, 1001 .. 1000000 (0: no down test)
+  int32_t z[LS_MAX_RULES];      // z * 1000, 0 .. 100000
+  int32_t min_recent;           // >= 1
+  int32_t min_baseline;         // >= 2
+  ShiftRec* rec;                // [S]
+  int32_t* big_list;            // [S] series deferred to the block pass
+  int32_t* big_n;
+};
+struct ShiftTextArgs {
+  const ShiftRec* rec;          // [S]
+  const int32_t* cls;           // [S]
+  const int32_t* delta;         // [n_classes]
+  int32_t n_classes;
+  const int32_t* perm;          // [n] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;
+  int32_t n_series;
+  int32_t nrule;
+  int32_t span[LS_MAX_RULES];
+  char ptxt[LS_MAX_RULES][8];   // "<p>:" per rule (at most "99.999:")
+  int32_t plen[LS_MAX_RULES];
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_shift_row_bound(max name bytes) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -712,6 +767,19 @@ void apm_peer_values(apm::PeerArgs* a, hipStream_t stream);
 // length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_peer_plan(apm::PeerTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_peer_write(apm::PeerTextArgs* a, hipStream_t stream);
+// shift.hip
+// the value pass' two paths (tests bracket them): a series whose window has at most
+// apm_shift_group_win() buckets and holds at most apm_shift_group_max() samples stays in its
+// 32-lane group, every other one is selected by a block
+int32_t apm_shift_group_max();
+int32_t apm_shift_group_win();
+size_t apm_shift_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes
+size_t apm_shift_row_bound(size_t name_bytes);
+void apm_shift_values(apm::ShiftArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_shift_plan(apm::ShiftTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_shift_write(apm::ShiftTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

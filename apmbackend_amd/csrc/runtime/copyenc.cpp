@@ -268,8 +268,8 @@ void append_pct_pairs(std::string& js, std::string_view rest) {
 }
 
 // Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw, 11 sb, 12 tf,
-// 13 po) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[14]*/) {
+// 13 po, 14 ls) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[15]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -642,6 +642,79 @@ int encode_line(std::string_view line, std::string* out /*[14]*/) {
     o += a.f[9];
     o += '\n';
     return 13;
+  }
+  if (t == "ls") {  // latency shift: timestamp, server, service, count, min_delta, rules json
+    // (utils/records.py entry_from_csv and shift_rules_from_text hold the same rules) a row is dropped
+    // whole unless it has exactly seven fields, n and minDelta are 1 to 10 plain digits and the last
+    // field is 1 to 4 groups k:p:mB:T2:mR:X2:a:b:V -- k, mB, mR, a, b 1 to 10 plain digits, p a
+    // percentile of at most three decimals below 100, T2 and X2 1 to 10 digits after an optional '-',
+    // V one of U, D, N
+    if (a.n != 7) return -1;
+    for (int i = 4; i <= 5; ++i)
+      if (!all_digits(a.f[i], 10)) return -1;
+    if (a.f[6].empty()) return -1;
+    std::string js = "[";
+    {
+      static const char* key[9] = {"{\"k\":", ",\"p\":", ",\"base\":", ",\"t2\":", ",\"recent\":", ",\"x2\":",
+                                   ",\"above\":", ",\"below\":", ",\"verdict\":"};
+      std::string_view rest = a.f[6];
+      int groups = 0;
+      for (;;) {
+        const size_t e = rest.find(',');
+        std::string_view g = rest.substr(0, e);
+        if (++groups > 4) return -1;
+        if (groups > 1) js += ',';
+        for (int p = 0; p < 9; ++p) {
+          const size_t c = g.find(':');
+          if ((p < 8) == (c == std::string_view::npos)) return -1;  // (exactly nine parts)
+          std::string_view part = g.substr(0, c);
+          js += key[p];
+          if (p == 8) {
+            if (part != "U" && part != "D" && part != "N") return -1;
+            js += '"';
+            js += part;
+            js += '"';
+          } else if (p == 1) {
+            const int64_t q = pct_from_text(part);
+            if (q < 0 || q > 99999) return -1;
+            js += '"';
+            append_i64(js, q / 1000);  // (the canonical text again: q / 1000 without trailing zeros)
+            if (q % 1000) {
+              char fr[4] = {(char)('0' + q % 1000 / 100), (char)('0' + q % 100 / 10), (char)('0' + q % 10), 0};
+              int n = 3;
+              while (fr[n - 1] == '0') --n;
+              js += '.';
+              js.append(fr, (size_t)n);
+            }
+            js += '"';
+          } else {
+            const bool neg = (p == 3 || p == 5) && !part.empty() && part[0] == '-';
+            if (neg) part.remove_prefix(1);
+            if (!all_digits(part, 10)) return -1;
+            int64_t v = 0;
+            for (char ch : part) v = v * 10 + (ch - '0');
+            append_i64(js, neg ? -v : v);
+          }
+          if (p < 8) g = g.substr(c + 1);
+        }
+        js += '}';
+        if (e == std::string_view::npos) break;
+        rest = rest.substr(e + 1);
+      }
+    }
+    js += ']';
+    std::string& o = out[14];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    for (int i = 4; i <= 5; ++i) {
+      int64_t v = 0;
+      for (char ch : a.f[i]) v = v * 10 + (ch - '0');
+      append_i64(o, v); o += '\t';
+    }
+    copy_escape(o, js);
+    o += '\n';
+    return 14;
   }
   if (t == "jx") {
     std::string& o = out[3];

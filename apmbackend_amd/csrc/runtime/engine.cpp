@@ -324,6 +324,29 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
                                   "name one; po_high 0 or 1001 .. 1000000, po_low 0 or 1 .. 999 (not both 0), po_z 0 .. 100000, "
                                   "po_min_delta >= 0, po_min_peers >= 3, po_min_samples >= 1");
   }
+  if (want(OUT_LS)) {  // K24: likewise
+    const auto& cl = cfg_.ls_classes;
+    bool ok = cl.size() >= 2 && cl[0].empty() && cl.size() <= (size_t)cfg_.max_series + 2;
+    for (size_t c = 1; ok && c < cl.size(); ++c) ok = cl[c].size() == 1 && cl[c][0] >= 1 && cl[c][0] <= 1073741823;
+    const auto in_range = [&](int32_t c) { return c >= 0 && (size_t)c < cl.size(); };
+    ok = ok && in_range(cfg_.ls_default);
+    for (const auto& kv : cfg_.ls_services) ok = ok && in_range(kv.second);
+    const int nr = cfg_.n_ls_rules;
+    ok = ok && nr >= 1 && nr <= LS_MAX_RULES && cfg_.ls_min_recent >= 1 && cfg_.ls_min_baseline >= 2;
+    for (int j = 0; ok && j < nr; ++j) {
+      const int32_t u = cfg_.ls_up[j], d = cfg_.ls_down[j], k = cfg_.ls_short[j], q = cfg_.ls_pct[j];
+      ok = k >= 1 && k <= std::min(64, cfg_.window) && q >= 1 && q <= 99999 && (j == 0 || k >= cfg_.ls_short[j - 1]) &&
+           (u == 0 || (u >= 1001 && u <= 1000000)) && (d == 0 || (d >= 1001 && d <= 1000000)) && (u != 0 || d != 0) &&
+           cfg_.ls_z[j] >= 0 && cfg_.ls_z[j] <= 100000;
+      for (int o = 0; ok && o < j; ++o) ok = cfg_.ls_short[o] != k || cfg_.ls_pct[o] != q;
+    }
+    if (!ok)
+      throw std::invalid_argument("ls stream: ls_classes must hold the empty class 0 and at least one gate {minDelta in 1 .. "
+                                  "1073741823}, every class index must name one; ls_short / ls_pct must hold 1 to 4 rules, "
+                                  "(span in 1 .. min(64, window), ascending; percentile in 1 .. 99999; no pair twice), ls_up "
+                                  "and ls_down 0 or 1001 .. 1000000 (not both 0), ls_z 0 .. 100000, ls_min_recent >= 1, "
+                                  "ls_min_baseline >= 2");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -597,6 +620,20 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     d_po_rec_ = (PeerRec*)res_.dmalloc((size_t)S * sizeof(PeerRec));
     text_alloc(po_, OUT_PO, apm_peer_tmp_bytes(S));
   }
+  if (want(OUT_LS)) {  // K24
+    const int32_t C = (int32_t)cfg_.ls_classes.size();  // (checked at the top of the constructor)
+    n_ls_classes_ = C;
+    d_ls_delta_ = (int32_t*)res_.dmalloc((size_t)C * 4);
+    {
+      std::vector<int32_t> tab((size_t)C, 0);
+      for (int32_t c = 1; c < C; ++c) tab[(size_t)c] = (int32_t)cfg_.ls_classes[c][0];
+      HIP_OK(hipMemcpy(d_ls_delta_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    }
+    d_ls_cls_ = (int32_t*)res_.dmalloc((size_t)S * 4);
+    HIP_OK(hipMemset(d_ls_cls_, 0, (size_t)S * 4));  // class 0 until a series' class is uploaded
+    d_ls_rec_ = (ShiftRec*)res_.dmalloc((size_t)S * sizeof(ShiftRec));
+    text_alloc(ls_, OUT_LS, apm_shift_tmp_bytes(S));
+  }
   if (want(OUT_LH)) text_alloc(lh_, OUT_LH, apm_hist_tmp_bytes(S));  // K15
   {
     const char* f = std::getenv("APM_TXCOPY_FORCE_FALLBACK");
@@ -832,6 +869,7 @@ int32_t Engine::series_for(int32_t server, int32_t service) {
   if (want(OUT_SB)) h_sb_cls_.push_back(burn_class_of(s));  // K21: likewise
   if (want(OUT_TF)) h_tf_cls_.push_back(traffic_class_of(s));  // K22: likewise
   if (want(OUT_PO)) h_po_cls_.push_back(peer_class_of(s));  // K23: likewise
+  if (want(OUT_LS)) h_ls_cls_.push_back(shift_class_of(s));  // K24: likewise
   h_suppressed_.push_back(0);
   zscore_seen_.push_back(0);
   h_active_.push_back(0);
@@ -884,6 +922,12 @@ int32_t Engine::peer_class_of(int32_t s) const {
   return it != cfg_.po_services.end() ? it->second : cfg_.po_default;
 }
 
+// K24: the same rule over the ls stream's own tables
+int32_t Engine::shift_class_of(int32_t s) const {
+  auto it = cfg_.ls_services.find(dict_.service_name(series_[s].service));
+  return it != cfg_.ls_services.end() ? it->second : cfg_.ls_default;
+}
+
 void Engine::refresh_series_settings() {
   flush();
   // config hot reload (updateAllServiceSettings, stream_calc_z_score.js:152-167)
@@ -928,6 +972,7 @@ void Engine::upload_series_tables(int32_t lo) {
   if (want(OUT_SB)) upload_burn_classes(lo);
   if (want(OUT_TF)) upload_traffic_classes(lo);
   if (want(OUT_PO)) upload_peer_classes(lo);
+  if (want(OUT_LS)) upload_shift_classes(lo);
 }
 
 // K17: the classes of series [lo, n) to the device, on the stats stream.  A full upload (lo == 0: a
@@ -1006,6 +1051,25 @@ void Engine::upload_peer_classes(int32_t lo) {
     stage_done();
   }
   po_cls_uploaded_ = n;
+}
+
+// K24: upload_slo_classes over the ls stream's own class array
+void Engine::upload_shift_classes(int32_t lo) {
+  const int32_t n = n_series_;
+  lo = std::min(lo, ls_cls_uploaded_);  // (series no earlier upload carried go along)
+  if (lo == 0 || h_ls_cls_.size() != (size_t)n) {
+    h_ls_cls_.resize((size_t)n);
+    for (int32_t s = 0; s < n; ++s) h_ls_cls_[s] = shift_class_of(s);
+    lo = 0;
+  }
+  if (n > lo) {
+    const size_t mc = (size_t)(n - lo);
+    int32_t* cs = (int32_t*)stage(mc * 4);
+    std::memcpy(cs, h_ls_cls_.data() + lo, mc * 4);
+    h2d(d_ls_cls_ + lo, cs, mc * 4, stream_);
+    stage_done();
+  }
+  ls_cls_uploaded_ = n;
 }
 
 std::vector<uint64_t> Engine::cache_stats(bool drain) {
@@ -1692,6 +1756,8 @@ void Engine::flush() {
     tf_rows_lane_ = 0;
     metrics_.po_rows += po_rows_lane_;
     po_rows_lane_ = 0;
+    metrics_.ls_rows += ls_rows_lane_;
+    ls_rows_lane_ = 0;
     if (!out_error_.empty()) { std::string e = out_error_; out_error_.clear(); throw std::runtime_error(e); }
   }
   if (!st_error_.empty()) { std::string e = st_error_; st_error_.clear(); throw std::runtime_error(e); }
@@ -2632,6 +2698,9 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   // what K16 reads -- window cells, counts, the sorted spill lists, d_win_ -- nothing queued since
   // K8 writes any of them, and the next append follows on this stream.
   if (want(OUT_RW)) recent_rollover(wa, edge_ts);
+  // K24: behind K20, for K16's reason once more: it reads only what K16 reads (window cells, counts,
+  // the sorted spill lists, d_win_) and its own class array, and writes buffers of its own.
+  if (want(OUT_LS)) shift_rollover(wa, edge_ts);
   // K21: last of all, for the same reason: it reads what K17 reads (window cells, counts, spill
   // lists, d_win_) and its own class array, and the next append follows on this stream.
   if (want(OUT_SB)) burn_rollover(wa, edge_ts);
@@ -2794,8 +2863,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[14];
-        int64_t counts[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::string enc[15];
+        int64_t counts[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3217,7 +3286,7 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   });
 }
 
-// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb, tf, po): buffers and the slot protocol, once.
+// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb, tf, po, ls): buffers and the slot protocol, once.
 // `rows`: text lanes per series (rw prints one row per span).
 void Engine::text_alloc(TextStream& t, int kind, size_t tmp_bytes, int rows) {
   const size_t S = (size_t)cfg_.max_series;
@@ -3272,6 +3341,12 @@ void Engine::text_end(TextStream& t, int32_t n) {
       const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
       std::lock_guard<std::mutex> g(out_mu_);
       po_rows_lane_ += rows;
+    }
+    if (ts->kind == OUT_LS) {  // (likewise)
+      const char* p = ts->text[k];
+      const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
+      std::lock_guard<std::mutex> g(out_mu_);
+      ls_rows_lane_ += rows;
     }
     emit_bytes(ts->kind, ts->text[k], total);
   });
@@ -3854,6 +3929,78 @@ void Engine::download_peers(std::vector<PeerRec>& rec) {
   HIP_OK(hipStreamSynchronize(stream_));
 }
 
+// ---- K24: ls rows.  Per st row whose service has a minDelta and for which a rule says up or down,
+// one row, in st order with the st rows' timestamp: value pass over K8's window (the rules are
+// decided on the device), then count / scan / write of the text -- the length pass is the
+// compaction, only the rows' bytes reach the host.
+void Engine::shift_rollover(const WindowArgs& wa, int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();
+  // (series whose settings no upload_series_tables() carried yet: as slo_rollover)
+  if (ls_cls_uploaded_ < n) upload_shift_classes(ls_cls_uploaded_);
+  const int nr = cfg_.n_ls_rules;
+  ShiftArgs va{};
+  va.w = wa;
+  va.cls = d_ls_cls_;
+  va.delta = d_ls_delta_;
+  va.n_classes = n_ls_classes_;
+  va.nrule = nr;
+  for (int j = 0; j < nr; ++j) {
+    va.span[j] = cfg_.ls_short[j];
+    va.q[j] = cfg_.ls_pct[j];
+    va.up[j] = cfg_.ls_up[j];
+    va.down[j] = cfg_.ls_down[j];
+    va.z[j] = cfg_.ls_z[j];
+  }
+  va.min_recent = cfg_.ls_min_recent;
+  va.min_baseline = cfg_.ls_min_baseline;
+  va.rec = d_ls_rec_;
+  va.big_list = ls_.big;
+  va.big_n = ls_.big + cfg_.max_series;
+  apm_shift_values(&va, stream_);
+  ls_last_n_ = n;
+  ShiftTextArgs ta{};
+  ta.rec = d_ls_rec_;
+  ta.cls = d_ls_cls_;
+  ta.delta = d_ls_delta_;
+  ta.n_classes = n_ls_classes_;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n;
+  ta.n_series = n;
+  ta.nrule = nr;
+  for (int j = 0; j < nr; ++j) {
+    ta.span[j] = cfg_.ls_short[j];
+    ta.plen[j] = pct_label(ta.ptxt[j], cfg_.ls_pct[j]);  // (as K16 prints it)
+  }
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  ta.len = ls_.len;
+  ta.off = ls_.off;
+  // the output bound needs no length pass: every row is at most apm_shift_row_bound bytes
+  ta.out = text_begin(ls_, (size_t)n * apm_shift_row_bound(max_name_len_) + 64);
+  if (apm_shift_plan(&ta, ls_.tmp, ls_.tmp_bytes, stream_) != 0) throw std::runtime_error("shift scan failed");
+  apm_shift_write(&ta, stream_);
+  text_end(ls_, n);
+}
+
+void Engine::download_shifts(std::vector<ShiftRec>& rec, std::vector<uint8_t>& has) {
+  rec.clear(); has.clear();
+  const int32_t n = ls_last_n_;
+  if (!want(OUT_LS) || n == 0) return;
+  rec.resize((size_t)n);
+  std::vector<WinStat> win((size_t)n);
+  std::vector<int32_t> cls((size_t)n);
+  HIP_OK(hipMemcpyAsync(rec.data(), d_ls_rec_, rec.size() * sizeof(ShiftRec), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(win.data(), d_win_, win.size() * sizeof(WinStat), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipMemcpyAsync(cls.data(), d_ls_cls_, cls.size() * 4, hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+  has.resize((size_t)n);
+  for (int32_t s = 0; s < n; ++s)
+    has[(size_t)s] = win[(size_t)s].active && cls[(size_t)s] > 0 && cls[(size_t)s] < n_ls_classes_;
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -3994,7 +4141,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls"};
   return n[k];
 }
 

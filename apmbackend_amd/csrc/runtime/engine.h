@@ -179,6 +179,22 @@ struct EngineConfig {
   int32_t po_default = 0;
   int32_t po_high = 0, po_low = 0, po_z = 3000;
   int32_t po_min_delta = 0, po_min_peers = 5, po_min_samples = 20;
+  // ls stream (K24): the gate {minDelta} per class (class 0 = no row, an empty list; minDelta in
+  // 1 .. 1073741823 ms), the class of each named service and of every other one (sl's scheme), the
+  // rules (span in buckets, 1 .. 64 and at most window, ascending; q = percentile * 1000 in 1 .. 99999,
+  // no (span, q) pair twice; r_u = up * 1000 and r_d = down * 1000 in 1001 .. 1000000 or 0 =
+  // none, not both 0; z * 1000 in 0 .. 100000), minRecent >= 1 and minBaseline >= 2; read at
+  // construction (OUT_LS in `outputs` without valid tables is an error)
+  std::vector<std::vector<int64_t>> ls_classes;
+  std::map<std::string, int32_t> ls_services;
+  int32_t ls_default = 0;
+  int32_t n_ls_rules = 0;
+  int32_t ls_short[4] = {0, 0, 0, 0};
+  int32_t ls_pct[4] = {0, 0, 0, 0};
+  int32_t ls_up[4] = {0, 0, 0, 0};
+  int32_t ls_down[4] = {0, 0, 0, 0};
+  int32_t ls_z[4] = {0, 0, 0, 0};
+  int32_t ls_min_recent = 20, ls_min_baseline = 100;
   int async_stats = 1;      // overlap batch i's stats with batch i+1's parse + join
   // RCCL watchdog: a collective not complete after this long (a dead or wedged peer) aborts the
   // communicator and throws, so the supervisor restarts the rank group from its checkpoint
@@ -204,14 +220,14 @@ struct EngineConfig {
 //   FS            z -> alerts/db  fs lines (one per series per LAG)
 //   AL            alerts -> db    al lines
 //   SX            new: per-JVM rollup fused with JMX / VM gauges (K14), one line per server
-enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, OUT_SV, OUT_RW, OUT_SB, OUT_TF, OUT_PO, N_OUT };
+enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, OUT_SV, OUT_RW, OUT_SB, OUT_TF, OUT_PO, OUT_LS, N_OUT };
 // Streams whose pending text a checkpoint stores (checkpoint.cpp).  The version-9 layout holds
-// exactly these; lh, wp, sl, tk, sv, rw, sb, tf and po rows are taken by their consumer before a checkpoint and are not persisted.
+// exactly these; lh, wp, sl, tk, sv, rw, sb, tf, po and ls rows are taken by their consumer before a checkpoint and are not persisted.
 constexpr int N_OUT_CKPT = OUT_FB + 1;
-// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk, sv, rw, sb, tf, po); the stats thread owns the rest
+// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk, sv, rw, sb, tf, po, ls); the stats thread owns the rest
 constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP) |
                                 (1u << OUT_SL) | (1u << OUT_TK) | (1u << OUT_SV) | (1u << OUT_RW) | (1u << OUT_SB) | (1u << OUT_TF) |
-                                (1u << OUT_PO);
+                                (1u << OUT_PO) | (1u << OUT_LS);
 const char* out_kind_name(int k);
 int out_kind_of(const std::string& name);
 
@@ -282,6 +298,7 @@ struct EngineMetrics {
   uint64_t sb_rows = 0;             // K21: sb rows emitted (since construction or restore; not checkpointed)
   uint64_t tf_rows = 0;             // K22: tf rows emitted (likewise)
   uint64_t po_rows = 0;             // K23: po rows emitted (likewise)
+  uint64_t ls_rows = 0;             // K24: ls rows emitted (likewise)
   uint64_t series_overflow_tx = 0;  // tx whose series could not be created (gpu.maxSeries full)
   uint64_t spill_dropped = 0;       // samples lost to a full bucket spill list (gpu.bucketOverflowCapacity)
   uint64_t nan_windows_clipped = 0; // NaN windows larger than the JS-emulation scratch (percentiles clipped)
@@ -781,7 +798,7 @@ class Engine {
   std::mutex out_pool_mu_;
   bool st_has_job_ = false, st_busy_ = false, st_stop_ = false;
   std::string st_error_;
-  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk / sv / rw / sb / tf / po streams (kLaneKinds)
+  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk / sv / rw / sb / tf / po / ls streams (kLaneKinds)
   std::thread out_thread_;
   std::mutex out_mu_;
   std::condition_variable out_cv_;
@@ -1249,7 +1266,7 @@ class Engine {
   PinnedBuf<uint32_t> h_fs_off_[2];
   size_t fs_rows_[2] = {0, 0};
 
-  // A rollover stream whose rows are printed on the device (lh, wp, sl, sv, rw, sb, tf, po): the buffers of its
+  // A rollover stream whose rows are printed on the device (lh, wp, sl, sv, rw, sb, tf, po, ls): the buffers of its
   // count / scan / write text pass and two device / pinned text slots, as for st / fs.  A rollover
   // takes the other slot than the one before it; a slot is reused only after its output-lane task
   // is done, and the lane reads a slot's total only after the slot's event.  Allocated when the
@@ -1442,9 +1459,32 @@ class Engine {
   void download_peers(std::vector<PeerRec>& rec);
  private:
 
+  // K24 ls rows (shift.hip), allocated when the stream is on: per series the rules of its class
+  // decided over the newest buckets of the window K8 read against the rest of that window, one row
+  // per series with a verdict, queued behind K20.  The classes follow sl's scheme with a table of
+  // their own; no device state outlives a rollover.
+  int32_t* d_ls_delta_ = nullptr;                           // [C] minDelta per class
+  int32_t n_ls_classes_ = 0;
+  int32_t* d_ls_cls_ = nullptr;                             // [S]
+  std::vector<int32_t> h_ls_cls_;                           // its host mirror (stats thread)
+  ShiftRec* d_ls_rec_ = nullptr;                            // [S]
+  TextStream ls_;
+  int32_t ls_cls_uploaded_ = 0;                             // series whose class is on the device
+  int32_t ls_last_n_ = 0;                                   // series of the last rollover's value pass
+  uint64_t ls_rows_lane_ = 0;                               // rows the output lane emitted since the last flush()
+  int32_t shift_class_of(int32_t s) const;
+  void upload_shift_classes(int32_t lo);
+  void shift_rollover(const WindowArgs& wa, int64_t edge_ts);
+ public:
+  // (tests) the value pass' result of the last rollover: per series its record, and whether the
+  // series had one at all (an st row and a class other than 0)
+  void download_shifts(std::vector<ShiftRec>& rec, std::vector<uint8_t>& has);
+  int32_t ls_nrule() const { return cfg_.n_ls_rules; }
+ private:
+
   // text outputs
   std::string blob_[N_OUT];
-  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   std::shared_ptr<ByteSink> byte_sink_[N_OUT];
   bool fs_copy_ = false;
   bool db_copy_ = false;
@@ -1453,7 +1493,7 @@ class Engine {
   void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
-  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // K14 server rollup + exogenous context
   std::vector<double> h_ctx_;                    // [servers][CTX_FIELDS] (stats thread)
   bool ctx_dirty_ = false;

@@ -27,11 +27,11 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import (as_bool, check_peer_outliers, check_recent_windows, check_slo_burn, check_traffic_watch,
+from ..utils.config import (as_bool, check_latency_shift, latency_shift, check_peer_outliers, check_recent_windows, check_slo_burn, check_traffic_watch,
                             gpu_opt, peer_outliers, slo_burn,
                             latency_objectives, leaderboard, recent_windows, service_window, traffic_watch,
                             window_percentiles, zscore_lag_settings)
-from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LeaderboardEntry, PeerEntry, RecentWindowEntry,
+from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LatencyShiftEntry, LeaderboardEntry, PeerEntry, RecentWindowEntry,
                              ServiceWindowEntry, SloBurnEntry, TrafficEntry,
                              StatEntry, TxEntry, WindowPctEntry, WindowSloEntry, entry_from_csv, hist_bin, hist_lower,
                              pct_ranks)
@@ -682,7 +682,10 @@ class StatsOracle:
                  recent_percentiles: Iterable[int] = (),
                  emit_burn: Optional[Callable[[str], None]] = None, burn: Optional[Dict[str, Any]] = None,
                  emit_traffic: Optional[Callable[[str], None]] = None, traffic: Optional[Dict[str, Any]] = None,
-                 emit_peer: Optional[Callable[[str], None]] = None, peer: Optional[Dict[str, Any]] = None):
+                 emit_peer: Optional[Callable[[str], None]] = None, peer: Optional[Dict[str, Any]] = None,
+                 emit_shift: Optional[Callable[[str], None]] = None, shift: Optional[Dict[str, Any]] = None):
+        self.emit_shift = emit_shift  # ls rows (docs/SHIFT.md); None = stream off
+        self.shift = shift            # config.parse_latency_shift's result
         self.emit_peer = emit_peer  # po rows (docs/PEERS.md); None = stream off
         self.peer = peer            # config.parse_peer_outliers's result
         self.emit_traffic = emit_traffic  # tf rows (docs/TRAFFIC.md); None = stream off
@@ -983,6 +986,60 @@ class StatsOracle:
                 rows.append(PeerEntry(edge_ts, server, service, m, po["percentile"], x, E, X2, D4, v).to_csv())
         return rows
 
+    @staticmethod
+    def shift_rule(base: List[Any], recent: List[Any], q: int, r_u: int, r_d: int, z: int, min_delta: int,
+                   min_recent: int, min_baseline: int) -> Tuple[int, int, int, int, int, int, str]:
+        """(mB, T2, mR, X2, a, b, verdict) of one rule over the samples of the baseline buckets and of the
+        recent span: the share of recent samples beyond the baseline's percentile against the share the
+        percentile predicts, in integers (docs/SHIFT.md)."""
+        S = 100000
+        # the engine stores int32; anything else is its NaN sentinel (engine.cpp)
+        fb = sorted(int(v) for v in base if v == v and -2147483647 <= v <= 2147483647)
+        fr = sorted(int(v) for v in recent if v == v and -2147483647 <= v <= 2147483647)
+        mB, mR = len(fb), len(fr)
+        T2 = X2 = a = b = 0
+        if mB:
+            lo, hi = pct_ranks(mB, q)
+            T2 = fb[lo] + fb[hi]
+            a = sum(1 for v in fr if 2 * v > T2)
+            b = sum(1 for v in fr if 2 * v < T2)
+        if mR:
+            lo, hi = pct_ranks(mR, q)
+            X2 = fr[lo] + fr[hi]
+        verdict = "N"
+        if mB >= min_baseline and mR >= min_recent:
+            var = z * z * mR * q * (S - q)
+            if (r_u and X2 - T2 >= 2 * min_delta and 1000 * a * S >= r_u * mR * (S - q) and a * S >= mR * (S - q)
+                    and (a * S - mR * (S - q)) ** 2 * 10 ** 6 >= var):
+                verdict = "U"
+            elif (r_d and T2 - X2 >= 2 * min_delta and 1000 * b * S >= r_d * mR * q and b * S >= mR * q
+                    and (b * S - mR * q) ** 2 * 10 ** 6 >= var):
+                verdict = "D"
+        return mB, T2, mR, X2, a, b, verdict
+
+    def shift_row(self, edge_ts: int, server: str, service: str, svc: Dict[int, List[int]]) -> Optional[str]:
+        """The ls row of one series with an st row: None unless its service has a minDelta and at least
+        one rule says U or D.  Rule (k, q, ...) sets the newest min(k, window buckets) buckets against
+        the other buckets of the window."""
+        named = self.shift["services"]
+        min_delta = named[service] if service in named else self.shift["default"]  # (named with null: no row)
+        if min_delta is None:
+            return None
+        newest = self.latest - self.buffer
+        oldest = self.latest - self.keep
+        n_win = self.keep - self.buffer + 1
+        rules = []
+        for k, q, r_u, r_d, z in self.shift["rules"]:
+            lo = newest - min(k, n_win)
+            base = [v for bk in sorted(svc) if oldest <= bk <= lo for v in svc[bk]]
+            recent = [v for bk in sorted(svc) if lo < bk <= newest for v in svc[bk]]
+            rules.append((k, q) + self.shift_rule(base, recent, q, r_u, r_d, z, min_delta, self.shift["minRecent"],
+                                                  self.shift["minBaseline"]))
+        if all(r[8] == "N" for r in rules):
+            return None
+        n = sum(len(svc[bk]) for bk in svc if oldest <= bk <= newest)
+        return LatencyShiftEntry(edge_ts, server, service, n, min_delta, rules).to_csv()
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -1045,6 +1102,10 @@ class StatsOracle:
                         self.emit_traffic(row)
                 if self.emit_peer is not None:
                     peer_members.append((server, service) + self.peer_member(win))
+                if self.emit_shift is not None:
+                    row = self.shift_row(edge_ts, server, service, svc)
+                    if row is not None:
+                        self.emit_shift(row)
         if self.emit_top is not None:
             for row in self.top_rows(st_rows):
                 self.emit_top(row)
@@ -1289,6 +1350,7 @@ class PipelineOracle:
         self.sb: List[str] = []
         self.tf: List[str] = []
         self.po: List[str] = []
+        self.ls: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1300,6 +1362,7 @@ class PipelineOracle:
         check_slo_burn(slo_burn(cfg), int(sc["windowSizeInIntervals"]))  # (likewise)
         check_traffic_watch(traffic_watch(cfg), int(sc["windowSizeInIntervals"]))  # (likewise)
         check_peer_outliers(peer_outliers(cfg))
+        check_latency_shift(latency_shift(cfg), int(sc["windowSizeInIntervals"]))  # (as check_traffic_watch)
         self.st = StatsOracle(self._on_st, self.tx_db.append, int(sc["intervalLengthInSeconds"]),
                               int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
                               emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None,
@@ -1316,7 +1379,8 @@ class PipelineOracle:
                               recent_percentiles=(recent_windows(cfg) or {}).get("percentiles", ()),
                               emit_burn=self.emit_burn if slo_burn(cfg) else None, burn=slo_burn(cfg),
                               emit_traffic=self.tf.append if traffic_watch(cfg) else None, traffic=traffic_watch(cfg),
-                              emit_peer=self.po.append if peer_outliers(cfg) else None, peer=peer_outliers(cfg))
+                              emit_peer=self.po.append if peer_outliers(cfg) else None, peer=peer_outliers(cfg),
+                              emit_shift=self.ls.append if latency_shift(cfg) else None, shift=latency_shift(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

@@ -73,12 +73,15 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
     # peer-outlier servers per service (po records, gpu.peerOutliers): likewise
     "po": ("dbPeerTable", ["timestamp", "server", "service", "count", "pct", "value2", "peers", "median2x2", "mad4",
                            "verdict"]),
+    # latency shifts against the window's own past (ls records, gpu.latencyShift): likewise
+    "ls": ("dbShiftTable", ["timestamp", "server", "service", "count", "min_delta", "rules"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls")
 # tables of the record types the reference does not know (its config has no key for them)
 DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct", "sl": "apm_window_slo",
                   "tk": "apm_leaderboard", "sv": "apm_service_window", "rw": "apm_recent_window",
-                  "sb": "apm_slo_burn", "tf": "apm_traffic", "po": "apm_peer_outlier"}
+                  "sb": "apm_slo_burn", "tf": "apm_traffic", "po": "apm_peer_outlier",
+                  "ls": "apm_latency_shift"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -166,7 +169,7 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
         elif c in ("stats", "entry", "bins", "pcts", "le", "rules"):
             out[c] = json.loads(v)
-        elif c in ("servers", "buckets", "elapsed_sum", "threshold", "target_q", "bad", "min_rate", "value2", "peers", "median2x2", "mad4"):  # (sv, rw, sb: plain integers; the sum may pass 2^53)
+        elif c in ("servers", "buckets", "elapsed_sum", "threshold", "target_q", "bad", "min_rate", "min_delta", "value2", "peers", "median2x2", "mad4"):  # (sv, rw, sb: plain integers; the sum may pass 2^53)
             out[c] = int(v)
         elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan", "rank", "average", "per75", "per95") or rtype == "jx" and c not in ("server",):
             f = float(v)

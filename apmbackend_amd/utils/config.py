@@ -104,6 +104,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "trafficQueue": "traffic",        # amqp mode: the queue the tf records go to
     "peerOutliers": None,             # K23 "po" stream: servers whose window percentile lies far from the median over the servers of the same service, {"percentile": 95, "default": {"minValue": 20}, "services": {...}, "high": 2, "low": 0.25, "z": 3, "minDelta": 10, "minPeers": 5, "minSamples": 20} (docs/PEERS.md)
     "peerQueue": "peer_outliers",     # amqp mode: the queue the po records go to
+    "latencyShift": None,             # K24 "ls" stream: latency shifts of a series' newest buckets against the rest of its own window, {"default": {"minDelta": 50}, "services": {...}, "rules": [{"short": 6, "percentile": 95, "up": 3, "z": 4}], "minRecent": 20, "minBaseline": 100} (docs/SHIFT.md)
+    "shiftQueue": "latency_shift",    # amqp mode: the queue the ls records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -745,6 +747,156 @@ def peer_tables(po: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[str
     return classes, services, default_class
 
 
+SHIFT_MAX_RULES = 4         # kernel_api.h LS_MAX_RULES
+SHIFT_SHORT_MAX = 64        # buckets of a rule's recent span
+SHIFT_DELTA_MAX = 1073741823  # 2 minDelta stays an int32
+SHIFT_Z_DEFAULT = 3000      # z * 1000
+
+
+def _shift_decimal(where: str, p: Any, lo: int, hi: int) -> int:
+    """A decimal with at most three places as the integer ``p * 1000`` in lo .. hi, read from its
+    text (never through float arithmetic), as _traffic_decimal."""
+    if isinstance(p, bool) or not isinstance(p, (int, float, str, decimal.Decimal)):
+        raise ValueError(f"gpu.latencyShift: {where}: {p!r} is not a number")
+    try:
+        d = decimal.Decimal(repr(p) if isinstance(p, float) else str(p).strip())
+    except decimal.InvalidOperation:
+        raise ValueError(f"gpu.latencyShift: {where}: {p!r} is not a number") from None
+    if not d.is_finite():
+        raise ValueError(f"gpu.latencyShift: {where}: {p!r} is not finite")
+    q = d * 1000
+    if q != q.to_integral_value():
+        raise ValueError(f"gpu.latencyShift: {where}: {p!r} has more than three decimals")
+    q = int(q)
+    if not lo <= q <= hi:
+        raise ValueError(f"gpu.latencyShift: {where}: {p!r} is outside {lo / 1000:g} .. {hi / 1000:g}")
+    return q
+
+
+def _shift_int(where: str, v: Any, lo: int, hi: int = SLO_T_MAX) -> int:
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError(f"gpu.latencyShift: {where} {v!r} is not an integer")
+    if not lo <= v <= hi:
+        raise ValueError(f"gpu.latencyShift: {where} {v!r} is outside {lo} .. {hi}")
+    return int(v)
+
+
+def _parse_shift_class(where: str, v: Any) -> Optional[int]:
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.latencyShift: {where} must be an object with 'minDelta' (or null), got {v!r}")
+    extra = set(v) - {"minDelta"}
+    if extra:
+        raise ValueError(f"gpu.latencyShift: {where}: unknown key(s) {sorted(extra, key=str)!r}")
+    if "minDelta" not in v:
+        raise ValueError(f"gpu.latencyShift: {where} needs 'minDelta', got {v!r}")
+    return _shift_int(f"{where}: minDelta", v["minDelta"], 1, SHIFT_DELTA_MAX)
+
+
+def parse_latency_shift(v: Any) -> Optional[Dict[str, Any]]:
+    """gpu.latencyShift -> {"default": minDelta | None, "services": {name: minDelta | None},
+    "rules": [(short, q, r_u, r_d, z), ...], "minRecent": n, "minBaseline": n}.  ``minDelta`` is a
+    JSON integer in 1 .. 1073741823 (bool, float and str are rejected); ``default`` may be absent or
+    null, a service named with null gets no rows.  ``rules``: 1 to 4 objects {"short": k,
+    "percentile": p, "up": x, "down": y, "z": w} with ``short`` ascending and no (short, percentile)
+    pair twice (one span may be judged at several percentiles, in any order); ``short`` a JSON integer in 1 .. 64 (its bound against the window is the engine's,
+    check_latency_shift); ``percentile`` one entry by parse_window_percentiles' rules, q = p * 1000 in
+    1 .. 99999; ``up`` and ``down`` decimals with at most three places, r * 1000 in 1001 .. 1000000,
+    at least one of the two (the missing one is 0 in the result); ``z`` likewise, z * 1000 in
+    0 .. 100000, default 3.  ``minRecent``: a JSON integer >= 1 (default 20); ``minBaseline``: >= 2
+    (default 100).  None, or an object in which no service has a minDelta -> None (stream off);
+    anything else raises ValueError."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.latencyShift: an object with 'default' and / or 'services', and 'rules', got {v!r}")
+    extra = set(v) - {"default", "services", "rules", "minRecent", "minBaseline"}
+    if extra:
+        raise ValueError(f"gpu.latencyShift: unknown key(s) {sorted(extra, key=str)!r}")
+    default = _parse_shift_class("default", v.get("default"))
+    services = v.get("services")
+    if services is None:
+        services = {}
+    if not isinstance(services, dict):
+        raise ValueError(f"gpu.latencyShift: services must be an object, got {services!r}")
+    named: Dict[str, Optional[int]] = {}
+    for name, o in services.items():
+        if not isinstance(name, str):
+            raise ValueError(f"gpu.latencyShift: service name {name!r} is not a string")
+        named[name] = _parse_shift_class(f"services[{name!r}]", o)
+    rules = v.get("rules")
+    if not isinstance(rules, list) or not 1 <= len(rules) <= SHIFT_MAX_RULES:
+        raise ValueError(f"gpu.latencyShift: rules must list 1 to {SHIFT_MAX_RULES} rules, got {rules!r}")
+    out_rules: List[Tuple[int, int, int, int, int]] = []
+    for i, r in enumerate(rules):
+        if not isinstance(r, dict):
+            raise ValueError(f"gpu.latencyShift: rules[{i}] must be an object with 'short', 'percentile' and 'up' and / or 'down', got {r!r}")
+        extra = set(r) - {"short", "percentile", "up", "down", "z"}
+        if extra:
+            raise ValueError(f"gpu.latencyShift: rules[{i}]: unknown key(s) {sorted(extra, key=str)!r}")
+        if "short" not in r or "percentile" not in r or ("up" not in r and "down" not in r):
+            raise ValueError(f"gpu.latencyShift: rules[{i}] needs 'short', 'percentile' and at least one of 'up' and 'down', got {r!r}")
+        k = r["short"]
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= SHIFT_SHORT_MAX:
+            raise ValueError(f"gpu.latencyShift: rules[{i}]: short must be an integer in 1 .. {SHIFT_SHORT_MAX}, got {k!r}")
+        try:
+            qs = parse_window_percentiles([r["percentile"]])
+        except ValueError as e:
+            raise ValueError(str(e).replace("gpu.windowPercentiles", f"gpu.latencyShift: rules[{i}]: percentile")) from None
+        if len(qs) != 1 or qs[0] >= PCT_SCALE:
+            raise ValueError(f"gpu.latencyShift: rules[{i}]: percentile {r['percentile']!r} is outside (0, 100)")
+        q = qs[0]
+        if out_rules and (int(k) < out_rules[-1][0] or any((int(k), q) == o[:2] for o in out_rules)):
+            raise ValueError(f"gpu.latencyShift: rules[{i}]: short {k!r} descends, or (short, percentile) "
+                             f"({k!r}, {r['percentile']!r}) stands twice")
+        ru = _shift_decimal(f"rules[{i}]: up", r["up"], 1001, 1000000) if "up" in r else 0
+        rd = _shift_decimal(f"rules[{i}]: down", r["down"], 1001, 1000000) if "down" in r else 0
+        z = _shift_decimal(f"rules[{i}]: z", r["z"], 0, 100000) if "z" in r else SHIFT_Z_DEFAULT
+        out_rules.append((int(k), q, ru, rd, z))
+    min_recent = _shift_int("minRecent", v.get("minRecent", 20), 1)
+    min_baseline = _shift_int("minBaseline", v.get("minBaseline", 100), 2)
+    if default is None and not any(o is not None for o in named.values()):
+        return None
+    return {"default": default, "services": named, "rules": out_rules, "minRecent": min_recent,
+            "minBaseline": min_baseline}
+
+
+def latency_shift(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """The validated gpu.latencyShift object of a config (None: off)."""
+    return parse_latency_shift(gpu_opt(cfg, "latencyShift"))
+
+
+def check_latency_shift(ls: Optional[Dict[str, Any]], window: int) -> None:
+    """The bound an engine puts on the rules' spans when it is constructed: at most
+    windowSizeInIntervals (as check_traffic_watch)."""
+    if ls and ls["rules"][-1][0] > int(window):
+        raise ValueError(f"gpu.latencyShift.rules: short at most windowSizeInIntervals ({int(window)}), "
+                         f"got {ls['rules'][-1][0]}")
+
+
+def shift_tables(ls: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[str, int], int]:
+    """(classes, service -> class, default class) as the engine takes them, by sl's scheme
+    (traffic_tables): class 0 is "no row" (an empty list), class 1 the default [minDelta] when there
+    is one, then one class per named service with a minDelta, in config order; a service named with
+    null maps to class 0."""
+    if not ls:
+        return [], {}, 0
+    classes: List[List[int]] = [[]]
+    default_class = 0
+    if ls["default"] is not None:
+        classes.append([ls["default"]])
+        default_class = 1
+    services: Dict[str, int] = {}
+    for name, o in ls["services"].items():
+        if o is not None:
+            classes.append([o])
+            services[name] = len(classes) - 1
+        else:
+            services[name] = 0
+    return classes, services, default_class
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -792,6 +944,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         parse_traffic_watch(merged["trafficWatch"])  # likewise
     if "peerOutliers" in merged:
         parse_peer_outliers(merged["peerOutliers"])  # likewise
+    if "latencyShift" in merged:
+        parse_latency_shift(merged["latencyShift"])  # likewise
     return cfg
 
 

@@ -686,6 +686,63 @@ class PeerEntry:
                 "median2x2": int(self.median2x2), "mad4": int(self.mad4), "verdict": self.verdict}
 
 
+# ---- ls: latency shifts against the window's own past (docs/SHIFT.md).  Integers only.
+SHIFT_MAX_RULES = 4
+
+
+def shift_rules_from_text(text: Optional[str]) -> Optional[List[tuple]]:
+    """``k:p:mB:T2:mR:X2:a:b:V,...`` -> [(k, q, mB, T2, mR, X2, a, b, V)], 1 to 4 groups: k, mB, mR, a
+    and b plain decimals of 1 to 10 digits, p a percentile of at most three decimals below 100
+    (q = p * 1000), T2 and X2 1 to 10 digits after an optional '-', V one of U, D, N; None: malformed
+    (copyenc.cpp holds the same rules)."""
+    groups = (text or "").split(",")
+    if not text or len(groups) > SHIFT_MAX_RULES:
+        return None
+    out = []
+    for g in groups:
+        parts = g.split(":")
+        if len(parts) != 9 or parts[8] not in ("U", "D", "N"):
+            return None
+        q = _pct_from_text(parts[1])
+        vals = [_svc_int(parts[0]), q, _svc_int(parts[2]), _svc_int(parts[3], 10, True), _svc_int(parts[4]),
+                _svc_int(parts[5], 10, True), _svc_int(parts[6]), _svc_int(parts[7])]
+        if any(v is None for v in vals) or q >= PCT_SCALE:
+            return None
+        out.append(tuple(vals) + (parts[8],))
+    return out
+
+
+@dataclass
+class LatencyShiftEntry:
+    """``ls|ts|server|service|n|minDelta|k:p:mB:T2:mR:X2:a:b:V,...`` -- at a rollover, a series whose
+    newest ``k`` window buckets are slower (``U``) or faster (``D``) than the other buckets of its K8
+    window, for at least one rule: ``count`` is the window's samples, ``min_delta`` the class' gate;
+    ``rules`` holds (k, q, mB, T2, mR, X2, a, b, verdict) per configured rule, q = p * 1000, mB / mR
+    the finite samples of the baseline / the recent span, T2 / X2 twice their percentile p, a / b the
+    recent finite samples strictly above / below the baseline's percentile (no reference
+    counterpart)."""
+    timestamp: Num
+    server: str
+    service: str
+    count: int
+    min_delta: int
+    rules: List[tuple]
+    type: str = "ls"
+
+    def to_csv(self) -> str:
+        groups = ",".join(f"{int(k)}:{pct_text(q)}:{int(mb)}:{int(t2)}:{int(mr)}:{int(x2)}:{int(a)}:{int(b)}:{v}"
+                          for k, q, mb, t2, mr, x2, a, b, v in self.rules)
+        return (f"ls|{js_str(self.timestamp)}|{self.server}|{self.service}|{int(self.count)}|{int(self.min_delta)}|"
+                f"{groups}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "count": int(self.count), "min_delta": int(self.min_delta),
+                "rules": [{"k": int(k), "p": pct_text(q), "base": int(mb), "t2": int(t2), "recent": int(mr),
+                           "x2": int(x2), "above": int(a), "below": int(b), "verdict": v}
+                          for k, q, mb, t2, mr, x2, a, b, v in self.rules]}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -800,7 +857,17 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
         if q is None or any(v is None for v in nums):
             return None
         return PeerEntry(parse_int(arr[1]), arr[2], arr[3], nums[0], q, nums[1], nums[2], nums[3], nums[4], arr[9])
+    if t == "ls":
+        # (copyenc.cpp holds the same rules) exactly seven fields; n and minDelta 1 to 10 digits; the
+        # groups by shift_rules_from_text; anything else is dropped
+        if len(arr) != 7:
+            return None
+        nums = [_svc_int(x) for x in arr[4:6]]
+        rules = shift_rules_from_text(arr[6])
+        if any(v is None for v in nums) or rules is None:
+            return None
+        return LatencyShiftEntry(parse_int(arr[1]), arr[2], arr[3], *nums, rules)
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls")
