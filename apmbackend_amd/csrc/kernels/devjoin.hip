@@ -380,14 +380,16 @@ __device__ int pre_fields(const Event& e, const uint8_t* __restrict__ p, AudF& f
   }
   if (e.kind == LK_SOAP) {
     const uint32_t m = e.mask;
-    if (m & PM_SOAP_IN) {  // ws[1].split('=')[1]; no '=' -> has_log_id false -> "undefined"
+    // ws[1].split('=')[1]; no '=' -> the logId is the value undefined, a cache key of its own: it is
+    // hashed with the other seed, so the logId text "undefined" of a timing line never meets it
+    if (m & PM_SOAP_IN) {
       int s = -1, t = -1;
       if (e.ntok >= 2) {
         const int a0 = e.t1s, b0 = e.t1e;
         for (int k = a0; k < b0; ++k) if (p[k] == '=') { s = k + 1; break; }
         if (s >= 0) { t = b0; for (int k = s; k < b0; ++k) if (p[k] == '=') { t = k; break; } }
       }
-      f.h_item = s >= 0 ? hash_bytes(p + s, (size_t)(t - s)) : hash_bytes("undefined", 9);
+      f.h_item = s >= 0 ? hash_bytes(p + s, (size_t)(t - s)) : hash_bytes("undefined", 9, kHashSeedEjb);
       return 1;
     }
     if (m & PM_SOAP_OUT) return 0;
@@ -614,7 +616,11 @@ struct SelScatterG {
 };
 
 // ------------------------------------------------------------------------ op build
-enum : uint8_t { SC_NONE = 0, SC_IN = 1, SC_OUT = 2, SC_ACCT = 3, SC_KEY = 4, SC_VALUE = 5 };
+// (SC_ACCT_BAD / SC_VALUE_BAD: an account that is not all digits -- saveAcctNum returns before it
+// touches the context, so the scan treats them as identity; k_soap_apply counts those that stand
+// where a valid one would have been saved)
+enum : uint8_t { SC_NONE = 0, SC_IN = 1, SC_OUT = 2, SC_ACCT = 3, SC_KEY = 4, SC_VALUE = 5, SC_ACCT_BAD = 6,
+                 SC_VALUE_BAD = 7 };
 
 __device__ const HostOp* find_hop(const HostOp* __restrict__ h, uint32_t n, uint32_t ev) {
   uint32_t lo = 0, hi = n;
@@ -670,9 +676,15 @@ __global__ __launch_bounds__(TB) void k_build_ops(DJArgs a) {
         case HOP_JOIN: op = h->op; break;
         case HOP_SOAP_IN: code = SC_IN; shash = h->lid_hash; break;
         case HOP_SOAP_OUT: code = SC_OUT; break;
-        case HOP_SOAP_ACCT: if (h->op.flags & JF_BAF_VALID) { code = SC_ACCT; snum = h->op.num; } break;
+        case HOP_SOAP_ACCT:
+          if (h->op.flags & JF_BAF_VALID) { code = SC_ACCT; snum = h->op.num; }
+          else code = SC_ACCT_BAD;
+          break;
         case HOP_SOAP_KEY: code = SC_KEY; break;
-        case HOP_SOAP_VALUE: if (h->op.flags & JF_BAF_VALID) { code = SC_VALUE; snum = h->op.num; } break;
+        case HOP_SOAP_VALUE:
+          if (h->op.flags & JF_BAF_VALID) { code = SC_VALUE; snum = h->op.num; }
+          else code = SC_VALUE_BAD;
+          break;
         default: break;
       }
     }
@@ -720,6 +732,8 @@ __global__ __launch_bounds__(TB) void k_build_ops(DJArgs a) {
         if (f.flags & PRE_SOAP_VALID) {
           snum = f.el;
           code = acct ? SC_ACCT : SC_VALUE;
+        } else {
+          code = acct ? SC_ACCT_BAD : SC_VALUE_BAD;
         }
       }
     }
@@ -871,6 +885,8 @@ __global__ __launch_bounds__(APM_WAVE) void k_soap_apply(DJArgs a) {
       op.num = a.soap_num[i];
       op.server = server;
       a.ops[i] = op;
+    } else if ((code == SC_ACCT_BAD && tag != 0) || (code == SC_VALUE_BAD && tag == 2)) {
+      atomicAdd(&a.counts->invalid_acct, 1ULL);
     }
     st = fcompose(__shfl(inc, APM_WAVE - 1, APM_WAVE), st);
   }

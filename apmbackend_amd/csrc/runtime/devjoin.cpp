@@ -381,7 +381,8 @@ void DeviceJoin::host_event(PrepassTask& T, const Event& e, uint32_t ev, const u
         }
       }
       h.kind = HOP_SOAP_IN;
-      h.lid_hash = has ? hash_bytes(lid.data(), lid.size()) : hash_bytes("undefined", 9);
+      // (no '=': the value undefined, not the text "undefined" -- the other seed keeps them apart)
+      h.lid_hash = has ? hash_bytes(lid.data(), lid.size()) : hash_bytes("undefined", 9, kHashSeedEjb);
     } else if (m & PM_SOAP_OUT) {
       h.kind = HOP_SOAP_OUT;
     } else if ((m & PM_SOAP_ACCT) || (!(m & PM_SOAP_KEY) && (m & PM_SOAP_VALUE))) {

@@ -242,7 +242,10 @@ void JoinShard::save_acct(std::string_view acct_raw, int32_t file, int source, s
     if (sc && sc->has_log_id) log_id = sc->log_id;  // storage survives soap_.erase below
     else log_id = kUndef;
   }
-  const uint64_t key = key_of(log_id);
+  // a SOAP block without a logId saves under the value undefined, which is no logId's text: the
+  // other seed keeps it apart from a timing line whose logId reads "undefined"
+  const bool no_lid = source != 2 && log_id.data() == kUndef.data();
+  const uint64_t key = no_lid ? hash_bytes(kUndef.data(), kUndef.size(), kHashSeedEjb) : key_of(log_id);
   const double a = js::parse_int(acct);
   auto& ae = acct_[key];
   ae.acct = a;
