@@ -12,6 +12,7 @@
 #include <memory>
 
 #include "kernels/burncmp.h"
+#include "kernels/incidentcmp.h"
 #include "kernels/kernel_api.h"
 #include "kernels/peercmp.h"
 #include "kernels/shiftcmp.h"
@@ -289,6 +290,25 @@ EngineConfig config_from(const py::dict& d) {
     if (v < 2 || v > 0x7fffffff) throw std::invalid_argument("ls_min_baseline: an integer >= 2");
     c.ls_min_baseline = (int32_t)v;
   }
+  if (d.contains("ic_open_after")) {  // K25 (the constructor checks them again when the ic stream is on)
+    const auto list = [&](const char* key) {
+      return d.contains(key) ? d[key].cast<std::vector<int64_t>>() : std::vector<int64_t>();
+    };
+    const auto o = list("ic_open_after"), cl = list("ic_close_after");
+    if (o.size() != 4 || cl.size() != 4)
+      throw std::invalid_argument("ic_open_after / ic_close_after: one value per source (sb, tf, po, ls), 0 for a source that is off");
+    for (size_t k = 0; k < 4; ++k) {
+      if ((o[k] == 0) != (cl[k] == 0) || o[k] < 0 || o[k] > 255 || cl[k] < 0 || cl[k] > 255)
+        throw std::invalid_argument("ic_open_after / ic_close_after: integers in 1 .. 255 (both 0: the source is off)");
+      c.ic_open_after[k] = (int32_t)o[k];
+      c.ic_close_after[k] = (int32_t)cl[k];
+    }
+  }
+  if (d.contains("ic_remind_every")) {
+    const int64_t v = d["ic_remind_every"].cast<int64_t>();
+    if (v < 0 || v > 65535) throw std::invalid_argument("ic_remind_every: 0 or an integer in 1 .. 65535");
+    c.ic_remind_every = (int32_t)v;
+  }
   if (d.contains("tk_k") && !d["tk_k"].is_none()) {  // (the constructor checks them when the tk stream is on)
     c.tk_k = d["tk_k"].cast<int32_t>();
     if (d.contains("tk_by")) c.tk_by = d["tk_by"].cast<std::vector<int32_t>>();
@@ -347,6 +367,8 @@ py::dict metrics_dict(const EngineMetrics& m) {
   d["tf_rows"] = m.tf_rows;
   d["po_rows"] = m.po_rows;
   d["ls_rows"] = m.ls_rows;
+  d["ic_rows"] = m.ic_rows;
+  d["ic_open_sb"] = m.ic_open[0]; d["ic_open_tf"] = m.ic_open[1]; d["ic_open_po"] = m.ic_open[2]; d["ic_open_ls"] = m.ic_open[3];
   d["formatted_bytes"] = m.formatted_bytes; d["lockstep_rollovers"] = m.lockstep_rollovers; d["format_fallbacks"] = m.format_fallbacks;
   d["t_parse_ms"] = m.t_parse_ms; d["t_join_ms"] = m.t_join_ms; d["t_stats_ms"] = m.t_stats_ms;
   d["t_total_ms"] = m.t_total_ms;
@@ -863,6 +885,27 @@ PYBIND11_MODULE(_apm_native, m) {
         }
         return out;
       })
+      .def("incidents", [](Engine& e) {
+        // per series id the K25 state: None for a series with every configured source closed and
+        // every run 0, else per source (sb, tf, po, ls) None when it is not configured or
+        // (code0 -- "" when closed, since_ts, age, hot_run, clear_run)
+        std::vector<IncidentState> st;
+        e.download_incidents(st);
+        py::list out;
+        for (size_t s = 0; s * 4 < st.size(); ++s) {
+          bool any = false;
+          py::list per;
+          for (int k = 0; k < 4; ++k) {
+            const IncidentState& x = st[s * 4 + k];
+            if (!e.ic_source(k)) { per.append(py::none()); continue; }
+            any = any || x.code0 != 0 || x.hot_run != 0 || x.clear_run != 0;
+            per.append(py::make_tuple(x.code0 ? std::string(1, (char)x.code0) : std::string(), (int64_t)x.since_ts,
+                                      (uint64_t)x.age, (int)x.hot_run, (int)x.clear_run));
+          }
+          if (any) out.append(py::tuple(per)); else out.append(py::none());
+        }
+        return out;
+      })
       .def("leaderboard", [](Engine& e) {
         // the last rollover's K18 records: (board, rank, series id, tpm, avg, p75, p95), raw doubles
         std::vector<std::tuple<int32_t, int32_t, int32_t, WinStat>> rows;
@@ -921,15 +964,15 @@ PYBIND11_MODULE(_apm_native, m) {
   m.def("copy_encode", [](py::bytes blob) {
     // wire lines -> Postgres COPY text per table type (runtime/sinks.py is the Python twin)
     std::string b = blob;
-    std::string out[15];
-    int64_t counts[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    std::string out[16];
+    int64_t counts[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     {
       py::gil_scoped_release rel;
       copyenc::encode_blob(b, out, counts);
     }
     py::dict d;
-    const char* names[15] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls"};
-    for (int k = 0; k < 15; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
+    const char* names[16] = {"tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls", "ic"};
+    for (int k = 0; k < 16; ++k) d[names[k]] = py::make_tuple(py::bytes(out[k]), counts[k]);
     return d;
   });
   m.def("set_blocking_sync", [](int device) {
@@ -1200,6 +1243,134 @@ PYBIND11_MODULE(_apm_native, m) {
     return std::string(v == LS_U ? "U" : v == LS_D ? "D" : "N");
   }, py::arg("a"), py::arg("b"), py::arg("mR"), py::arg("mB"), py::arg("T2"), py::arg("X2"), py::arg("q"), py::arg("r_u"),
      py::arg("r_d"), py::arg("z"), py::arg("min_delta"), py::arg("min_recent"), py::arg("min_baseline"));
+  // ic incidents (incident.hip): one step of the state machine the kernel runs (incidentcmp.h, the
+  // same routine compiled for the host).  state = (code0 "" or a letter, since_ts, age, hot_run,
+  // clear_run); returns (state, event "" / "O" / "S" / "C", code0 the row prints, run the row prints)
+  m.def("incident_step", [](const std::tuple<std::string, int64_t, uint64_t, int, int>& state, bool hot, const std::string& code,
+                            int64_t edge_ts, int64_t open_after, int64_t close_after, int64_t remind_every) {
+    const std::string& c0 = std::get<0>(state);
+    const uint64_t age = std::get<2>(state);
+    const int hr = std::get<3>(state), cr = std::get<4>(state);
+    if (c0.size() > 1 || age > 0xffffffffull || hr < 0 || hr > 255 || cr < 0 || cr > 255 || open_after < 1 || open_after > 255 ||
+        close_after < 1 || close_after > 255 || remind_every < 0 || remind_every > 65535 || (hot && code.size() != 1) ||
+        (hot && code[0] == 0))
+      throw std::invalid_argument("incident_step: code0 at most one letter, age below 2^32, runs in 0 .. 255, open_after and "
+                                  "close_after in 1 .. 255, remind_every in 0 .. 65535, one letter of code when hot");
+    IncidentState st{};
+    st.code0 = c0.empty() ? 0 : (uint8_t)c0[0];
+    st.since_ts = std::get<1>(state);
+    st.age = (uint32_t)age;
+    st.hot_run = (uint8_t)hr;
+    st.clear_run = (uint8_t)cr;
+    const IncidentOut o = incident_step(st, hot, hot ? (uint8_t)code[0] : 0, edge_ts, (uint32_t)open_after, (uint32_t)close_after,
+                                        (uint32_t)remind_every);
+    return py::make_tuple(py::make_tuple(st.code0 ? std::string(1, (char)st.code0) : std::string(), (int64_t)st.since_ts,
+                                         (uint64_t)st.age, (int)st.hot_run, (int)st.clear_run),
+                          o.event ? std::string(1, (char)o.event) : std::string(),
+                          o.code0 ? std::string(1, (char)o.code0) : std::string(), (int)o.run);
+  }, py::arg("state"), py::arg("hot"), py::arg("code"), py::arg("edge_ts"), py::arg("open_after"), py::arg("close_after"),
+     py::arg("remind_every"));
+  m.def("incident_row_bound", [](uint64_t name_bytes) { return (uint64_t)apm_incident_row_bound((size_t)name_bytes); });
+  m.def("incident_kernels", [](py::bytes state, py::bytes ev, const std::vector<py::object>& words, py::bytes active,
+                               int32_t n_series, const std::vector<int32_t>& open_after, const std::vector<int32_t>& close_after,
+                               int32_t remind_every, int64_t edge_ts, const std::vector<int32_t>& perm,
+                               const std::vector<std::tuple<int32_t, int32_t, int32_t, int32_t>>& series_names, py::bytes names) {
+    // the K25 kernels alone (test hook) over `cap` slots: state is cap * 4 * 16 bytes, ev cap * 4,
+    // active cap; words holds per source None (off) or cap int32 verdict words (stride 4); perm the
+    // series in emission order (empty: no text pass).  Returns (state, ev, open counts, text).
+    const std::string st = state, e0 = ev, act = active, nm = names;
+    const size_t cap = act.size();
+    if (st.size() != cap * 64 || e0.size() != cap * 4 || words.size() != 4 || open_after.size() != 4 || close_after.size() != 4 ||
+        n_series < 0 || (size_t)n_series > cap || series_names.size() != cap || remind_every < 0 || remind_every > 65535)
+      throw std::invalid_argument("incident_kernels: state cap * 64 bytes, ev cap * 4, four sources, n_series <= cap");
+    size_t longest = 0;
+    for (const auto& t : series_names) {
+      const int64_t so = std::get<0>(t), sl = std::get<1>(t), vo = std::get<2>(t), vl = std::get<3>(t);
+      if (so < 0 || sl < 0 || vo < 0 || vl < 0 || (size_t)(so + sl) > nm.size() || (size_t)(vo + vl) > nm.size())
+        throw std::invalid_argument("incident_kernels: a name lies outside `names`");
+      longest = std::max(longest, (size_t)(sl + vl));
+    }
+    for (int32_t s : perm)
+      if (s < 0 || s >= n_series) throw std::invalid_argument("incident_kernels: perm names no series");
+    DevMem dst(cap * 64), dev(cap * 4), dcodes(cap * 8), dact(cap), dopen(16), dnames(nm.size() + 64), dsn(cap * 16);
+    std::vector<std::unique_ptr<DevMem>> dw;
+    IncidentArgs a{};
+    for (int k = 0; k < 4; ++k) {
+      a.src[k].kind = k;
+      a.src[k].stride_bytes = 4;
+      a.open_after[k] = open_after[k];
+      a.close_after[k] = close_after[k];
+      if (words[k].is_none()) continue;
+      const auto w = words[k].cast<std::vector<int32_t>>();
+      if (w.size() != cap || open_after[k] < 1 || open_after[k] > 255 || close_after[k] < 1 || close_after[k] > 255)
+        throw std::invalid_argument("incident_kernels: cap words per source, open_after and close_after in 1 .. 255");
+      dw.emplace_back(new DevMem(cap * 4));
+      if (cap) HIP_OK(hipMemcpy(dw.back()->p, w.data(), cap * 4, hipMemcpyHostToDevice));
+      a.src[k].word = dw.back()->as<int32_t>();
+    }
+    if (cap) {
+      HIP_OK(hipMemcpy(dst.p, st.data(), st.size(), hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(dev.p, e0.data(), e0.size(), hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(dact.p, act.data(), cap, hipMemcpyHostToDevice));
+      std::vector<int32_t> sn;
+      for (const auto& t : series_names) {
+        sn.push_back(std::get<0>(t)); sn.push_back(std::get<1>(t)); sn.push_back(std::get<2>(t)); sn.push_back(std::get<3>(t));
+      }
+      HIP_OK(hipMemcpy(dsn.p, sn.data(), cap * 16, hipMemcpyHostToDevice));
+    }
+    HIP_OK(hipMemset(dcodes.p, 0, std::max<size_t>(cap * 8, 8)));
+    HIP_OK(hipMemset(dopen.p, 0, 16));
+    HIP_OK(hipMemset(dnames.p, 0, nm.size() + 64));
+    if (!nm.empty()) HIP_OK(hipMemcpy(dnames.p, nm.data(), nm.size(), hipMemcpyHostToDevice));
+    a.active = dact.as<uint8_t>();
+    a.n_series = n_series;
+    a.remind_every = remind_every;
+    a.edge_ts = edge_ts;
+    a.state = dst.as<IncidentState>();
+    a.ev = dev.as<uint8_t>();
+    a.codes = dcodes.as<uint8_t>();
+    a.open_n = dopen.as<int32_t>();
+    apm_incident_step(&a, 0);
+    std::string text;
+    const int32_t n = (int32_t)perm.size();
+    if (n > 0) {
+      const int32_t np = n * IC_MAX_SOURCES;
+      const size_t bound = (size_t)np * apm_incident_row_bound(longest) + 64;
+      const size_t tmpb = apm_incident_tmp_bytes(n);
+      DevMem dperm((size_t)n * 4), dlen(((size_t)np + 1) * 4), doff(((size_t)np + 1) * 4), dtmp(tmpb), dout(bound);
+      HIP_OK(hipMemcpy(dperm.p, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+      IncidentTextArgs t{};
+      t.state = a.state; t.ev = a.ev; t.codes = a.codes;
+      t.perm = dperm.as<int32_t>();
+      t.series_names = dsn.as<int4>();
+      t.names = dnames.as<char>();
+      t.n = np;
+      t.n_series = n_series;
+      t.ts_len = std::snprintf(t.ts, sizeof t.ts, "%lld|", (long long)edge_ts);
+      t.len = dlen.as<uint32_t>();
+      t.off = doff.as<uint32_t>();
+      t.out = dout.as<char>();
+      if (apm_incident_plan(&t, dtmp.p, tmpb, 0) != 0) throw std::runtime_error("incident_kernels: scan failed");
+      apm_incident_write(&t, 0);
+      uint32_t total = 0;
+      HIP_OK(hipMemcpy(&total, t.off + np, 4, hipMemcpyDeviceToHost));
+      if (total > bound) throw std::runtime_error("incident_kernels: the rows pass the row bound");
+      text.resize(total);
+      if (total) HIP_OK(hipMemcpy(&text[0], dout.p, total, hipMemcpyDeviceToHost));
+    }
+    HIP_OK(hipDeviceSynchronize());
+    std::string st1(cap * 64, '\0'), ev1(cap * 4, '\0');
+    int32_t open_n[4] = {0, 0, 0, 0};
+    if (cap) {
+      HIP_OK(hipMemcpy(&st1[0], dst.p, st1.size(), hipMemcpyDeviceToHost));
+      HIP_OK(hipMemcpy(&ev1[0], dev.p, ev1.size(), hipMemcpyDeviceToHost));
+    }
+    HIP_OK(hipMemcpy(open_n, dopen.p, 16, hipMemcpyDeviceToHost));
+    return py::make_tuple(py::bytes(st1), py::bytes(ev1), py::make_tuple(open_n[0], open_n[1], open_n[2], open_n[3]),
+                          py::bytes(text));
+  }, py::arg("state"), py::arg("ev"), py::arg("words"), py::arg("active"), py::arg("n_series"), py::arg("open_after"),
+     py::arg("close_after"), py::arg("remind_every"), py::arg("edge_ts"), py::arg("perm"), py::arg("series_names"),
+     py::arg("names"));
   m.def("apm_topk_tile", []() { return apm_topk_tile(); });
   m.def("apm_topk_final_span", []() { return apm_topk_final_span(); });
   m.def("topk_select", [](const std::vector<std::tuple<double, double, double, double, int32_t>>& win_rows,

@@ -566,6 +566,47 @@ struct ShiftTextArgs {
   uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
   char* out;                    // at least apm_shift_row_bound(max name bytes) * n bytes
 };
+// K25 ic rows: incidents opened and closed on the device (incident.hip, docs/INCIDENTS.md).  The
+// four verdict streams (sb, tf, po, ls) are level-triggered; per (series, source) a 16-byte state
+// (incidentcmp.h) is stepped once a rollover from the source's verdict word and the series' st flag,
+// and a row is printed only when the step has an event (opened, still open, closed):
+//   ic|<edge ts>|server|service|<sb|tf|po|ls>|<O|S|C>|<code0>|<code>|<since ts>|<age>|<run>
+// A source is handed over as a strided view of its records' verdict words, so the kernel depends on
+// none of the four record layouts (a test hands it plain int32 arrays with stride 4).
+constexpr int IC_MAX_SOURCES = 4;     // sb, tf, po, ls in this order (incidentcmp.h IC_SB ..)
+struct IncidentSource {
+  const int32_t* word;          // the verdict word of record 0 (null: the source is off)
+  int32_t stride_bytes;         // sizeof of the record
+  int32_t kind;                 // IC_SB / IC_TF / IC_PO / IC_LS
+};
+struct IncidentState;
+struct IncidentArgs {
+  IncidentSource src[IC_MAX_SOURCES];  // slot k belongs to source kind k
+  const uint8_t* active;        // [S] the series has an st row at this rollover (PeerArgs::active)
+  int32_t n_series;             // series ids at or above it are not touched
+  int32_t open_after[IC_MAX_SOURCES];   // 1 .. 255
+  int32_t close_after[IC_MAX_SOURCES];  // 1 .. 255
+  int32_t remind_every;         // 0 (never) or 1 .. 65535
+  long long edge_ts;
+  IncidentState* state;         // [S][4]
+  uint8_t* ev;                  // [S][4] this rollover's event: 0, 'O', 'S', 'C'
+  uint8_t* codes;               // [S][4][2] what the row prints: {code0, code} ('-': not hot)
+  int32_t* open_n;              // [4] += open incidents per source (the caller zeroes them)
+};
+struct IncidentTextArgs {
+  const IncidentState* state;   // [S][4]
+  const uint8_t* ev;            // [S][4]
+  const uint8_t* codes;         // [S][4][2]
+  const int32_t* perm;          // [n / 4] series in emission order
+  const int4* series_names;     // [S] {server off, len, service off, len} into `names`
+  const char* names;
+  int32_t n;                    // text positions: emission positions * 4 (position p: series perm[p / 4], source p % 4)
+  int32_t n_series;
+  int32_t ts_len;
+  char ts[24];                  // "<edge ts>|"
+  uint32_t *len, *off;          // [n + 1] row bytes / exclusive offsets (off[n] = total)
+  char* out;                    // at least apm_incident_row_bound(max name bytes) * n bytes
+};
 struct AlertArgs {
   const WinStat* win;         // [S]
   const ZOut* z;              // [S] for this lag
@@ -780,6 +821,16 @@ void apm_shift_values(apm::ShiftArgs* a, hipStream_t stream);
 // length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
 int apm_shift_plan(apm::ShiftTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
 void apm_shift_write(apm::ShiftTextArgs* a, hipStream_t stream);
+// incident.hip
+// scan scratch for n_max series (4 text positions each)
+size_t apm_incident_tmp_bytes(int32_t n_max);
+// upper bound of a row's bytes for names of `name_bytes` (server + service) bytes
+size_t apm_incident_row_bound(size_t name_bytes);
+// one step of every (series, source) state below n_series; a->open_n must be zero before it
+void apm_incident_step(apm::IncidentArgs* a, hipStream_t stream);
+// length pass + scan: afterwards a->off[0..n] hold the rows' offsets, off[n] the total bytes
+int apm_incident_plan(apm::IncidentTextArgs* a, void* tmp, size_t tmp_bytes, hipStream_t stream);
+void apm_incident_write(apm::IncidentTextArgs* a, hipStream_t stream);
 // fleet.hip
 void apm_service_moments(const int32_t* series_service, const uint8_t* active, int32_t n_series, int32_t S,
                          int32_t n_lags, int32_t n_services_cap, const double* const* sums, const double* const* comps,

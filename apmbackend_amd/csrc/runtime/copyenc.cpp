@@ -268,8 +268,8 @@ void append_pct_pairs(std::string& js, std::string_view rest) {
 }
 
 // Returns the type index (0 tx, 1 fs, 2 al, 3 jx, 4 fb, 5 lh, 6 wp, 7 sl, 8 tk, 9 sv, 10 rw, 11 sb, 12 tf,
-// 13 po, 14 ls) the row was appended to, or -1.
-int encode_line(std::string_view line, std::string* out /*[15]*/) {
+// 13 po, 14 ls, 15 ic) the row was appended to, or -1.
+int encode_line(std::string_view line, std::string* out /*[16]*/) {
   Fields a;
   split(line, '|', a);
   const std::string_view t = a.f[0];
@@ -715,6 +715,41 @@ int encode_line(std::string_view line, std::string* out /*[15]*/) {
     copy_escape(o, js);
     o += '\n';
     return 14;
+  }
+  if (t == "ic") {  // incident: timestamp, server, service, source, event, code0, code, since, age, run
+    // (utils/records.py entry_from_csv holds the same rules) a row is dropped whole unless it has
+    // exactly eleven fields, the source is one of sb, tf, po, ls, the event one of O, S, C, code0 one
+    // of B, D, S, H, L, U and code one of those or '-', since 1 to 15 plain digits and at most
+    // 253402300799999 (the last ms of the year 9999), age 1 to 10 plain digits and run 1 to 3
+    if (a.n != 11) return -1;
+    const std::string_view src = a.f[4], ev = a.f[5], c0 = a.f[6], c1 = a.f[7];
+    if (src != "sb" && src != "tf" && src != "po" && src != "ls") return -1;
+    if (ev != "O" && ev != "S" && ev != "C") return -1;
+    static const std::string_view kCodes = "BDSHLU";
+    if (c0.size() != 1 || kCodes.find(c0[0]) == std::string_view::npos) return -1;
+    if (c1.size() != 1 || (c1[0] != '-' && kCodes.find(c1[0]) == std::string_view::npos)) return -1;
+    const std::string_view since = a.f[8];
+    if (!all_digits(since, 15) || !all_digits(a.f[9], 10) || !all_digits(a.f[10], 3)) return -1;
+    int64_t sv = 0;
+    for (char ch : since) sv = sv * 10 + (ch - '0');
+    std::string since_txt;
+    if (sv > 253402300799999LL || !ts_text((double)sv, ' ', since_txt)) return -1;
+    std::string& o = out[15];
+    c_ts(o, a, 1); o += '\t';
+    c_str(o, a, 2); o += '\t';
+    c_str(o, a, 3); o += '\t';
+    o += src; o += '\t';
+    o += ev; o += '\t';
+    o += c0; o += '\t';
+    o += c1; o += '\t';
+    o += since_txt; o += "+00\t";
+    for (int i = 9; i <= 10; ++i) {
+      int64_t v = 0;
+      for (char ch : a.f[i]) v = v * 10 + (ch - '0');
+      append_i64(o, v);
+      o += i == 9 ? '\t' : '\n';
+    }
+    return 15;
   }
   if (t == "jx") {
     std::string& o = out[3];

@@ -54,7 +54,7 @@ void encode_blob(std::string_view blob, std::string* out, int64_t* counts);
 
 namespace {
 
-constexpr int NT = 15;  // tx, fs, al, jx, fb, lh, wp, sl, tk, sv, rw, sb, tf, po, ls
+constexpr int NT = 16;  // tx, fs, al, jx, fb, lh, wp, sl, tk, sv, rw, sb, tf, po, ls, ic
 
 double mono_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -78,6 +78,7 @@ int type_of(std::string_view line) {
   if (a == 't' && b == 'f') return 12;
   if (a == 'p' && b == 'o') return 13;
   if (a == 'l' && b == 's') return 14;
+  if (a == 'i' && b == 'c') return 15;
   return -1;
 }
 
@@ -120,8 +121,8 @@ struct SpoolWriter : Writer {
   std::string dir;
   uint64_t rotate;
   std::string suffix;  // "" for lane 0, ".lane<k>" for writer lane k
-  int fd[NT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
-  uint64_t size[NT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int fd[NT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  uint64_t size[NT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   SpoolWriter(std::string d, uint64_t r, std::string sfx = "") : dir(std::move(d)), rotate(r), suffix(std::move(sfx)) {
     ::mkdir(dir.c_str(), 0755);
   }
@@ -305,7 +306,7 @@ class DbSink : public ByteSink {
          int lanes = 1, double ack_timeout_ms = 120000.0)
       : limit_(std::max<int64_t>(1, limit)), max_wait_ms_(max_wait_ms), tables_(std::move(tables)),
         columns_(std::move(columns)), lanes_(std::max(1, std::min(lanes, 64))), order_((size_t)lanes_) {
-    // Shim for callers written before the lh / wp / sl / tk / sv / rw / sb / tf / po / ls types, which name five to fourteen tables: the missing
+    // Shim for callers written before the lh / wp / sl / tk / sv / rw / sb / tf / po / ls / ic types, which name five to fifteen tables: the missing
     // buffers then get the default table and columns of sinks.py (DEFAULT_TABLES / COLUMNS) -- such
     // a caller feeds no such rows -- and close() returns the buffers the caller knows.
     nt_given_ = (int)tables_.size();
@@ -349,7 +350,11 @@ class DbSink : public ByteSink {
       tables_.push_back("apm_latency_shift");
       columns_.push_back("timestamp, server, service, count, min_delta, rules");
     }
-    if (tables_.size() != NT || columns_.size() != NT) throw std::runtime_error("DbSink: 15 tables / column lists");
+    if (tables_.size() == columns_.size() && tables_.size() == 15) {
+      tables_.push_back("apm_incident");
+      columns_.push_back("timestamp, server, service, source, event, code0, code, since, age, run");
+    }
+    if (tables_.size() != NT || columns_.size() != NT) throw std::runtime_error("DbSink: 16 tables / column lists");
     // Writer lanes: `lanes` independent writers (own spool files / own psql connection), each
     // writing its share of the flushes in submission order -- the reference's pg Pool likewise
     // keeps several INSERTs in flight (stream_insert_db.js:277-327).
@@ -942,7 +947,7 @@ class DbSink : public ByteSink {
         to_encode_.pop_front();
       }
       std::string out[NT];
-      int64_t counts[NT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      int64_t counts[NT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       copyenc::encode_blob(j->lines, out, counts);
       {
         std::lock_guard<std::mutex> lk(mu_);
@@ -1016,7 +1021,7 @@ class DbSink : public ByteSink {
           if (!back.empty()) {
             if (as_copy && b.n > 0 && !b.enc) {  // the buffer's wire lines -> COPY rows
               std::string out[NT];
-              int64_t counts[NT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+              int64_t counts[NT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
               copyenc::encode_blob(b.lines, out, counts);
               b.lines.swap(out[t]);
             }
@@ -1055,7 +1060,7 @@ class DbSink : public ByteSink {
   std::condition_variable cv_, done_cv_;
   Buf buf_[NT];
   int nt_given_ = NT;  // tables the caller named
-  bool encoded_[NT] = {false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};  // type buffered as COPY rows (engine-encoded)
+  bool encoded_[NT] = {false, false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};  // type buffered as COPY rows (engine-encoded)
   std::vector<std::deque<std::shared_ptr<Job>>> order_;  // per writer lane, submission order
   std::deque<std::shared_ptr<Job>> to_encode_;
   uint64_t rr_ = 0;
@@ -1065,7 +1070,7 @@ class DbSink : public ByteSink {
   std::map<uint64_t, std::shared_ptr<Job>> live_;  // submitted, not yet written (by sequence)
   uint64_t rebuf_floor_[NT] = {UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX,
                                UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX,
-                               UINT64_MAX, UINT64_MAX};
+                               UINT64_MAX, UINT64_MAX, UINT64_MAX};
   int ack_fd_ = -1;
   uint64_t incarnation_ = 0;
   bool stop_ = false;

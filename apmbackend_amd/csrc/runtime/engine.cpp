@@ -24,6 +24,7 @@
 #include <stdexcept>
 
 #include "../kernels/devjoin_api.h"
+#include "../kernels/incidentcmp.h"
 #include "../kernels/kernel_api.h"
 #include "format.h"
 
@@ -347,6 +348,20 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
                                   "and ls_down 0 or 1001 .. 1000000 (not both 0), ls_z 0 .. 100000, ls_min_recent >= 1, "
                                   "ls_min_baseline >= 2");
   }
+  if (want(OUT_IC)) {  // K25: likewise; a source also needs its own stream, whose records it reads
+    static const int kSrcOut[4] = {OUT_SB, OUT_TF, OUT_PO, OUT_LS};
+    bool ok = cfg_.ic_remind_every >= 0 && cfg_.ic_remind_every <= 65535, any = false;
+    for (int k = 0; ok && k < 4; ++k) {
+      const int32_t o = cfg_.ic_open_after[k], c = cfg_.ic_close_after[k];
+      if (o == 0 && c == 0) continue;
+      ok = o >= 1 && o <= 255 && c >= 1 && c <= 255 && want(kSrcOut[k]);
+      any = true;
+    }
+    if (!ok || !any)
+      throw std::invalid_argument("ic stream: ic_open_after / ic_close_after must hold 1 .. 255 for at least one of the "
+                                  "sources sb, tf, po, ls (0 / 0: not configured), every configured source's own "
+                                  "stream must be in outputs, ic_remind_every 0 or 1 .. 65535");
+  }
   HIP_OK(hipSetDevice(cfg_.device));
   {
     // Ranks sharing one GPU (a rehearsal of the node on one card): host threads that spin in
@@ -633,6 +648,16 @@ Engine::Engine(const EngineConfig& cfg) : cfg_(cfg) {
     HIP_OK(hipMemset(d_ls_cls_, 0, (size_t)S * 4));  // class 0 until a series' class is uploaded
     d_ls_rec_ = (ShiftRec*)res_.dmalloc((size_t)S * sizeof(ShiftRec));
     text_alloc(ls_, OUT_LS, apm_shift_tmp_bytes(S));
+  }
+  if (want(OUT_IC)) {  // K25: every incident closed, every run 0
+    d_ic_state_ = (IncidentState*)res_.dmalloc((size_t)S * IC_MAX_SOURCES * sizeof(IncidentState));
+    d_ic_ev_ = (uint8_t*)res_.dmalloc((size_t)S * IC_MAX_SOURCES);
+    d_ic_codes_ = (uint8_t*)res_.dmalloc((size_t)S * IC_MAX_SOURCES * 2);
+    d_ic_open_ = (int32_t*)res_.dmalloc(IC_MAX_SOURCES * 4);
+    HIP_OK(hipMemset(d_ic_state_, 0, (size_t)S * IC_MAX_SOURCES * sizeof(IncidentState)));
+    HIP_OK(hipMemset(d_ic_ev_, 0, (size_t)S * IC_MAX_SOURCES));
+    HIP_OK(hipMemset(d_ic_codes_, 0, (size_t)S * IC_MAX_SOURCES * 2));
+    text_alloc(ic_, OUT_IC, apm_incident_tmp_bytes(S), IC_MAX_SOURCES);
   }
   if (want(OUT_LH)) text_alloc(lh_, OUT_LH, apm_hist_tmp_bytes(S));  // K15
   {
@@ -1758,6 +1783,9 @@ void Engine::flush() {
     po_rows_lane_ = 0;
     metrics_.ls_rows += ls_rows_lane_;
     ls_rows_lane_ = 0;
+    metrics_.ic_rows += ic_rows_lane_;
+    ic_rows_lane_ = 0;
+    for (int j = 0; j < 4; ++j) metrics_.ic_open[j] = ic_open_lane_[j];
     if (!out_error_.empty()) { std::string e = out_error_; out_error_.clear(); throw std::runtime_error(e); }
   }
   if (!st_error_.empty()) { std::string e = st_error_; st_error_.clear(); throw std::runtime_error(e); }
@@ -2709,6 +2737,11 @@ void Engine::do_rollover(int64_t L, double batch_t0, int64_t prev) {
   // K23: after it, for the same reason: it reads what K16 reads (window cells, counts, spill lists,
   // d_win_), the service groups and its own class array, and writes buffers of its own.
   if (want(OUT_PO)) peer_rollover(wa, edge_ts);
+  // K25: the last call, behind K23 on this stream: the four records it reads (sb, tf, po, ls) are
+  // all written by now, each by its own rollover above, and nothing queued before the next rollover
+  // writes any of them or the st flags (the next append follows on this stream).  Its state is its
+  // own and is touched by this call alone.
+  if (want(OUT_IC)) incident_rollover(edge_ts);
   const double tr3 = now_ms();
   metrics_.t_rollover_ms += tr2 - tr1;
   metrics_.t_format_ms += tr3 - tr2;
@@ -2863,8 +2896,8 @@ void Engine::release_device_finish() {
       HIP_OK(hipStreamSynchronize(rel_stream_));
       const double tl1 = now_ms();
       if (host_enc) {
-        std::string enc[15];
-        int64_t counts[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        std::string enc[16];
+        int64_t counts[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         copyenc::encode_blob(std::string_view(h, total), enc, counts);
         emit_bytes(OUT_DB, enc[0].data(), enc[0].size());
       } else if (rows) {
@@ -3028,6 +3061,8 @@ void Engine::rebuild_cool() {
   HIP_OK(hipMemsetAsync(d_cool_t_, 0xff, (size_t)cfg_.max_series * 8, stream_));
   if (n_series_ > 0) HIP_OK(hipMemcpyAsync(d_cool_t_, t.data(), (size_t)n_series_ * 8, hipMemcpyHostToDevice, stream_));
   HIP_OK(hipStreamSynchronize(stream_));
+  // K25: the series ids may have changed their meaning -- no incident survives (not checkpointed)
+  incident_reset();
 }
 
 int32_t Engine::intern_name(const std::string& name) {
@@ -3286,7 +3321,7 @@ void Engine::format_rollover_text(int64_t edge_ts) {
   });
 }
 
-// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb, tf, po, ls): buffers and the slot protocol, once.
+// ---- The text streams of a rollover (lh, wp, sl, sv, rw, sb, tf, po, ls, ic): buffers and the slot protocol, once.
 // `rows`: text lanes per series (rw prints one row per span).
 void Engine::text_alloc(TextStream& t, int kind, size_t tmp_bytes, int rows) {
   const size_t S = (size_t)cfg_.max_series;
@@ -3320,6 +3355,10 @@ void Engine::text_end(TextStream& t, int32_t n) {
   t.task[k] = post_out([this, ts, k, dst]() {
     HIP_OK(hipEventSynchronize(ts->ev[k]));
     const size_t total = ts->total[k];
+    if (ts->kind == OUT_IC) {  // (metrics: the slot's open incidents per source, rows or not)
+      std::lock_guard<std::mutex> g(out_mu_);
+      for (int j = 0; j < 4; ++j) ic_open_lane_[j] = ts->total[8 + 4 * k + j];
+    }
     if (!total) return;
     res_.reserve(ts->text[k], total, total * 2 + (1 << 20));
     lane_d2h(ts->text[k], dst, total);
@@ -3347,6 +3386,12 @@ void Engine::text_end(TextStream& t, int32_t n) {
       const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
       std::lock_guard<std::mutex> g(out_mu_);
       ls_rows_lane_ += rows;
+    }
+    if (ts->kind == OUT_IC) {  // (likewise)
+      const char* p = ts->text[k];
+      const uint64_t rows = (uint64_t)std::count(p, p + total, '\n');
+      std::lock_guard<std::mutex> g(out_mu_);
+      ic_rows_lane_ += rows;
     }
     emit_bytes(ts->kind, ts->text[k], total);
   });
@@ -4001,6 +4046,82 @@ void Engine::download_shifts(std::vector<ShiftRec>& rec, std::vector<uint8_t>& h
     has[(size_t)s] = win[(size_t)s].active && cls[(size_t)s] > 0 && cls[(size_t)s] < n_ls_classes_;
 }
 
+// ---- K25: ic rows.  One step of every (series, source) state from the verdict words the four
+// rollovers above left in their records, then count / scan / write of the text over n * 4
+// positions -- the event byte is the row policy, so the length pass is the compaction, nothing
+// waits for it and only off[n * 4] bytes reach the host.  A series may print a row (a close, a
+// reminder) without an st row: d_perm_ covers every series id below n_series (sync_format_tables
+// merges every series in, active or not).
+void Engine::incident_rollover(int64_t edge_ts) {
+  const int32_t n = n_series_;
+  if (n == 0) return;
+  sync_format_tables();
+  IncidentArgs va{};
+  const int32_t* word[4] = {want(OUT_SB) ? &d_sb_rec_->fired : nullptr, want(OUT_TF) ? &d_tf_rec_->verdict : nullptr,
+                            want(OUT_PO) ? &d_po_rec_->verdict : nullptr, want(OUT_LS) ? &d_ls_rec_->verdict : nullptr};
+  const int32_t stride[4] = {(int32_t)sizeof(BurnRec), (int32_t)sizeof(TrafficRec), (int32_t)sizeof(PeerRec),
+                             (int32_t)sizeof(ShiftRec)};
+  for (int k = 0; k < IC_MAX_SOURCES; ++k) {
+    const bool on = ic_source(k);  // (the constructor checked that its stream is on)
+    va.src[k].word = on ? word[k] : nullptr;
+    va.src[k].stride_bytes = stride[k];
+    va.src[k].kind = k;
+    va.open_after[k] = cfg_.ic_open_after[k];
+    va.close_after[k] = cfg_.ic_close_after[k];
+  }
+  va.active = d_active_;
+  va.n_series = n;
+  va.remind_every = cfg_.ic_remind_every;
+  va.edge_ts = edge_ts;
+  va.state = d_ic_state_;
+  va.ev = d_ic_ev_;
+  va.codes = d_ic_codes_;
+  va.open_n = d_ic_open_;
+  HIP_OK(hipMemsetAsync(d_ic_open_, 0, IC_MAX_SOURCES * 4, stream_));
+  apm_incident_step(&va, stream_);
+  IncidentTextArgs ta{};
+  ta.state = d_ic_state_;
+  ta.ev = d_ic_ev_;
+  ta.codes = d_ic_codes_;
+  ta.perm = d_perm_;
+  ta.series_names = reinterpret_cast<const int4*>(d_ser_names_);
+  ta.names = d_names_;
+  ta.n = n * IC_MAX_SOURCES;
+  ta.n_series = n;
+  ta.ts_len = std::snprintf(ta.ts, sizeof ta.ts, "%lld|", (long long)edge_ts);
+  ta.len = ic_.len;
+  ta.off = ic_.off;
+  // the output bound needs no length pass: every row is at most apm_incident_row_bound bytes
+  ta.out = text_begin(ic_, (size_t)n * IC_MAX_SOURCES * apm_incident_row_bound(max_name_len_) + 64);
+  if (apm_incident_plan(&ta, ic_.tmp, ic_.tmp_bytes, stream_) != 0) throw std::runtime_error("incident scan failed");
+  apm_incident_write(&ta, stream_);
+  {
+    // the open counts ride in the slot's pinned totals (text_alloc pins 64 of them), behind the
+    // slot's own total and ahead of its event
+    ExportArgs ex{};
+    for (int j = 0; j < IC_MAX_SOURCES; ++j) ex.add(d_ic_open_ + j, ic_.total.d + 8 + 4 * ic_.k + j, 4);
+    apm_export(&ex, stream_);
+  }
+  text_end(ic_, n * IC_MAX_SOURCES);
+}
+
+void Engine::incident_reset() {
+  if (!want(OUT_IC) || !d_ic_state_) return;
+  const size_t S = (size_t)cfg_.max_series;
+  HIP_OK(hipMemsetAsync(d_ic_state_, 0, S * IC_MAX_SOURCES * sizeof(IncidentState), stream_));
+  HIP_OK(hipMemsetAsync(d_ic_ev_, 0, S * IC_MAX_SOURCES, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+}
+
+void Engine::download_incidents(std::vector<IncidentState>& st) {
+  st.clear();
+  const int32_t n = want(OUT_IC) ? n_series_ : 0;
+  if (n == 0) return;
+  st.resize((size_t)n * IC_MAX_SOURCES);
+  HIP_OK(hipMemcpyAsync(st.data(), d_ic_state_, st.size() * sizeof(IncidentState), hipMemcpyDeviceToHost, stream_));
+  HIP_OK(hipStreamSynchronize(stream_));
+}
+
 // Ingest (caller) thread: the sample applies from the next processed batch on.
 bool Engine::set_server_context(const std::string& server, double ts_ms, const std::vector<double>& gauges,
                                 double host_load) {
@@ -4141,7 +4262,7 @@ void Engine::download_zout(int l, std::vector<ZOut>& out) {
 }
 
 const char* out_kind_name(int k) {
-  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls"};
+  static const char* n[N_OUT] = {"transactions", "audit_db", "db", "st", "fs", "al", "sx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls", "ic"};
   return n[k];
 }
 

@@ -195,6 +195,13 @@ struct EngineConfig {
   int32_t ls_down[4] = {0, 0, 0, 0};
   int32_t ls_z[4] = {0, 0, 0, 0};
   int32_t ls_min_recent = 20, ls_min_baseline = 100;
+  // ic stream (K25): per source (sb, tf, po, ls in this order) openAfter and closeAfter in 1 .. 255,
+  // 0 / 0 for a source that is not configured (at least one is, and each one's own stream must be in
+  // `outputs`); remindEvery 0 (never) or 1 .. 65535 rollovers; read at construction (OUT_IC in
+  // `outputs` without valid values is an error)
+  int32_t ic_open_after[4] = {0, 0, 0, 0};
+  int32_t ic_close_after[4] = {0, 0, 0, 0};
+  int32_t ic_remind_every = 0;
   int async_stats = 1;      // overlap batch i's stats with batch i+1's parse + join
   // RCCL watchdog: a collective not complete after this long (a dead or wedged peer) aborts the
   // communicator and throws, so the supervisor restarts the rank group from its checkpoint
@@ -220,14 +227,14 @@ struct EngineConfig {
 //   FS            z -> alerts/db  fs lines (one per series per LAG)
 //   AL            alerts -> db    al lines
 //   SX            new: per-JVM rollup fused with JMX / VM gauges (K14), one line per server
-enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, OUT_SV, OUT_RW, OUT_SB, OUT_TF, OUT_PO, OUT_LS, N_OUT };
+enum OutKind { OUT_TRANSACTIONS = 0, OUT_AUDIT_DB, OUT_DB, OUT_ST, OUT_FS, OUT_AL, OUT_SX, OUT_FB, OUT_LH, OUT_WP, OUT_SL, OUT_TK, OUT_SV, OUT_RW, OUT_SB, OUT_TF, OUT_PO, OUT_LS, OUT_IC, N_OUT };
 // Streams whose pending text a checkpoint stores (checkpoint.cpp).  The version-9 layout holds
-// exactly these; lh, wp, sl, tk, sv, rw, sb, tf, po and ls rows are taken by their consumer before a checkpoint and are not persisted.
+// exactly these; lh, wp, sl, tk, sv, rw, sb, tf, po, ls and ic rows are taken by their consumer before a checkpoint and are not persisted.
 constexpr int N_OUT_CKPT = OUT_FB + 1;
-// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk, sv, rw, sb, tf, po, ls); the stats thread owns the rest
+// streams written by the engine's output lane (released tx, st, fs, lh, wp, sl, tk, sv, rw, sb, tf, po, ls, ic); the stats thread owns the rest
 constexpr uint32_t kLaneKinds = (1u << OUT_DB) | (1u << OUT_ST) | (1u << OUT_FS) | (1u << OUT_LH) | (1u << OUT_WP) |
                                 (1u << OUT_SL) | (1u << OUT_TK) | (1u << OUT_SV) | (1u << OUT_RW) | (1u << OUT_SB) | (1u << OUT_TF) |
-                                (1u << OUT_PO) | (1u << OUT_LS);
+                                (1u << OUT_PO) | (1u << OUT_LS) | (1u << OUT_IC);
 const char* out_kind_name(int k);
 int out_kind_of(const std::string& name);
 
@@ -299,6 +306,8 @@ struct EngineMetrics {
   uint64_t tf_rows = 0;             // K22: tf rows emitted (likewise)
   uint64_t po_rows = 0;             // K23: po rows emitted (likewise)
   uint64_t ls_rows = 0;             // K24: ls rows emitted (likewise)
+  uint64_t ic_rows = 0;             // K25: ic rows emitted (likewise)
+  uint64_t ic_open[4] = {0, 0, 0, 0};  // K25: open incidents per source (sb, tf, po, ls) at the last rollover the output lane has seen
   uint64_t series_overflow_tx = 0;  // tx whose series could not be created (gpu.maxSeries full)
   uint64_t spill_dropped = 0;       // samples lost to a full bucket spill list (gpu.bucketOverflowCapacity)
   uint64_t nan_windows_clipped = 0; // NaN windows larger than the JS-emulation scratch (percentiles clipped)
@@ -462,6 +471,9 @@ class Engine {
   std::vector<std::pair<int64_t, std::string>> export_pending();
   void import_pending(const std::vector<int64_t>& ends, const std::vector<std::string>& lines);
   std::vector<std::pair<std::string, double>> export_cooldowns();
+  // (it rebuilds the device cooldown table through rebuild_cool(), which also closes every K25
+  // incident and zeroes every run -- a side effect when the ic stream is on, although this import
+  // renumbers no series: its caller is the start from a resume file)
   void import_cooldowns(const std::vector<std::pair<std::string, double>>& c);
   std::vector<int32_t> export_alert_counters(int lag_idx);
   void import_alert_counters(int lag_idx, const std::vector<int32_t>& series, const std::vector<int32_t>& counts);
@@ -798,7 +810,7 @@ class Engine {
   std::mutex out_pool_mu_;
   bool st_has_job_ = false, st_busy_ = false, st_stop_ = false;
   std::string st_error_;
-  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk / sv / rw / sb / tf / po / ls streams (kLaneKinds)
+  // output lane: FIFO of emit tasks; it owns the db / st / fs / lh / wp / sl / tk / sv / rw / sb / tf / po / ls / ic streams (kLaneKinds)
   std::thread out_thread_;
   std::mutex out_mu_;
   std::condition_variable out_cv_;
@@ -1266,7 +1278,7 @@ class Engine {
   PinnedBuf<uint32_t> h_fs_off_[2];
   size_t fs_rows_[2] = {0, 0};
 
-  // A rollover stream whose rows are printed on the device (lh, wp, sl, sv, rw, sb, tf, po, ls): the buffers of its
+  // A rollover stream whose rows are printed on the device (lh, wp, sl, sv, rw, sb, tf, po, ls, ic): the buffers of its
   // count / scan / write text pass and two device / pinned text slots, as for st / fs.  A rollover
   // takes the other slot than the one before it; a slot is reused only after its output-lane task
   // is done, and the lane reads a slot's total only after the slot's event.  Allocated when the
@@ -1482,9 +1494,30 @@ class Engine {
   int32_t ls_nrule() const { return cfg_.n_ls_rules; }
  private:
 
+  // K25 ic rows (incident.hip), allocated when the stream is on: per (series, source) the state of
+  // incidentcmp.h, stepped once a rollover behind the four verdict streams, one row per event.  The
+  // first stream whose device state outlives a rollover: it is not checkpointed, and every path
+  // that renumbers series (restore, rebuild) closes every incident (incident_reset).  All arrays
+  // are sized for max_series, as d_cool_t_ is, so there is nothing to grow.
+  IncidentState* d_ic_state_ = nullptr;                     // [S][4]
+  uint8_t* d_ic_ev_ = nullptr;                              // [S][4] the last rollover's events
+  uint8_t* d_ic_codes_ = nullptr;                           // [S][4][2] the letters its rows print
+  int32_t* d_ic_open_ = nullptr;                            // [4] open incidents per source
+  TextStream ic_;                                           // (total[8 + 4 k + j]: slot k's open count of source j)
+  uint64_t ic_rows_lane_ = 0;                               // rows the output lane emitted since the last flush()
+  uint64_t ic_open_lane_[4] = {0, 0, 0, 0};                 // the open counts of the last slot the lane emitted
+  void incident_rollover(int64_t edge_ts);
+  void incident_reset();                                    // every incident closed, every run 0
+ public:
+  // (tests) the state of every (series, source) below n_series (a series no rollover stepped yet is
+  // closed with both runs 0)
+  void download_incidents(std::vector<IncidentState>& st);
+  bool ic_source(int k) const { return cfg_.ic_open_after[k] != 0; }
+ private:
+
   // text outputs
   std::string blob_[N_OUT];
-  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+  int sink_fd_[N_OUT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   std::shared_ptr<ByteSink> byte_sink_[N_OUT];
   bool fs_copy_ = false;
   bool db_copy_ = false;
@@ -1493,7 +1526,7 @@ class Engine {
   void lane_sync();  // the output stream
   int cu_reserved_ = 0;  // CUs kept out of the parse / stats / output streams (APM_CU_RESERVE)
   void lane_d2h(void* h, const void* d, size_t n, hipStream_t s = nullptr);  // (null: the output stream)  // APM_TXCOPY_FORCE_FALLBACK=1: every release takes the host path (tests)
-  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t sink_bytes_[N_OUT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // K14 server rollup + exogenous context
   std::vector<double> h_ctx_;                    // [servers][CTX_FIELDS] (stats thread)
   bool ctx_dirty_ = false;

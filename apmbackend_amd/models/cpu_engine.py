@@ -27,7 +27,7 @@ class CpuOracleEngine:
                                 server_fn=lambda p: self._server.get(p, "undefined"))
         self.watermark = 0.0
         self._taken = {"transactions": 0, "audit_db": 0, "db": 0, "st": 0, "fs": 0, "al": 0, "lh": 0, "wp": 0, "sl": 0,
-                       "tk": 0, "sv": 0, "rw": 0, "sb": 0, "tf": 0, "po": 0, "ls": 0}
+                       "tk": 0, "sv": 0, "rw": 0, "sb": 0, "tf": 0, "po": 0, "ls": 0, "ic": 0}
         self.lines = 0
         self.batches = 0
 
@@ -61,7 +61,7 @@ class CpuOracleEngine:
         P = self.P
         return {"transactions": P.tx_out, "audit_db": P.audit_db, "db": P.tx_db, "st": P.stats, "fs": P.fs,
                 "al": P.al, "lh": P.lh, "wp": P.wp, "sl": P.sl, "tk": P.tk,
-                "sv": P.sv, "rw": P.rw, "sb": P.sb, "tf": P.tf, "po": P.po, "ls": P.ls}[kind]
+                "sv": P.sv, "rw": P.rw, "sb": P.sb, "tf": P.tf, "po": P.po, "ls": P.ls, "ic": P.ic}[kind]
 
     def take(self, kind: str) -> List[str]:
         s = self._stream(kind)

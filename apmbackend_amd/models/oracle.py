@@ -27,11 +27,11 @@ from collections import OrderedDict
 from typing import Any, Callable, Dict, Iterable, List, Optional, Tuple
 
 from ..utils import jsfmt
-from ..utils.config import (as_bool, check_latency_shift, latency_shift, check_peer_outliers, check_recent_windows, check_slo_burn, check_traffic_watch,
+from ..utils.config import (as_bool, check_incidents, incidents, check_latency_shift, latency_shift, check_peer_outliers, check_recent_windows, check_slo_burn, check_traffic_watch,
                             gpu_opt, peer_outliers, slo_burn,
                             latency_objectives, leaderboard, recent_windows, service_window, traffic_watch,
                             window_percentiles, zscore_lag_settings)
-from ..utils.records import (AlertEntry, FullStatEntry, LatencyHistEntry, LatencyShiftEntry, LeaderboardEntry, PeerEntry, RecentWindowEntry,
+from ..utils.records import (AlertEntry, FullStatEntry, IncidentEntry, LatencyHistEntry, LatencyShiftEntry, LeaderboardEntry, PeerEntry, RecentWindowEntry,
                              ServiceWindowEntry, SloBurnEntry, TrafficEntry,
                              StatEntry, TxEntry, WindowPctEntry, WindowSloEntry, entry_from_csv, hist_bin, hist_lower,
                              pct_ranks)
@@ -683,7 +683,12 @@ class StatsOracle:
                  emit_burn: Optional[Callable[[str], None]] = None, burn: Optional[Dict[str, Any]] = None,
                  emit_traffic: Optional[Callable[[str], None]] = None, traffic: Optional[Dict[str, Any]] = None,
                  emit_peer: Optional[Callable[[str], None]] = None, peer: Optional[Dict[str, Any]] = None,
-                 emit_shift: Optional[Callable[[str], None]] = None, shift: Optional[Dict[str, Any]] = None):
+                 emit_shift: Optional[Callable[[str], None]] = None, shift: Optional[Dict[str, Any]] = None,
+                 emit_incident: Optional[Callable[[str], None]] = None, incident: Optional[Dict[str, Any]] = None):
+        self.emit_incident = emit_incident  # ic rows (docs/INCIDENTS.md); None = stream off
+        self.incident = incident            # config.parse_incidents' result
+        # (server, service, source) -> [code0 or "", since_ts, age, hot_run, clear_run]
+        self.incident_state: Dict[Tuple[str, str, str], List[Any]] = {}
         self.emit_shift = emit_shift  # ls rows (docs/SHIFT.md); None = stream off
         self.shift = shift            # config.parse_latency_shift's result
         self.emit_peer = emit_peer  # po rows (docs/PEERS.md); None = stream off
@@ -1040,6 +1045,60 @@ class StatsOracle:
         n = sum(len(svc[bk]) for bk in svc if oldest <= bk <= newest)
         return LatencyShiftEntry(edge_ts, server, service, n, min_delta, rules).to_csv()
 
+    @staticmethod
+    def incident_code(source: str, row: Optional[str]) -> str:
+        """The code of one source at this rollover from the row its stream printed for the series
+        ("" = not hot): sb ``B`` for any row; tf / ls the verdict of the lowest-numbered rule that is
+        not N; po its letter."""
+        if row is None:
+            return ""
+        if source == "sb":
+            return "B"
+        e = entry_from_csv(row)
+        if source == "po":
+            return e.verdict if e.verdict in ("H", "L") else ""
+        for r in e.rules:
+            if r[-1] != "N":
+                return r[-1]
+        return ""
+
+    def incident_rows(self, edge_ts: int, codes: "OrderedDict[Tuple[str, str], Dict[str, str]]") -> List[str]:
+        """One step of every (series, source) incident and the rows of the steps with an event.
+        ``codes``: per series with an st row, in st order, its code per configured source.  This
+        oracle prints an st row for every series it has ever seen, at every rollover, so every state
+        it holds is stepped here, in st order: the "series without an st row" of docs/INCIDENTS.md
+        cannot occur in it."""
+        ic = self.incident
+        remind = ic["remindEvery"]
+        rows = []
+        for server, service in codes:
+            for src, (open_after, close_after) in ic["sources"].items():
+                code = codes.get((server, service), {}).get(src, "")
+                st = self.incident_state.setdefault((server, service, src), ["", 0, 0, 0, 0])
+                hot = code != ""
+                was_open = st[0] != ""
+                if hot:
+                    st[3], st[4] = min(st[3] + 1, 255), 0
+                else:
+                    st[4], st[3] = min(st[4] + 1, 255), 0
+                event = ""
+                if not was_open:
+                    if hot and st[3] >= open_after:
+                        st[0], st[1], st[2] = code, edge_ts, 0
+                        event = "O"
+                else:
+                    st[2] = min(st[2] + 1, 2 ** 32 - 1)
+                    if not hot and st[4] >= close_after:
+                        event = "C"
+                    elif remind and st[2] % remind == 0:
+                        event = "S"
+                if event:
+                    rows.append(IncidentEntry(edge_ts, server, service, src, event, st[0], code or "-", st[1], st[2],
+                                              st[3] if hot else st[4]).to_csv())
+                if event == "C":
+                    st[0] = ""
+        return rows
+
     def rollover(self, prev: Optional[int] = None):
         self.rollovers += 1
         for srv in self.servers.values():
@@ -1055,6 +1114,8 @@ class StatsOracle:
         st_rows: List[str] = []
         svc_wins: "OrderedDict[str, List[List[int]]]" = OrderedDict()
         peer_members: List[Tuple[str, str, int, int]] = []
+        ic_codes: "OrderedDict[Tuple[str, str], Dict[str, str]]" = OrderedDict()
+        ic_src = self.incident["sources"] if self.emit_incident is not None else {}
         for server, srv in self.servers.items():
             for service, svc in srv.items():
                 win: List[List[int]] = []
@@ -1092,20 +1153,28 @@ class StatsOracle:
                 if self.emit_recent is not None and cnt != 0:
                     for row in self.recent_rows(edge_ts, server, service, svc):
                         self.emit_recent(row)
+                if self.emit_incident is not None:
+                    ic_codes[(server, service)] = {}
                 if self.emit_burn is not None:
                     row = self.burn_row(edge_ts, server, service, svc)
                     if row is not None:
                         self.emit_burn(row)
+                    if "sb" in ic_src:
+                        ic_codes[(server, service)]["sb"] = self.incident_code("sb", row)
                 if self.emit_traffic is not None:
                     row = self.traffic_row(edge_ts, server, service, svc)
                     if row is not None:
                         self.emit_traffic(row)
+                    if "tf" in ic_src:
+                        ic_codes[(server, service)]["tf"] = self.incident_code("tf", row)
                 if self.emit_peer is not None:
                     peer_members.append((server, service) + self.peer_member(win))
                 if self.emit_shift is not None:
                     row = self.shift_row(edge_ts, server, service, svc)
                     if row is not None:
                         self.emit_shift(row)
+                    if "ls" in ic_src:
+                        ic_codes[(server, service)]["ls"] = self.incident_code("ls", row)
         if self.emit_top is not None:
             for row in self.top_rows(st_rows):
                 self.emit_top(row)
@@ -1115,6 +1184,12 @@ class StatsOracle:
         if self.emit_peer is not None:
             for row in self.peer_rows(edge_ts, peer_members):
                 self.emit_peer(row)
+                if "po" in ic_src:
+                    e = entry_from_csv(row)
+                    ic_codes[(e.server, e.service)]["po"] = self.incident_code("po", row)
+        if self.emit_incident is not None:
+            for row in self.incident_rows(edge_ts, ic_codes):
+                self.emit_incident(row)
 
 
 # ----------------------------------------------------------------------------- z-score oracle
@@ -1351,6 +1426,7 @@ class PipelineOracle:
         self.tf: List[str] = []
         self.po: List[str] = []
         self.ls: List[str] = []
+        self.ic: List[str] = []
         g = cfg.get("gpu", {})
         self.zs = ZScoreOracle(cfg, self._on_fs, g.get("emulateOverrideAliasing", False),
                                g.get("zscoreSigma", "sqrt_mean"))
@@ -1363,6 +1439,7 @@ class PipelineOracle:
         check_traffic_watch(traffic_watch(cfg), int(sc["windowSizeInIntervals"]))  # (likewise)
         check_peer_outliers(peer_outliers(cfg))
         check_latency_shift(latency_shift(cfg), int(sc["windowSizeInIntervals"]))  # (as check_traffic_watch)
+        check_incidents(incidents(cfg), cfg)
         self.st = StatsOracle(self._on_st, self.tx_db.append, int(sc["intervalLengthInSeconds"]),
                               int(sc["windowSizeInIntervals"]), int(sc["bufferSizeInIntervals"]),
                               emit_hist=self.lh.append if as_bool(gpu_opt(cfg, "latencyHistogram")) else None,
@@ -1380,7 +1457,8 @@ class PipelineOracle:
                               emit_burn=self.emit_burn if slo_burn(cfg) else None, burn=slo_burn(cfg),
                               emit_traffic=self.tf.append if traffic_watch(cfg) else None, traffic=traffic_watch(cfg),
                               emit_peer=self.po.append if peer_outliers(cfg) else None, peer=peer_outliers(cfg),
-                              emit_shift=self.ls.append if latency_shift(cfg) else None, shift=latency_shift(cfg))
+                              emit_shift=self.ls.append if latency_shift(cfg) else None, shift=latency_shift(cfg),
+                              emit_incident=self.ic.append if incidents(cfg) else None, incident=incidents(cfg))
         self.parse = ParseOracle(self._on_tx, tz, g.get("recordTtlSeconds", 120),
                                  g.get("acctTtlSeconds", 120), g.get("needTtlSeconds", 30), server_fn=server_fn)
 

@@ -22,7 +22,7 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 from .. import _native
 from ..models.oracle import file_kind, server_of
 from ..ops.parse_ref import tz_table
-from ..utils.config import (LEADERBOARD_KEYS, burn_tables, check_latency_shift, check_peer_outliers, check_recent_windows,
+from ..utils.config import (LEADERBOARD_KEYS, burn_tables, check_incidents, incident_tables, incidents, check_latency_shift, check_peer_outliers, check_recent_windows,
                             check_slo_burn, latency_shift, shift_tables,
                             check_traffic_watch, latency_objectives, leaderboard, peer_outliers, peer_tables, recent_windows, service_window, slo_burn, slo_tables,
                             traffic_tables, traffic_watch, window_percentiles)
@@ -55,13 +55,16 @@ FULL_OUT_KINDS = STREAM_OUT_KINDS + ("sb",)
 EVERY_OUT_KINDS = FULL_OUT_KINDS + ("tf",)
 # ... and tests/test_traffic_*.py pin EVERY_OUT_KINDS; WHOLE_OUT_KINDS is engine.h's OutKind up to po.
 WHOLE_OUT_KINDS = EVERY_OUT_KINDS + ("po",)
-# ... and tests/test_peers_*.py pin WHOLE_OUT_KINDS; COMPLETE_OUT_KINDS is engine.h's OutKind in full and
-# the tuple a stream's bit index comes from.
+# ... and tests/test_peers_*.py pin WHOLE_OUT_KINDS; COMPLETE_OUT_KINDS is engine.h's OutKind up to ls.
 COMPLETE_OUT_KINDS = WHOLE_OUT_KINDS + ("ls",)
+# ... and tests/test_shift_*.py pin COMPLETE_OUT_KINDS; TOTAL_OUT_KINDS is engine.h's OutKind in full and
+# the tuple a stream's bit index comes from.
+TOTAL_OUT_KINDS = COMPLETE_OUT_KINDS + ("ic",)
 # keep_text=True materialises these; lh (K15 latency histograms), wp (K16 window percentiles),
 # sl (K17 threshold counts), tk (K18 leaderboards), sv (K19 per-service window stats), rw (K20
 # stats of the newest window buckets), sb (K21 SLO burn-rate breaches), tf (K22 traffic drops and
-# surges), po (K23 peer-outlier servers) and ls (K24 latency shifts) are opt-in through `outputs` only
+# surges), po (K23 peer-outlier servers), ls (K24 latency shifts) and ic (K25 incidents) are opt-in through
+# `outputs` only
 KEEP_TEXT_KINDS = tuple(k for k in OUT_KINDS if k != "lh")
 # What the reference persists (db_insert queue): released + audit tx, fs, al.  `transactions`
 # and `st` are internal hand-offs that only the AMQP bridge needs.
@@ -72,14 +75,14 @@ MAX_LAGS = 16  # apm_types.h MAX_LAGS: LAG capacity per engine (each LAG is an H
 def output_mask(kinds) -> int:
     m = 0
     for k in kinds:
-        m |= 1 << COMPLETE_OUT_KINDS.index(k)
+        m |= 1 << TOTAL_OUT_KINDS.index(k)
     return m
 
 
 def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False, outputs=None,
                   tz: Optional[TzOffset] = None, tz_centre_ms: Optional[int] = None, **kw) -> Dict[str, Any]:
     """Engine settings from the reference config keys + the `gpu` section.  keep_text=True
-    materialises every stream but the opt-in lh / wp / sl / tk / sv / rw / sb / tf / po / ls; `outputs` (iterable of COMPLETE_OUT_KINDS) selects explicitly.
+    materialises every stream but the opt-in lh / wp / sl / tk / sv / rw / sb / tf / po / ls / ic; `outputs` (iterable of TOTAL_OUT_KINDS) selects explicitly.
     The two add up: keep_text=True with outputs=("lh",) is every stream (before the lh stream
     existed, `outputs` was ignored under keep_text).  "wp" takes its percentiles from
     gpu.windowPercentiles (ValueError when the list is missing or malformed), "sl" its thresholds
@@ -88,7 +91,7 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
     bound of a span against windowSizeInIntervals is checked where an engine is constructed, not here: a
     reload reads the settings through this function too), "sb" its objectives and rules from gpu.sloBurn
     (likewise, the bound of a rule's span included), "tf" its classes and rules from gpu.trafficWatch
-    (likewise), "po" its percentile, classes and ratios from gpu.peerOutliers (likewise), "ls" its classes and rules from gpu.latencyShift (likewise).  `tz` (a TzOffset) stands in for gpu.timezone; the zone's
+    (likewise), "po" its percentile, classes and ratios from gpu.peerOutliers (likewise), "ls" its classes and rules from gpu.latencyShift (likewise), "ic" its sources from gpu.incidents (likewise; every source it names must be in `outputs` too).  `tz` (a TzOffset) stands in for gpu.timezone; the zone's
     transition table is centred on `tz_centre_ms` (default: the wall clock now, see
     ops.parse_ref.tz_table)."""
     g = cfg.get("gpu", {})
@@ -123,6 +126,15 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
     if "ls" in (outputs or ()) and not shift:
         raise ValueError('outputs names "ls" but gpu.latencyShift is not set')
     ls_classes, ls_services, ls_default = shift_tables(shift)
+    ic = incidents(cfg)
+    if "ic" in (outputs or ()):
+        if not ic:
+            raise ValueError('outputs names "ic" but gpu.incidents is not set')
+        check_incidents(ic, cfg)
+        for name in ic["sources"]:
+            if name not in outputs:
+                raise ValueError(f'outputs names "ic" and gpu.incidents the source {name!r}, but outputs does not name {name!r}')
+    ic_open, ic_close = incident_tables(ic)
     # (the spans' bound against the window holds at construction only -- APMEngine.__init__ and the
     # native constructor: a reload may shorten the window below a span, which then reads all of it)
     zc = cfg["streamCalcZScore"]
@@ -251,6 +263,10 @@ def engine_config(cfg: Dict[str, Any], device: int = 0, keep_text: bool = False,
         "ls_z": [r[4] for r in shift["rules"]] if shift else [],
         "ls_min_recent": shift["minRecent"] if shift else 20,
         "ls_min_baseline": shift["minBaseline"] if shift else 100,
+        # K25: openAfter / closeAfter per source (sb, tf, po, ls; 0: not configured) and remindEvery, likewise
+        "ic_open_after": ic_open,
+        "ic_close_after": ic_close,
+        "ic_remind_every": ic["remindEvery"] if ic else 0,
     }
     # intervalLengthInSeconds only scales the TPM divisor: the bucket label is endTs without its
     # last 4 digits whatever the interval (stream_calc_stats.js:89-96, :186), as here
@@ -317,6 +333,7 @@ class APMEngine:
         check_traffic_watch(traffic_watch(cfg), int(cfg["streamCalcStats"]["windowSizeInIntervals"]))  # K22: likewise
         check_peer_outliers(peer_outliers(cfg))  # K23 (no setting depends on the window)
         check_latency_shift(latency_shift(cfg), int(cfg["streamCalcStats"]["windowSizeInIntervals"]))  # K24: as K22
+        check_incidents(incidents(cfg), cfg)  # K25: a source needs its own stream configured
         self.N = _native.load()
         # the engine's zone (tz, else gpu.timezone as read now) and the time its transition table is
         # centred on (the wall clock at construction).  Both are kept: the zone is not applied live,
@@ -340,7 +357,7 @@ class APMEngine:
     @classmethod
     def restart_required(cls, old: Dict[str, Any], new: Dict[str, Any]) -> List[str]:
         """The engine settings that differ between two engine_config results and are not applied
-        live (win_pcts, the slo_* tables, the tk_* settings, svc_pcts, rw_buckets, rw_pcts, the sb_*, tf_*, po_* and ls_* settings, ...)."""
+        live (win_pcts, the slo_* tables, the tk_* settings, svc_pcts, rw_buckets, rw_pcts, the sb_*, tf_*, po_*, ls_* and ic_* settings, ...)."""
         return sorted(k for k in new if k not in cls.LIVE_KEYS and k not in ("outputs", "tz_table")
                       and new[k] != old.get(k))
 

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import datetime as _dt
 import email.utils
+import html
 import json
 import logging
 import os
@@ -33,7 +34,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple
 
 from ..utils.config import as_bool
 from ..utils.jsfmt import to_fixed
-from ..utils.records import AlertEntry, entry_from_csv
+from ..utils.records import AlertEntry, IncidentEntry, entry_from_csv
 
 log = logging.getLogger("apm.alerts")
 
@@ -71,6 +72,20 @@ def format_alerts_html(alerts: List[AlertEntry]) -> str:
                     f'<td class="bbcenter">{_fx1(e.average)}</td><td class="bbcenter">{_fx1(e.averageUB)}</td>'
                     f'<td class="bbcenter">{_fx1(e.per75)}</td><td class="bbcenter">{_fx1(e.per75UB)}</td></tr>')
     return css + header + "".join(rows) + "</table>"
+
+
+def format_incidents_html(incidents: List[IncidentEntry]) -> str:
+    """The "Incidents" block of a mail (docs/INCIDENTS.md): one line per opened / closed incident --
+    time, server, service, source, event, codes, and for a close how long it was open."""
+    lines = []
+    for e in incidents:
+        what = "opened" if e.event == "O" else "closed" if e.event == "C" else "still open"
+        codes = e.code0 if e.code in ("-", e.code0) else f"{e.code0} (now {e.code})"
+        ln = f"{log_date(e.timestamp)}  {html.escape(e.server)}  {html.escape(e.service)}  {e.source}  {what}  {codes}"
+        if e.event == "C":
+            ln += f"  after {to_fixed(max(0, e.timestamp - e.since) / 60000.0, 1)} minutes (since {log_date(e.since)})"
+        lines.append(ln)
+    return "<pre>\n<b>Incidents</b>\n" + "\n".join(lines) + "\n</pre>"
 
 
 def grafana_url_params(alerts: List[AlertEntry], now_ms: float, grafana: Dict[str, Any]) -> Tuple[str, int]:
@@ -219,6 +234,7 @@ class AlertNotifier:
         self.clock = clock
         self.renderer = renderer
         self.buffer: List[AlertEntry] = []
+        self.incidents: List[IncidentEntry] = []  # K25 ic rows (O and C) when gpu.incidents.email is set
         self.base = self._ac()["alertCollectionIntervalInSeconds"]
         self.interval = float(self.base)
         self.next_due = clock() + self.interval
@@ -257,9 +273,23 @@ class AlertNotifier:
             if ln:
                 self.add_line(ln)
 
+    def add_incident_lines(self, lines):
+        """ic rows: incidents that opened or closed wait for the next mail (reminders do not)."""
+        for ln in lines:
+            e = entry_from_csv(ln) if ln else None
+            if isinstance(e, IncidentEntry) and e.event in ("O", "C"):
+                self.incidents.append(e)
+
+    def build_incident_email(self, interval_s: float) -> str:
+        """The body of a mail without alerts: the Incidents block and the cooldown line."""
+        return (format_incidents_html(self.incidents) +
+                f"<pre>\nCooldown until further alerts are sent out: {to_fixed(interval_s / 60, 0)} minutes\n</pre>")
+
     def build_email(self, now_ms: float, interval_s: float) -> Tuple[str, str]:
         grafana = self.cfg.get("grafana", {})
         body = format_alerts_html(self.buffer)
+        if self.incidents:
+            body += format_incidents_html(self.incidents)
         url, render_url = grafana_urls(self.buffer, now_ms, grafana)
         lh = url.replace(grafana.get("grafanaHostname", "") or "\0", "localhost")
         body += (f'<pre>\n\n<a href="{lh}">(Citi) View Alert Graphs</a> - <i>Requires tunnel</i>\n'
@@ -276,14 +306,21 @@ class AlertNotifier:
         ac = self._ac()
         sent = False
         interval = float(self.base)
-        if self.buffer and as_bool(ac.get("emailsEnabled", True)):
+        if (self.buffer or self.incidents) and as_bool(ac.get("emailsEnabled", True)):
             interval = self.interval
             if as_bool(ac.get("increaseCollectionIntervalAfterAlert", False)):
                 if interval < float(ac.get("maxCollectionIntervalInSeconds", 3840)):
                     interval *= 2
                     log.info("Increasing alert collection interval to %s seconds.", interval)
-            body, render_url = self.build_email(now * 1000.0, interval)
             frm = ac.get("fromEmail", "apm@localhost")
+            if not self.buffer:  # incidents only: no alert table and no graph to render
+                self.mailer.send(frm, ac.get("emailList", ""), "APM Incidents", self.build_incident_email(interval))
+                self.incidents = []
+                self.emails += 1
+                self.interval = interval
+                self.next_due = now + interval
+                return True
+            body, render_url = self.build_email(now * 1000.0, interval)
             try:
                 img = self.renderer(render_url, self.cfg.get("grafana", {}))
                 self.mailer.send(frm, ac.get("emailList", ""), "APM Alerts Triggered!", body, img)
@@ -291,6 +328,7 @@ class AlertNotifier:
                 log.error("Error while trying to render graph: %s", e)
                 self.mailer.send(frm, ac.get("testEmailList", ac.get("emailList", "")), "APM Alerts Triggered!", body)
             self.buffer = []
+            self.incidents = []
             self.emails += 1
             sent = True
         self.interval = interval

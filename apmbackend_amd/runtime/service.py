@@ -38,9 +38,9 @@ import time
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 from ..models.oracle import file_kind, server_of
-from ..models.pipeline import COMPLETE_OUT_KINDS, DB_OUTPUTS, KIND_CODE, APMEngine
+from ..models.pipeline import TOTAL_OUT_KINDS, DB_OUTPUTS, KIND_CODE, APMEngine
 from ..parallel.dist import dist_env, shard_servers
-from ..utils.config import (ConfigWatcher, as_bool, gpu_opt, latency_objectives, latency_shift, leaderboard, peer_outliers,
+from ..utils.config import (ConfigWatcher, as_bool, check_incidents, gpu_opt, incidents, latency_objectives, latency_shift, leaderboard, peer_outliers,
                             read_apm_config,
                             recent_windows, service_window, slo_burn, traffic_watch, window_percentiles)
 from . import logger as apmlog
@@ -169,16 +169,21 @@ class IngestService:
             outs.add("po")
         if latency_shift(self.cfg):  # K24 latency shifts against the window's own past (ValueError on a malformed object)
             outs.add("ls")
+        ic = incidents(self.cfg)  # K25 incidents over the sb / tf / po / ls verdicts (ValueError on a malformed object)
+        check_incidents(ic, self.cfg)  # (... or on a source whose own stream is not configured)
+        self.ic_email = bool(ic and ic["email"])
+        if ic:
+            outs.add("ic")
         if self.world > 1 and engine == "native" and as_bool(g.get("fleetBaseline", True)) \
                 and as_bool(g.get("fleetBaselineRows", True)):
             outs.add("fb")  # fleet-merged per-service baselines (rank 0 emits them)
         if self.mode == "amqp":
             outs |= {"transactions" if "transactions" in self.bridge else "", "st" if "stats" in self.bridge else ""}
             outs.discard("")
-        self.outputs = [k for k in COMPLETE_OUT_KINDS if k in outs]
+        self.outputs = [k for k in TOTAL_OUT_KINDS if k in outs]
         self.outs_set = set(self.outputs)
         if self.mode == "amqp" and "z_score" in self.bridge:
-            self.outputs = [k for k in COMPLETE_OUT_KINDS if k in set(self.outputs) | {"fs"}]
+            self.outputs = [k for k in TOTAL_OUT_KINDS if k in set(self.outputs) | {"fs"}]
         if engine == "native":
             self.eng = APMEngine(self.cfg, device=self.local_rank, outputs=self.outputs)
             self.native = self.eng.eng
@@ -309,6 +314,8 @@ class IngestService:
                 self.producers["peers"] = self.qm.get_queue(gpu_opt(self.cfg, "peerQueue"), "p")
             if "ls" in self.outs_set:
                 self.producers["shift"] = self.qm.get_queue(gpu_opt(self.cfg, "shiftQueue"), "p")
+            if "ic" in self.outs_set:
+                self.producers["incidents"] = self.qm.get_queue(gpu_opt(self.cfg, "incidentQueue"), "p")
             self.qm.on("pause", lambda: log.info("queue backpressure: pausing ingest"))
         elif self.mode != "none":
             raise ValueError(f"unknown gpu.outputMode {self.mode!r}")
@@ -862,7 +869,9 @@ class IngestService:
             counts[k] = blob.count(b"\n")
             if k == "al" and self.notifier:
                 self.notifier.add_lines(blob.decode("utf-8").split("\n"))
-            if self.inserter is not None and (k in DB_OUTPUTS or k in ("fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls")):
+            if k == "ic" and self.notifier and self.ic_email:  # (its O and C rows; gpu.incidents.email)
+                self.notifier.add_incident_lines(blob.decode("utf-8").split("\n"))
+            if self.inserter is not None and (k in DB_OUTPUTS or k in ("fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls", "ic")):
                 self.inserter.consume_bytes(blob)
             elif self.qm is not None:
                 if k == "fb":
@@ -887,6 +896,8 @@ class IngestService:
                     prod = self.producers.get("peers")
                 elif k == "ls":
                     prod = self.producers.get("shift")
+                elif k == "ic":
+                    prod = self.producers.get("incidents")
                 elif k in DB_OUTPUTS:
                     prod = self.producers["db"]
                 elif k == "transactions":

@@ -75,13 +75,16 @@ COLUMNS: Dict[str, Tuple[str, List[str]]] = {
                            "verdict"]),
     # latency shifts against the window's own past (ls records, gpu.latencyShift): likewise
     "ls": ("dbShiftTable", ["timestamp", "server", "service", "count", "min_delta", "rules"]),
+    # incidents opened and closed over the sb / tf / po / ls verdicts (ic records, gpu.incidents): likewise
+    "ic": ("dbIncidentTable", ["timestamp", "server", "service", "source", "event", "code0", "code", "since", "age",
+                               "run"]),
 }
-TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls")
+TYPES = ("tx", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls", "ic")
 # tables of the record types the reference does not know (its config has no key for them)
 DEFAULT_TABLES = {"fb": "apm_fleet_stats", "lh": "apm_latency_hist", "wp": "apm_window_pct", "sl": "apm_window_slo",
                   "tk": "apm_leaderboard", "sv": "apm_service_window", "rw": "apm_recent_window",
                   "sb": "apm_slo_burn", "tf": "apm_traffic", "po": "apm_peer_outlier",
-                  "ls": "apm_latency_shift"}
+                  "ls": "apm_latency_shift", "ic": "apm_incident"}
 
 
 # --------------------------------------------------------------------------- COPY text encoding
@@ -169,7 +172,7 @@ def pg_row_from_copy(rtype: str, row: str) -> Dict[str, Any]:
             out[c] = _dt.datetime.strptime(v[:-3], "%Y-%m-%d %H:%M:%S.%f").replace(tzinfo=_dt.timezone.utc)
         elif c in ("stats", "entry", "bins", "pcts", "le", "rules"):
             out[c] = json.loads(v)
-        elif c in ("servers", "buckets", "elapsed_sum", "threshold", "target_q", "bad", "min_rate", "min_delta", "value2", "peers", "median2x2", "mad4"):  # (sv, rw, sb: plain integers; the sum may pass 2^53)
+        elif c in ("servers", "buckets", "elapsed_sum", "threshold", "target_q", "bad", "min_rate", "min_delta", "value2", "peers", "median2x2", "mad4", "age", "run"):  # (sv, rw, sb: plain integers; the sum may pass 2^53)
             out[c] = int(v)
         elif c in ("tpm", "elapsed", "acctnum", "nseries", "count", "nan", "rank", "average", "per75", "per95") or rtype == "jx" and c not in ("server",):
             f = float(v)
@@ -375,7 +378,7 @@ def _json_row(r: Any) -> Any:
     return r
 
 
-_TS_COLS = {"endts", "startts", "timestamp", "entrytimestamp", "alerttimestamp"}
+_TS_COLS = {"endts", "startts", "timestamp", "entrytimestamp", "alerttimestamp", "since"}
 
 
 def load_resume(path: str) -> Dict[str, List[Dict[str, Any]]]:

@@ -106,6 +106,8 @@ GPU_OPTIONAL: Dict[str, Any] = {
     "peerQueue": "peer_outliers",     # amqp mode: the queue the po records go to
     "latencyShift": None,             # K24 "ls" stream: latency shifts of a series' newest buckets against the rest of its own window, {"default": {"minDelta": 50}, "services": {...}, "rules": [{"short": 6, "percentile": 95, "up": 3, "z": 4}], "minRecent": 20, "minBaseline": 100} (docs/SHIFT.md)
     "shiftQueue": "latency_shift",    # amqp mode: the queue the ls records go to
+    "incidents": None,                # K25 "ic" stream: incidents opened and closed over the sb / tf / po / ls verdicts, {"sources": {"sb": {"openAfter": 2, "closeAfter": 6}, ...}, "remindEvery": 90, "email": true} (docs/INCIDENTS.md)
+    "incidentQueue": "incidents",     # amqp mode: the queue the ic records go to
 }
 
 def gpu_opt(cfg: Dict[str, Any], key: str) -> Any:
@@ -897,6 +899,87 @@ def shift_tables(ls: Optional[Dict[str, Any]]) -> Tuple[List[List[int]], Dict[st
     return classes, services, default_class
 
 
+INCIDENT_SOURCES = ("sb", "tf", "po", "ls")   # incidentcmp.h IC_SB .. IC_LS, the order of a series' rows
+# the gpu key of each source's own stream
+INCIDENT_SOURCE_KEYS = {"sb": "sloBurn", "tf": "trafficWatch", "po": "peerOutliers", "ls": "latencyShift"}
+INCIDENT_RUN_MAX = 255        # the runs saturate there (incidentcmp.h)
+INCIDENT_REMIND_MAX = 65535
+
+
+def _incident_int(where: str, v: Any, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError(f"gpu.incidents: {where} {v!r} is not an integer")
+    if not lo <= v <= hi:
+        raise ValueError(f"gpu.incidents: {where} {v!r} is outside {lo} .. {hi}")
+    return int(v)
+
+
+def parse_incidents(v: Any) -> Optional[Dict[str, Any]]:
+    """gpu.incidents -> {"sources": {name: (openAfter, closeAfter)}, "remindEvery": n, "email": bool}.
+    ``sources`` holds one to four of sb, tf, po, ls, each an object with ``openAfter`` and
+    ``closeAfter``, JSON integers in 1 .. 255 (bool, float and str are rejected); ``remindEvery`` a
+    JSON integer, 0 (never, the default) or 1 .. 65535 rollovers; ``email`` a JSON boolean (default
+    false).  Unknown members at any level raise ValueError.  None -> None (stream off).  That a named
+    source's own stream is configured is check_incidents' part."""
+    if v is None:
+        return None
+    if not isinstance(v, dict):
+        raise ValueError(f"gpu.incidents: an object with 'sources', got {v!r}")
+    extra = set(v) - {"sources", "remindEvery", "email"}
+    if extra:
+        raise ValueError(f"gpu.incidents: unknown key(s) {sorted(extra, key=str)!r}")
+    sources = v.get("sources")
+    if not isinstance(sources, dict) or not sources:
+        raise ValueError(f"gpu.incidents: sources must be an object naming one to four of {', '.join(INCIDENT_SOURCES)}, "
+                         f"got {sources!r}")
+    out: Dict[str, Tuple[int, int]] = {}
+    for name in INCIDENT_SOURCES:  # (the result's order is the rows' order, whatever the config's)
+        if name not in sources:
+            continue
+        o = sources[name]
+        if not isinstance(o, dict):
+            raise ValueError(f"gpu.incidents: sources[{name!r}] must be an object with 'openAfter' and 'closeAfter', got {o!r}")
+        extra = set(o) - {"openAfter", "closeAfter"}
+        if extra:
+            raise ValueError(f"gpu.incidents: sources[{name!r}]: unknown key(s) {sorted(extra, key=str)!r}")
+        if "openAfter" not in o or "closeAfter" not in o:
+            raise ValueError(f"gpu.incidents: sources[{name!r}] needs 'openAfter' and 'closeAfter', got {o!r}")
+        out[name] = (_incident_int(f"sources[{name!r}]: openAfter", o["openAfter"], 1, INCIDENT_RUN_MAX),
+                     _incident_int(f"sources[{name!r}]: closeAfter", o["closeAfter"], 1, INCIDENT_RUN_MAX))
+    extra = set(sources) - set(INCIDENT_SOURCES)
+    if extra:
+        raise ValueError(f"gpu.incidents: sources: unknown source(s) {sorted(extra, key=str)!r}")
+    remind = _incident_int("remindEvery", v.get("remindEvery", 0), 0, INCIDENT_REMIND_MAX)
+    email = v.get("email", False)
+    if not isinstance(email, bool):
+        raise ValueError(f"gpu.incidents: email {email!r} is not a boolean")
+    return {"sources": out, "remindEvery": remind, "email": email}
+
+
+def incidents(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """The validated gpu.incidents object of a config (None: off)."""
+    return parse_incidents(gpu_opt(cfg, "incidents"))
+
+
+def check_incidents(ic: Optional[Dict[str, Any]], cfg: Dict[str, Any]) -> None:
+    """What a config, a service and an engine ask of gpu.incidents beyond its own shape: every named
+    source's own stream is configured (sb needs gpu.sloBurn, ...)."""
+    if not ic:
+        return
+    parsers = {"sb": slo_burn, "tf": traffic_watch, "po": peer_outliers, "ls": latency_shift}
+    for name in ic["sources"]:
+        if not parsers[name](cfg):
+            raise ValueError(f"gpu.incidents: source {name!r} needs gpu.{INCIDENT_SOURCE_KEYS[name]} to be set")
+
+
+def incident_tables(ic: Optional[Dict[str, Any]]) -> Tuple[List[int], List[int]]:
+    """(openAfter, closeAfter) per source in the order sb, tf, po, ls as the engine takes them; 0 / 0
+    for a source that is not configured."""
+    src = ic["sources"] if ic else {}
+    return ([src[k][0] if k in src else 0 for k in INCIDENT_SOURCES],
+            [src[k][1] if k in src else 0 for k in INCIDENT_SOURCES])
+
+
 _BOOL_STRINGS = {"true": True, "false": False, "1": True, "0": False, "yes": True, "no": False}
 
 
@@ -946,6 +1029,8 @@ def read_apm_config(path: Optional[str] = None, first_run: bool = False) -> Opti
         parse_peer_outliers(merged["peerOutliers"])  # likewise
     if "latencyShift" in merged:
         parse_latency_shift(merged["latencyShift"])  # likewise
+    if "incidents" in merged:
+        check_incidents(parse_incidents(merged["incidents"]), cfg)  # likewise; a source needs its own stream
     return cfg
 
 

@@ -743,6 +743,45 @@ class LatencyShiftEntry:
                           for k, q, mb, t2, mr, x2, a, b, v in self.rules]}
 
 
+# ---- ic: incidents opened and closed over the sb / tf / po / ls verdicts (docs/INCIDENTS.md).
+INCIDENT_SOURCES = ("sb", "tf", "po", "ls")
+INCIDENT_EVENTS = ("O", "S", "C")
+INCIDENT_CODES = ("B", "D", "S", "H", "L", "U")
+INCIDENT_SINCE_MAX = 253402300799999  # the last ms of the year 9999
+
+
+@dataclass
+class IncidentEntry:
+    """``ic|ts|server|service|source|event|code0|code|since|age|run`` -- at a rollover, an incident of
+    one series and one source (sb, tf, po, ls) opened (``O``), is still open at a reminder step
+    (``S``) or closed (``C``): ``code0`` is the code it opened with, ``code`` this rollover's (``-``
+    when the source is not hot), ``since`` the timestamp of the rollover that opened it, ``age`` the
+    rollovers since then and ``run`` the consecutive hot (or, when not hot, clear) rollovers (no
+    reference counterpart)."""
+    timestamp: Num
+    server: str
+    service: str
+    source: str
+    event: str
+    code0: str
+    code: str
+    since: int
+    age: int
+    run: int
+    type: str = "ic"
+
+    def to_csv(self) -> str:
+        return (f"ic|{js_str(self.timestamp)}|{self.server}|{self.service}|{self.source}|{self.event}|{self.code0}|"
+                f"{self.code}|{int(self.since)}|{int(self.age)}|{int(self.run)}")
+
+    def to_pg_row(self) -> Dict[str, Any]:
+        return {"timestamp": _ms_to_dt(self.timestamp), "server": self.server, "service": self.service,
+                "source": self.source, "event": self.event, "code0": self.code0, "code": self.code,
+                # (integer arithmetic: a float of seconds is a microsecond off near the year 9999)
+                "since": _dt.datetime(1970, 1, 1, tzinfo=_dt.timezone.utc) + _dt.timedelta(milliseconds=int(self.since)),
+                "age": int(self.age), "run": int(self.run)}
+
+
 def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
     """EntryFactory.getEntryFromCSV (entries.js:174-193). Returns None for unknown types."""
     if isinstance(line, bytes):
@@ -867,7 +906,20 @@ def entry_from_csv(line: Union[str, bytes], delim: str = "|"):
         if any(v is None for v in nums) or rules is None:
             return None
         return LatencyShiftEntry(parse_int(arr[1]), arr[2], arr[3], *nums, rules)
+    if t == "ic":
+        # (copyenc.cpp holds the same rules) exactly eleven fields; the source, the event and the two
+        # codes from their sets; since 1 to 15 digits up to the year 9999, age 1 to 10, run 1 to 3;
+        # anything else is dropped
+        if len(arr) != 11:
+            return None
+        if (arr[4] not in INCIDENT_SOURCES or arr[5] not in INCIDENT_EVENTS or arr[6] not in INCIDENT_CODES
+                or arr[7] not in INCIDENT_CODES + ("-",)):
+            return None
+        since, age, run = _svc_int(arr[8], 15), _svc_int(arr[9]), _svc_int(arr[10], 3)
+        if since is None or age is None or run is None or since > INCIDENT_SINCE_MAX:
+            return None
+        return IncidentEntry(parse_int(arr[1]), arr[2], arr[3], arr[4], arr[5], arr[6], arr[7], since, age, run)
     return None
 
 
-RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls")
+RECORD_TYPES = ("tx", "st", "fs", "al", "jx", "fb", "lh", "wp", "sl", "tk", "sv", "rw", "sb", "tf", "po", "ls", "ic")
